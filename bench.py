@@ -93,6 +93,22 @@ def _probe_result(out, res, t0):
     return res
 
 
+def load_built_library(pkg):
+    """dlopen libdqnhip.so without writing to the tree when build() has already made it.  The package's own load takes a
+    write lock in csrc/ before it asks make, which fails where the benchmarked tree is read-only to the user running this
+    (a tree built beforehand and kept fixed, e.g. while another build is compared against it).  `make -q` writes nothing
+    and exits non-zero when the library is missing or older than any of its sources: then the package builds it as usual."""
+    import subprocess
+    capi = pkg.capi
+    if subprocess.run(["make", "-q", "-C", os.path.dirname(capi.LIB)], capture_output=True).returncode != 0:
+        return capi.load()
+    build, capi.build = capi.build, lambda *a, **k: capi.LIB      # up to date: nothing for the locked make to do
+    try:
+        return capi.load()
+    finally:
+        capi.build = build
+
+
 def prefill(dqn, n, seed, chunk=131072):
     from synth import synth_replay
     rng = np.random.default_rng(seed)
@@ -193,6 +209,25 @@ def timed_n(d, sync, n, warm):
     d.update_async_n(n)
     sync()
     return (time.perf_counter() - t0) / n
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dqn, pkg, out_dir):
+    """What a caller of the timed path receives after its last step: (critic loss, avg Q) of that update and the weights of the
+    four nets it leaves behind, as float32 <out_dir>/<name>.npy (4 x 1024: 49 MiB in all, so every weight is written, none sampled)."""
+    loss, avgq = dqn.read_stats()            # (waits for the last update)
+    arrays = {"critic_loss": np.array([loss], np.float32), "avg_q": np.array([avgq], np.float32)}
+    for name, net in (("actor_weights", pkg.ACTOR), ("critic_weights", pkg.CRITIC),
+                      ("actor_target_weights", pkg.ACTOR_TARGET), ("critic_target_weights", pkg.CRITIC_TARGET)):
+        arrays[name] = dqn.get_params(net)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def env_roofline(S_, workers, us_per_step):
@@ -514,7 +549,12 @@ def main():
     ap.add_argument("--no-subrecords", action="store_true", help="skip the per-config sub-records (configs #3, #5; strong scaling under N > 1)")
     ap.add_argument("--mode", default="dp", choices=["dp", "replicas"],
                     help="N>1: dp = gradient all-reduce (weak scaling), replicas = independent learners")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the K timed steps, write what the last one computed (critic loss, avg Q, the four nets' weights) as DIR/<name>.npy; "
+                         "the prewarm then runs a fixed number of updates instead of --prewarm-ms of wall clock, so that equal arguments give equal inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and (args.dp_per_layer or args.dp_shard_opt):
         # the per-layer and sharded exchange forms have never run on more than one rank (dqnhip_dp_init refuses them for real
         # groups); the N-GPU line is measured on the one supported form: replicated optimiser, ONE all-reduce per net
@@ -529,6 +569,7 @@ def main():
 
     import torch
     pkg = load_package()
+    load_built_library(pkg)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -661,9 +702,12 @@ def main():
     # the GPU needs a few tens of milliseconds of load before its clocks settle.  With a short --warmup / --steps
     # pair (the driver has used 5 / 20 = 9 ms in total) the timed region would otherwise sit on that ramp.
     # Reported as config.prewarm_updates; the W warm-up steps and the K timed steps follow unchanged.
+    # --dump-outputs: a fixed count (ten updates per millisecond, about the rate of the current build) instead of the clock, so that
+    # the weights and the sampling counter the timed steps start from do not depend on how fast the build is.
     prewarm = 0
+    prewarm_fixed = 16 * max(1, round(args.prewarm_ms * 10 / 16)) if args.dump_outputs else None
     t_pw = time.perf_counter()
-    while time.perf_counter() - t_pw < args.prewarm_ms * 1e-3 or prewarm < 1:
+    while (prewarm < prewarm_fixed) if prewarm_fixed else (time.perf_counter() - t_pw < args.prewarm_ms * 1e-3 or prewarm < 1):
         steps(16)
         prewarm += 16
         if dist_on:
@@ -675,6 +719,8 @@ def main():
     steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dqn, pkg, args.dump_outputs)
     if args.trace_child:
         print(json.dumps({"trace_child": True, "ms_per_step": elapsed / args.steps * 1e3}), flush=True)
         dqn.close()

@@ -5,9 +5,10 @@ header next to the driver — the same effect as deleting src/dqn.{hpp,cpp} in t
 INTEGRATION.md), together with dqn-hfo_amd/csrc/dqn_dropin.cpp, against include/shim/ (gflags,
 glog, boost, caffe, HFO are absent from this image) and libdqnhip.so.
 
-Output: tests/cpp/_dropin/dqn (git-ignored; it travels to the GPU box with the snapshot, where
-/root/reference does not exist).  This is a source-compatibility / end-to-end demonstration of
-the boundary, NOT an oracle: nothing compares numbers against it.
+Output: oracle/_ref/dropin/dqn, where everything built from the reference lives (git-ignored; it
+travels to the GPU box with the snapshot, where /root/reference does not exist).  This is a
+source-compatibility / end-to-end demonstration of the boundary, NOT an oracle: nothing compares
+numbers against it.
 """
 import os
 import subprocess
@@ -15,7 +16,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/src"
-OUT_DIR = os.path.join(ROOT, "tests", "cpp", "_dropin")
+OUT_DIR = os.path.join(ROOT, "oracle", "_ref", "dropin")
 EXE = os.path.join(OUT_DIR, "dqn")
 INC = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "include", "shim")]
 
@@ -43,7 +44,9 @@ def build(lib):
             if r.returncode:
                 raise RuntimeError("compile %s:\n%s" % (src, r.stderr[-4000:]))
             objs.append(obj)
-        r = subprocess.run(["g++", "-o", EXE] + objs + [lib, "-Wl,-rpath," + os.path.dirname(lib), "-lpthread"],
+        # by name and relative to the binary: the tree is built in one place and run in another (the GPU box's own libdqnhip.so)
+        libdir = os.path.dirname(lib)
+        r = subprocess.run(["g++", "-o", EXE] + objs + ["-L" + libdir, "-ldqnhip", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(libdir, OUT_DIR), "-lpthread"],
                            capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError("link:\n%s" % r.stderr[-4000:])

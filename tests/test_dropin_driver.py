@@ -14,7 +14,7 @@ import subprocess
 
 import pytest
 
-import dropin_build as db
+from oracle import dropin_build as db
 
 ROOT = db.ROOT
 needs_ref = pytest.mark.skipif(not db.reference_present(), reason="/root/reference is only present in the build container")
