@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""bench.py — DQN updates/sec on MI355X (BASELINE.json metric), with the kernel roofline
-and the CPU baseline timed beside it.
+"""bench.py — DQN updates/sec on MI355X (BASELINE.json metric); with --full, also the kernel roofline,
+the CPU baseline and the per-config side records.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,11 @@ target, 2x (clip + Adam), 2x soft target update.  Workload = BASELINE.json confi
 58-dim synthetic states.  N > 1: data-parallel weak scaling — every rank keeps its own
 replay shard and a 256-row local minibatch (global minibatch 256*N), gradients summed by
 RCCL all-reduce; value is reported in minibatch-256 updates/s (= N x global updates/s).
+
+A plain run sets up, warms up, times the K steps, writes what the last one computed (--dump-outputs) and prints the line.  --full
+measures the rest after the K steps: the same steps as one update per graph launch, the roofline (live rocprofv3 child
+passes), the drop-in's blocking forms, env-steps/sec, the CPU baseline and the side records of the other BASELINE configs
+(N > 1: the N = 1 point of the same job, strong scaling).  The headline fields mean the same in both.
 
 Prints ONE JSON line on rank 0.
 """
@@ -506,6 +511,77 @@ def sub_records(pkg, par, args, rank, world, local_rank, native, barrier):
     return out if rank == 0 else None
 
 
+def roofline(dqn, step, args, rank, world):
+    """--full: the roofline of the dominant kernel family, timed live on the learner's stream (rank 0; None elsewhere)"""
+    roof = None
+    n_t = 20
+    # every rank runs the extra updates (under data parallelism they contain collectives); only rank 0
+    # brackets its launches with events
+    if rank == 0:
+        dqn.set_kernel_timing(True)
+    for _ in range(n_t):
+        step()
+    if rank == 0:
+        fp16 = args.precision == "fp16"
+        fam_flops = family_flops16(B, S, HIDDEN) if fp16 else family_flops(B, S, HIDDEN, shifted=not (args.tuning & 4) and B >= 64)
+        peak = MFMA_F16_PEAK_TF if fp16 else MFMA_F32_PEAK_TF
+        stats = {}
+        for fam in list(fam_flops) + ["adam"]:
+            ms, cnt = dqn.kernel_timing(fam)
+            stats[fam] = (ms, cnt)
+        dqn.kernel_timing("adam", reset=True)
+        dqn.set_kernel_timing(False)
+        events_stats = dict(stats)
+        dur_src = "HIP events (hipExtLaunchKernelGGL start / stop) around each launch of %d eager updates after the timed region" % n_t
+        trace = None
+        extra = ["--minibatch", str(B), "--precision", args.precision, "--tuning", str(args.tuning)]
+        if world == 1 and not args.no_live_trace and not args.no_graph:
+            trace, why = live_kernel_trace(extra)
+            if trace is None:
+                dur_src += " [live kernel trace unavailable: %s]" % why
+            else:
+                # fold the traced kernels into the timing families: (mean ms per launch, launches in n_t updates)
+                fam_acc = {}
+                for kname, (us, per_upd) in trace.items():
+                    fam = next((f for pre, f in TRACE_FAMILY if kname.startswith(pre)), None)
+                    if fam is None:
+                        continue
+                    a = fam_acc.setdefault(fam, [0.0, 0.0])
+                    a[0] += us * per_upd; a[1] += per_upd
+                if all(f in fam_acc for f in fam_flops):
+                    stats = {f: ((fam_acc[f][0] / fam_acc[f][1]) * 1e-3, fam_acc[f][1] * n_t) for f in fam_acc}
+                    dur_src = why
+                else:
+                    dur_src += " [live kernel trace lacks families: %s]" % sorted(set(fam_flops) - set(fam_acc))
+                    trace = None
+        dom = max(fam_flops, key=lambda f: stats[f][0] * stats[f][1])
+        ms, cnt = stats[dom]
+        per_update_launches = cnt / n_t
+        flops_per_launch = fam_flops[dom] / per_update_launches
+        ach = flops_per_launch / (ms * 1e-3) / 1e12
+        traffic, traffic_src = (None, None)
+        if world == 1 and not args.no_live_pmc:
+            traffic, traffic_src = live_pmc_traffic(KERNEL_NAMES[dom], extra)
+        if traffic is None:
+            why = traffic_src
+            traffic, traffic_src = pmc_traffic(KERNEL_NAMES[dom])
+            if traffic_src and why:
+                traffic_src += " [live PMC pass unavailable: %s]" % why
+        roof = {"bound": "mfma", "kernel": KERNEL_NAMES[dom], "achieved": round(ach, 2), "peak": peak,
+                "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "avg_launch_us": round(ms * 1e3, 2), "launches_per_update": per_update_launches,
+                "flops_per_launch": flops_per_launch,
+                "duration_source": dur_src,
+                "families_us": {f: [round(stats[f][0] * 1e3, 2), round(stats[f][1] / n_t, 3)] for f in stats},
+                # the same families timed with eager HIP events in this process (a cross-check; differs by a few per cent run to run)
+                "families_us_eager_events": {f: [round(events_stats[f][0] * 1e3, 2), events_stats[f][1] / n_t] for f in events_stats},
+                **({"kernel_trace_us": {k: [round(v[0], 2), round(v[1], 3)] for k, v in sorted(trace.items()) if v[1] >= 0.5}} if trace else {}),
+                # every GEMM family's own fraction of the peak (algorithmic FLOPs of its launches / their summed duration)
+                "families_frac": {f: round(fam_flops[f] * n_t / (stats[f][0] * 1e-3 * stats[f][1]) / 1e12 / peak, 4) for f in fam_flops if stats[f][1] / n_t >= 0.5}}     # (a family whose work rides elsewhere in most updates - the first layers inside a graph - has no launch of its own to rate)
+    return roof
+
+
 def main():
     global B
     ap = argparse.ArgumentParser()
@@ -513,7 +589,9 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--replay", type=int, default=REPLAY)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the CPU baseline, env-steps/sec, the drop-in's blocking forms and the side records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--one-update-per-launch", action="store_true",
                     help="N = 1: enqueue the K steps as K calls of dqnhip_update_async (one hipGraph launch each) instead of one dqnhip_update_async_n(K)")
@@ -521,7 +599,7 @@ def main():
     ap.add_argument("--minibatch", type=int, default=B, help="rows per GPU (BASELINE metric: 256)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
                     help="fp16: tower GEMMs on fp16 MFMA with fp32 accumulate (BASELINE config #5); not the headline metric")
-    ap.add_argument("--no-env", action="store_true", help="skip the env-steps/sec leg")
+    ap.add_argument("--no-env", action="store_true", help="--full: skip the env-steps/sec leg")
     ap.add_argument("--frames-per-trial", type=int, default=500)
     ap.add_argument("--force-dp", action="store_true", help="use the data-parallel path even with one rank (testing)")
     ap.add_argument("--strong", action="store_true",
@@ -542,11 +620,11 @@ def main():
     ap.add_argument("--dp-fp32-grads", action="store_true", help="native DP, fp16 learner: all-reduce fp32 gradients instead of bf16 (DQNHIP_DP_HALF_GRADS)")
     ap.add_argument("--dp-timeout", type=int, default=600, help="N > 1: seconds the headline measurement may take before every rank gives up")
     ap.add_argument("--tuning", type=int, default=0, help="dqnhip_config.tuning_flags (A/B switches, include/dqnhip.h DQNHIP_TUNE_*)")
-    ap.add_argument("--test-strong-record", action="store_true", help="testing: also run the N > 1 strong-scaling record with the ranks there are")
+    ap.add_argument("--test-strong-record", action="store_true", help="testing, --full: also run the N > 1 strong-scaling record with the ranks there are")
     ap.add_argument("--trace-child", action="store_true", help="internal (live_kernel_trace): leave right after the K timed steps, so that they are the last updates in the kernel trace")
-    ap.add_argument("--no-live-trace", action="store_true", help="roofline durations from eager HIP events around single launches instead of a live rocprofv3 --kernel-trace child pass (graph replay)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC summary instead of two live rocprofv3 --pmc child passes")
-    ap.add_argument("--no-subrecords", action="store_true", help="skip the per-config sub-records (configs #3, #5; strong scaling under N > 1)")
+    ap.add_argument("--no-live-trace", action="store_true", help="--full: roofline durations from eager HIP events around single launches instead of a live rocprofv3 --kernel-trace child pass (graph replay)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: roofline.traffic from the committed PMC summary instead of two live rocprofv3 --pmc child passes")
+    ap.add_argument("--no-subrecords", action="store_true", help="--full: skip the per-config sub-records (configs #3, #5; strong scaling under N > 1)")
     ap.add_argument("--mode", default="dp", choices=["dp", "replicas"],
                     help="N>1: dp = gradient all-reduce (weak scaling), replicas = independent learners")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -725,8 +803,11 @@ def main():
         print(json.dumps({"trace_child": True, "ms_per_step": elapsed / args.steps * 1e3}), flush=True)
         dqn.close()
         return                               # (a normal exit: the profiler writes its trace from its exit handlers)
+    # Beyond this point a plain run only reads back what the result line reports.  The other records (the K steps again as one
+    # update per graph launch, the N = 1 point of the job, the roofline, the drop-in's blocking forms, env steps, the CPU
+    # baseline, the side records) are measured under --full only.
     one_per_launch_ms = None
-    if batched_enqueue and not args.no_graph:
+    if args.full and batched_enqueue and not args.no_graph:
         # the same K updates as K calls of dqnhip_update_async (one update per hipGraph launch), for the record
         barrier()
         t1 = time.perf_counter()
@@ -747,7 +828,7 @@ def main():
     # stay in step), so that a SCALE record can be cross-checked against the BENCH record of the same round without trusting
     # that two boxes clock alike
     n1_same_job = None
-    if dist_on and world > 1 and not args.strong:
+    if args.full and dist_on and world > 1 and not args.strong:
         d1 = pkg.DQN(S, minibatch=B, hidden=HIDDEN, memory=100000, seed=1, device=local_rank, use_graph=not args.no_graph,
                      precision=args.precision, tuning=args.tuning)
         prefill(d1, 60000, seed=5 + rank)
@@ -757,73 +838,7 @@ def main():
         n1_same_job = {"updates_per_s": round(1 / dt1, 1), "ms_per_step": round(dt1 * 1e3, 5),
                        "what": "rank 0's plain single learner (dqnhip_update_async_n, 320 updates, 60 000-transition replay) while every other rank runs its own: the N = 1 point of the same job"}
 
-    # roofline of the dominant kernel family, timed live with HIP events on the learner's stream
-    roof = None
-    n_t = 20
-    # every rank runs the extra updates (under data parallelism they contain collectives); only rank 0
-    # brackets its launches with events
-    if rank == 0:
-        dqn.set_kernel_timing(True)
-    for _ in range(n_t):
-        step()
-    if rank == 0:
-        fp16 = args.precision == "fp16"
-        fam_flops = family_flops16(B, S, HIDDEN) if fp16 else family_flops(B, S, HIDDEN, shifted=not (args.tuning & 4) and B >= 64)
-        peak = MFMA_F16_PEAK_TF if fp16 else MFMA_F32_PEAK_TF
-        stats = {}
-        for fam in list(fam_flops) + ["adam"]:
-            ms, cnt = dqn.kernel_timing(fam)
-            stats[fam] = (ms, cnt)
-        dqn.kernel_timing("adam", reset=True)
-        dqn.set_kernel_timing(False)
-        events_stats = dict(stats)
-        dur_src = "HIP events (hipExtLaunchKernelGGL start / stop) around each launch of %d eager updates after the timed region" % n_t
-        trace = None
-        extra = ["--minibatch", str(B), "--precision", args.precision, "--tuning", str(args.tuning)]
-        if world == 1 and not args.no_live_trace and not args.no_graph:
-            trace, why = live_kernel_trace(extra)
-            if trace is None:
-                dur_src += " [live kernel trace unavailable: %s]" % why
-            else:
-                # fold the traced kernels into the timing families: (mean ms per launch, launches in n_t updates)
-                fam_acc = {}
-                for kname, (us, per_upd) in trace.items():
-                    fam = next((f for pre, f in TRACE_FAMILY if kname.startswith(pre)), None)
-                    if fam is None:
-                        continue
-                    a = fam_acc.setdefault(fam, [0.0, 0.0])
-                    a[0] += us * per_upd; a[1] += per_upd
-                if all(f in fam_acc for f in fam_flops):
-                    stats = {f: ((fam_acc[f][0] / fam_acc[f][1]) * 1e-3, fam_acc[f][1] * n_t) for f in fam_acc}
-                    dur_src = why
-                else:
-                    dur_src += " [live kernel trace lacks families: %s]" % sorted(set(fam_flops) - set(fam_acc))
-                    trace = None
-        dom = max(fam_flops, key=lambda f: stats[f][0] * stats[f][1])
-        ms, cnt = stats[dom]
-        per_update_launches = cnt / n_t
-        flops_per_launch = fam_flops[dom] / per_update_launches
-        ach = flops_per_launch / (ms * 1e-3) / 1e12
-        traffic, traffic_src = (None, None)
-        if world == 1 and not args.no_live_pmc:
-            traffic, traffic_src = live_pmc_traffic(KERNEL_NAMES[dom], extra)
-        if traffic is None:
-            why = traffic_src
-            traffic, traffic_src = pmc_traffic(KERNEL_NAMES[dom])
-            if traffic_src and why:
-                traffic_src += " [live PMC pass unavailable: %s]" % why
-        roof = {"bound": "mfma", "kernel": KERNEL_NAMES[dom], "achieved": round(ach, 2), "peak": peak,
-                "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic,
-                "traffic_source": traffic_src,
-                "avg_launch_us": round(ms * 1e3, 2), "launches_per_update": per_update_launches,
-                "flops_per_launch": flops_per_launch,
-                "duration_source": dur_src,
-                "families_us": {f: [round(stats[f][0] * 1e3, 2), round(stats[f][1] / n_t, 3)] for f in stats},
-                # the same families timed with eager HIP events in this process (a cross-check; differs by a few per cent run to run)
-                "families_us_eager_events": {f: [round(events_stats[f][0] * 1e3, 2), events_stats[f][1] / n_t] for f in events_stats},
-                **({"kernel_trace_us": {k: [round(v[0], 2), round(v[1], 3)] for k, v in sorted(trace.items()) if v[1] >= 0.5}} if trace else {}),
-                # every GEMM family's own fraction of the peak (algorithmic FLOPs of its launches / their summed duration)
-                "families_frac": {f: round(fam_flops[f] * n_t / (stats[f][0] * 1e-3 * stats[f][1]) / 1e12 / peak, 4) for f in fam_flops if stats[f][1] / n_t >= 0.5}}     # (a family whose work rides elsewhere in most updates - the first layers inside a graph - has no launch of its own to rate)
+    roof = roofline(dqn, step, args, rank, world) if args.full else None
     torch.cuda.synchronize()
 
     # What the reference's UNCHANGED driver gets through the drop-in (src/dqn_main.cpp:361 -> DQN::Update ->
@@ -831,7 +846,7 @@ def main():
     # and a blocking (loss, avg_q) read-back per update — against the async headline above.  Measured inside the
     # library (dqnhip_benchmark_blocking), so no Python is in the loop; and the one-deep pipelined read-back.
     dropin = None
-    if rank == 0 and not dist_on and not args.no_subrecords:
+    if args.full and rank == 0 and not dist_on and not args.no_subrecords:
         ms_b = dqn.BenchmarkBlocking(1000, 100, seed=1, pipelined=False)
         ms_p = dqn.BenchmarkBlocking(1000, 100, seed=1, pipelined=True)
         ms_c = dqn.BenchmarkBlocking(1000, 100, seed=1, pipelined=2)
@@ -851,7 +866,7 @@ def main():
     # env-steps/sec (the other half of BASELINE.json's metric): N synthetic workers -> batched
     # SelectActions + GetAction + HFOGameState reward + LabelTransitions/AddTransitions, all on device
     env_res = None
-    if rank == 0 and not args.no_env:
+    if args.full and rank == 0 and not args.no_env:
         env_res = {}
         for workers in (64, 256, 1024, 2048):     # BASELINE configs #3 (64 workers) and #5 (2048 workers; 256 = its share per GPU on 8)
             # episode buffers must fit the replay ring: cap the episode length for the widest runs
@@ -898,7 +913,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
             "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
             "dtype": "f32" if args.precision == "fp32" else "f16 operands, f32 accumulate (master weights / Adam / heads f32)",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             # (the driver keeps 120 characters of `workload`: the sizes it cut off last round are keys of their own)
             "config": {"workload": "BASELINE configs[1]: 1v0 HFO, 1 MI355X, 4x1024 actor-critic, minibatch %d, %s-transition device replay" % (B, ("%dM" % (args.replay // 1000000)) if args.replay % 1000000 == 0 else str(args.replay)),
                        "replay_transitions": args.replay, "state_size": S, "hidden": list(HIDDEN), "minibatch": B,
@@ -925,7 +940,7 @@ def main():
             "env_steps": env_res,
             "sub_records": None,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(B, S, HIDDEN)
         else:
             out["cpu_baseline"] = None
@@ -947,7 +962,7 @@ def main():
     # side records (configs[2], configs[4]; strong scaling under N > 1).  They must never cost the headline:
     # a watchdog on every rank prints the line without them if they do not finish (e.g. one rank stuck in a
     # collective the others never entered), and an exception only drops the side records.
-    if not args.no_subrecords and not args.strong and args.precision == "fp32" and B == 256:
+    if args.full and not args.no_subrecords and not args.strong and args.precision == "fp32" and B == 256:
         import threading
         dog = threading.Timer(300.0, emit_and_exit, kwargs={"note": "side records did not finish within 300 s"})
         dog.daemon = True

@@ -8,7 +8,7 @@ cp $L /tmp/lib_orig.so
 for rep in $(seq $reps); do
   for v in A B; do
     cp ab_libs/lib$v.so $L
-    out=$(python bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-env --no-subrecords --no-live-pmc "$@" 2>/dev/null | grep '^{' | tail -1)
+    out=$(python bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-env --no-subrecords --no-live-pmc "$@" 2>/dev/null | grep '^{' | tail -1)
     echo "[$v] $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); f=d["roofline"]["families_us"]; print(d["value"], d["ms_per_step"], {k: v[0] for k, v in f.items()})')"
   done
 done

@@ -5,7 +5,7 @@ cd /root/repo
 A=${1:-0}; B=${2:-2}; reps=${3:-3}; shift 3
 for rep in $(seq $reps); do
   for v in $A $B; do
-    out=$(python bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-env --no-subrecords --no-live-pmc --tuning $v "$@" 2>/dev/null | grep '^{' | tail -1)
+    out=$(python bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-env --no-subrecords --no-live-pmc --tuning $v "$@" 2>/dev/null | grep '^{' | tail -1)
     echo "[tuning $v] $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); f=d["roofline"]["families_us"]; print(d["value"], d["ms_per_step"], {k: v[0] for k, v in f.items()})')"
   done
 done

@@ -18,7 +18,7 @@ stats() {  # tag n_updates title -- command...
   python scripts/stats_to_md.py "$f" $nup "$title" "rocprofv3 --kernel-trace --stats --output-format csv -- $*" > $O/${tag}_kernel_stats.md
   if [ $(grep -c '^| `' $O/${tag}_kernel_stats.md) -lt 3 ]; then echo "EMPTY table for $tag"; rc=1; fi
 }
-C="--no-cpu-baseline --no-env --no-subrecords --no-live-pmc --no-live-trace"
+C="--full --no-cpu-baseline --no-env --no-subrecords --no-live-pmc --no-live-trace"
 if [ "$what" != pmc ]; then
 stats ${R}_fp32_b256 0 "rocprofv3 --kernel-trace --stats — round $N, fp32, B=256 (headline; hipGraph replay)" python bench.py --steps 500 --warmup 50 $C
 stats ${R}_fp16_b4096 0 "rocprofv3 --kernel-trace --stats — round $N, fp16 learner, minibatch 4096, 4x1024 (BASELINE configs[4] on one GPU)" python bench.py --precision fp16 --minibatch 4096 --steps 200 --warmup 20 --replay 200000 $C

@@ -141,7 +141,7 @@ def test_bench_strong_scaling_record_with_the_ranks_there_are(pkg, gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29647", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "20", "--warmup", "5", "--replay", "20000", "--no-cpu-baseline", "--no-env", "--force-dp",
-           "--test-strong-record", "--no-live-pmc"]
+           "--test-strong-record", "--no-live-pmc", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     import json
@@ -167,7 +167,7 @@ def test_bench_two_ranks_flow_on_one_gpu(pkg, gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29643", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "20", "--warmup", "5", "--replay", "20000", "--no-cpu-baseline",
-           "--backend", "gloo", "--share-device0"]
+           "--backend", "gloo", "--share-device0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     import json
@@ -178,6 +178,21 @@ def test_bench_two_ranks_flow_on_one_gpu(pkg, gpu):
     # the N = 1 point measured in the same job (two plain learners share GPU 0 here, so only its presence and sanity are checked)
     n1 = d["config"]["n1_same_job"]
     assert n1["updates_per_s"] > 100 and abs(n1["ms_per_step"] * n1["updates_per_s"] - 1e3) < 1.0
+
+
+def test_bench_two_ranks_plain_flow_on_one_gpu(pkg, gpu):
+    """The N = 2 flow of a plain run (no --full): after the timed steps every rank goes straight to the line, so the ranks
+    must still meet in the same collectives (the elapsed-time all-reduce, the final barrier) and none of the all-rank
+    legs of --full may run."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+           "--master-addr", "127.0.0.1", "--master-port", "29653", os.path.join(ROOT, "bench.py"),
+           "--gpus", "2", "--steps", "20", "--warmup", "5", "--replay", "20000", "--backend", "gloo", "--share-device0"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    import json
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["n_gpus"] == 2 and d["value"] > 10 and d["config"]["parallelism"].startswith("dp2") and d["full"] is False
+    assert d["roofline"] is None and d["sub_records"] is None and "n1_same_job" not in d["config"]
 
 
 def test_unverified_exchange_forms_are_fenced_for_real_groups(pkg, gpu):
