@@ -15,7 +15,7 @@ def tower_weights(in_dim, hidden):
 def family_flops(B, S, hidden, shifted=True):
     """Algorithmic GEMM FLOPs per update, per kernel (tower layers only; the skinny heads are
     separate kernels).  See DESIGN.md §5.  Keys are the learner's timing families.
-    shifted: the backward schedule of learner.hip tower_backward (default for >= 2 tower layers at minibatches whose layers
+    shifted: the backward schedule of tower_backward in learner.hip (bwd_is_shifted, learner_plan.hip, decides; default for >= 2 tower layers at minibatches whose layers
     take the one-workgroup-type form): dgrad(L-1) | wgrad(i+1) + dgrad(i) ... | wgrad(1) + wgrad(0); else wgrad(i) + dgrad(i)
     per layer and the first layer's wgrad alone (DQNHIP_TUNE_BWD_UNSHIFTED, or the side-by-side pair launches of small shapes)."""
     wa = tower_weights(S, hidden)

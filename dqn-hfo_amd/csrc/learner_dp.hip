@@ -126,27 +126,10 @@ int dp_sequence(H* h, const int* idx_dev) {
   return run_phase(h, 2, nullptr);
 }
 
-// multi: kMultiU updates in one graph, each gather riding in the previous update's last launch (capture_graph)
+// multi: kMultiU updates in one graph, each gather riding in the previous update's last launch
 int dp_capture(H* h, bool multi = false) {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t* out = multi ? &h->dp_graph_n : &h->dp_graph;
-  HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  const int it_a = h->h_actor_iter, it_c = h->h_critic_iter;
-  int rc = 0;
-  for (int u = 0; u < (multi ? kMultiU : 1) && !rc; ++u) {
-    h->cap_u = multi ? u : -1;
-    rc = dp_sequence(h, nullptr);
-  }
-  h->cap_u = -1;
-  select_panels(h, 0);
-  h->h_actor_iter = it_a; h->h_critic_iter = it_c;   // capture does not execute
-  hipError_t e = hipStreamEndCapture(h->stream, &graph);
-  if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess) return fail("hipStreamEndCapture (dp): %s", hipGetErrorString(e));
-  e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-  hipGraphDestroy(graph);
-  if (e != hipSuccess) { *out = nullptr; return fail("hipGraphInstantiate (dp): %s", hipGetErrorString(e)); }
-  return 0;
+  CaptureSpec s; s.body = dp_sequence; s.multi = multi; s.updates = multi ? kMultiU : 1;
+  return capture_exec(h, s, multi ? &h->dp_graph_n : &h->dp_graph);
 }
 
 // ---- file rendezvous (one node, no launcher support) ----------------------------------------------

@@ -1,10 +1,19 @@
 // learner_internal.hip.h — what the translation units of libdqnhip.so share: the learner object behind dqnhip_handle, the
 // parameter-arena layout, the error convention, and the prototypes of the host-side building blocks.
-//   learner.hip      the update (forward / backward building blocks, the three phases, graph capture, the update entry points)
-//   learner_dp.hip   native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
-//   learner_io.hip   acting, replay memory (+ .replaymemory files), parameters, multi-agent sharing, introspection
-//   learner_env.hip  host side of the batched env front-end (include/dqnhip_env.h)
-//   snapshot.cpp     Caffe snapshot layout (no device code)
+//   learner.hip         what an update launches: the forward / backward / optimiser building blocks and the three phases of the
+//                       fp32 and fp16 schedules (run_phase), dqnhip_apply_update*.  Every kernel of the update is launched — and
+//                       has its launch attributes set (prepare_kernels) — from this unit
+//   learner_plan.hip    the error channel, parameter layout, config validation, shape predicates, the plan (plan_of); host only
+//   learner_create.hip  learner lifetime: dqnhip_create / dqnhip_destroy, staging buffers, drop_graphs; host only
+//   learner_update.hip  index staging, graph capture (capture_updates), dqnhip_update* / dqnhip_get_update_plan / dqnhip_read_stats,
+//                       the in-library benchmark loops; host only
+//   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
+//   learner_io.hip      acting, replay memory (+ .replaymemory files), parameters, multi-agent sharing, introspection
+//   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
+//   snapshot.cpp        Caffe snapshot layout (no device code)
+// A unit that launches a kernel embeds its own copy of the device code the headers' inline launchers name (~0.4 MB), and a launch
+// attribute (hipFuncSetAttribute) of a kernel with internal linkage holds for the calling unit's copy only: host-only units cost
+// nothing, and an attribute is set in the unit that launches the kernel.
 // Not installed, not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +45,7 @@
 namespace dqnhip_host {
 using namespace dqnhip;
 
-extern thread_local std::string g_err;      // defined in learner.hip; dqnhip_last_error() returns it
+extern thread_local std::string g_err;      // defined in learner_plan.hip; dqnhip_last_error() returns it
 
 inline int fail(const char* fmt, ...) {
   char buf[1024];
@@ -82,6 +91,19 @@ struct NetLayout {
 void layout_init(NetLayout& l, int in_dim, const dqnhip_config& c, bool actor);
 
 struct TimingRec { int family; hipEvent_t a, b; };
+
+// the captured launch sequences a single learner replays (dqnhip_learner::graph_exec)
+enum GraphSlot {
+  kGraphSampled,      // one update, indices sampled on the device
+  kGraphExplicit,     // one update, explicit indices (the pinned buffer)
+  kGraphPipe0,        // dqnhip_update_pipelined: explicit indices in pipeline slot 0 ...
+  kGraphPipe1,        // ... and slot 1
+  kGraphMulti,        // kMultiU device-sampled updates (dqnhip_update_async_n)
+  kGraphChainHead,    // dqnhip_update_chained: head of a chain (own gather, parity 0) ...
+  kGraphChainPar1,    // ... continued at panel parity 1 ...
+  kGraphChainPar0,    // ... and at parity 0
+  kNumGraphSlots
+};
 
 }  // namespace dqnhip_host
 
@@ -182,13 +204,8 @@ struct dqnhip_learner {
   // graph
   int cap_u = -1;              // while capturing a multi-update graph: the position of the update being captured (else -1)
   int cap_n = 16;              // ... and the number of updates of that graph (the last one carries no riders for a successor)
-  // dqnhip_update_async_n: graphs of 8 / 4 / 2 updates for what is left after the sixteen-update graphs (round 6: a remainder of r
-  // updates used to be r one-update graphs, each with its own gather, its own first-layer launch and the 8-us gap between two graph
-  // launches — the driver's 20 timed steps are 16 + 4)
-  hipGraphExec_t graph_small[3] = {nullptr, nullptr, nullptr};
-  // [0]: device-sampled, [1]: explicit idx (pinned buffer), [2], [3]: explicit idx in the pipelined slots, [4]: kMultiU device-sampled
-  // updates (dqnhip_update_async_n), [5] .. [7]: dqnhip_update_chained — head of a chain (own gather, parity 0), continued at parity 1 / 0
-  hipGraphExec_t graph_exec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipGraphExec_t graph_small[3] = {nullptr, nullptr, nullptr};   // dqnhip_update_async_n: 8 / 4 / 2 updates, for what is left after the sixteen-update graphs
+  hipGraphExec_t graph_exec[kNumGraphSlots] = {nullptr};         // by GraphSlot
   bool graph_failed = false;
   // dqnhip_update_chained (the drop-in's blocking update with the NEXT update's indices known one call ahead): the next update's gather
   // and first layers ride in this update's optimiser launches, as inside a multi-update graph.  What rode along is only used if the
@@ -254,9 +271,14 @@ void dense_to_arena(const NetLayout& l, const float* dense, std::vector<float>& 
 void arena_to_dense(const NetLayout& l, const std::vector<float>& arena, float* dense);
 inline const NetLayout& layout_of(const H* h, int net) { return (net & 1) ? h->lc : h->la; }
 int validate(const dqnhip_config* c);
+// shape predicates of the launch schedules (learner_plan.hip)
+bool bwd_layer_is_pair(const NetLayout& l, int i, int rows);
+bool bwd_is_shifted(const H* h, const NetLayout& l, int rows);
+bool head_big_ok(const H* h, int rows, int Hd);
+bool early_l0(const H* h);                               // plan_of(h).early_l0 while a multi-update graph is being captured
 inline size_t grad_arena_floats(const NetLayout& la, const NetLayout& lc) { return la.arena + 64 + lc.arena + 64; }
 
-// ---- building blocks defined in learner.hip, used by the other translation units ---------------------------------
+// ---- building blocks defined in learner.hip ----------------------------------------------------------------------
 // seed_w / seed_out: the TOP layer's launch also writes the dq = -1 pass's tower-top gradient (GemmProblem::seed_w)
 struct FwdPass { int net; const NetLayout* l; float** act; const float* seed_w = nullptr; float* seed_out = nullptr;
                  const float* dot_w = nullptr; float* dot_out = nullptr; };   // dot_w / dot_out: GemmProblem::dot_w, same layer
@@ -275,7 +297,7 @@ int head_forward(H* h, hipStream_t st, const HeadArgs& a, const HeadArgs* b = nu
   HIPCHK(hipGetLastError());
   return 0;
 }
-constexpr int kMultiU = 16;    // updates per replay of the multi-update graph (dqnhip_update_async_n; see capture_graph)
+constexpr int kMultiU = 16;    // updates per replay of the multi-update graph (dqnhip_update_async_n; see learner_update.hip)
 // Philox key of SampleTransitionsFromMemory: cfg.seed on rank 0 (what oracle/c_oracle.philox_indices
 // reproduces); data-parallel ranks get distinct streams from the SAME cfg.seed, so that the weight
 // initialisation (also keyed by cfg.seed) stays identical across the group
@@ -285,7 +307,7 @@ inline void shard_range(const H* h, int net, size_t& lo, size_t& hi, int rank = 
   const size_t r = (size_t)(rank < 0 ? h->cfg.dp_rank : rank);
   lo = r * slice; hi = lo + slice;
 }
-// Which merged forms the update of a learner takes (plan_of, learner.hip: the one place that decides; dqnhip_get_update_plan reports it)
+// Which merged forms the update of a learner takes (plan_of, learner_plan.hip: the one place that decides; dqnhip_get_update_plan reports it)
 struct UpdatePlan {
   bool fp16, dp;
   bool shifted_c, shifted_a;        // the shifted backward schedule (tower_backward) for the critic's Step(1) / the actor's backward
@@ -310,8 +332,22 @@ int to_bf16_launch(H* h, int net);                       // k_to_bf16: the bf16 
 int shard_scal_launch(H* h, float* tail);                // k_shard_scal: this rank's share of the clip norm -> tail[3]
 int run_phase(H* h, int phase, const int* idx_dev);
 int sync_dirty16(H* h);
+int prepare_kernels(const H* h);                         // the launch attributes (dynamic LDS above 64 KB) of the update's kernels
+// learner_update.hip
 int refresh_ring(H* h);
 int stage_indices(H* h, const int32_t* idx_host, const int** idx_dev);
+int run_update(H* h, const int* idx_dev);                // phases 0, 1, 2
+// One capture: `updates` runs of `body` on the learner's stream.  multi: as positions 0 .. updates - 1 of a multi-update graph of
+// `of` updates (each update's riders serve its successor; the last of `of` has none).  chain_pos >= 0 (dqnhip_update_chained): ONE
+// update captured as that position, its riders reading the next update's explicit indices.
+struct CaptureSpec {
+  int updates = 1; bool multi = false; int of = kMultiU; int chain_pos = -1;
+  const int* idx_dev = nullptr;                          // explicit indices (nullptr: sampled on the device)
+  int (*body)(H*, const int*) = run_update;              // (data parallel: dp_sequence, the phases with the exchange between them)
+};
+int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph);
+int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out);      // ... and instantiate
+// learner_create.hip
 int ensure_stage(H* h, size_t bytes);
 int ensure_act(H* h, int rows);
 void drop_graphs(H* h);                                  // every captured launch sequence of this learner

@@ -1,0 +1,460 @@
+// learner_update.hip — the update entry points of include/dqnhip.h: index staging, graph capture (capture_updates: the one
+// place that sets up and tears down a capture), replay-or-run, dqnhip_update* / dqnhip_get_update_plan / dqnhip_read_stats and the
+// in-library benchmark loops.  What an update launches is run_phase's business (learner.hip); this translation unit launches no
+// kernel and embeds no device code.
+#include "learner_internal.hip.h"
+
+namespace dqnhip_host {
+
+// re-read (head,size) after the env front-end appended episodes on the device
+int refresh_ring(H* h) {
+  if (!RO(h)->ring_stale) return 0;
+  int hs[2];
+  HIPCHK(hipMemcpyAsync(hs, RO(h)->st, sizeof hs, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  RO(h)->h_head = hs[0]; RO(h)->h_size = hs[1]; RO(h)->ring_stale = false;
+  return 0;
+}
+
+// every index inside the replay memory's current size (`what`: "sampled" / "next sampled")
+int check_indices(H* h, const int32_t* idx, const char* what) {
+  const long long size = RO(h)->h_size;
+  for (int i = 0; i < h->B; ++i)
+    if (idx[i] < 0 || idx[i] >= size) return fail("%s index %d = %d out of range [0,%lld)", what, i, idx[i], size);
+  return 0;
+}
+
+int stage_indices(H* h, const int32_t* idx_host, const int** idx_dev) {
+  *idx_dev = nullptr;
+  if (idx_host || RO(h)->h_size < 1) RC(refresh_ring(h));
+  if (RO(h)->h_size < 1) return fail("replay memory is empty");
+  if (idx_host) {
+    RC(check_indices(h, idx_host, "sampled"));
+    // the pinned staging buffer may still be in flight from the previous update
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(h->idx_pinned, idx_host, h->B * sizeof(int));
+    *idx_dev = h->idx_pinned_dev;           // the gather reads them from the pinned host buffer itself
+  }
+  return 0;
+}
+
+int run_update(H* h, const int* idx_dev) {
+  for (int p = 0; p < 3; ++p) RC(run_phase(h, p, idx_dev));
+  return 0;
+}
+
+// ---- graph capture ------------------------------------------------------------------------------------------------------------
+// Captures s.updates runs of s.body on the learner's stream into *graph.  Nothing executes: replays re-read every changing scalar
+// from DevState, so the host's iteration mirrors are put back, and every capture ends with panel parity 0 selected and the
+// capture position cleared, whichever way it ends.  A failed body's error text survives the clean-up.
+int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph) {
+  *graph = nullptr;
+  HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  const int it_a = h->h_actor_iter, it_c = h->h_critic_iter;
+  int rc = 0;
+  h->cap_n = s.of;
+  h->chain_cap = s.chain_pos >= 0;
+  for (int u = 0; u < s.updates && !rc; ++u) {
+    h->cap_u = s.multi ? u : s.chain_pos;
+    rc = s.body(h, s.idx_dev);
+  }
+  h->cap_u = -1; h->chain_cap = false; h->cap_n = kMultiU;
+  select_panels(h, 0);
+  h->h_actor_iter = it_a; h->h_critic_iter = it_c;
+  const std::string msg = g_err;
+  const hipError_t e = hipStreamEndCapture(h->stream, graph);
+  if (rc) { if (*graph) hipGraphDestroy(*graph); *graph = nullptr; g_err = msg; return rc; }
+  if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
+  return 0;
+}
+// ... instantiated into *out (nullptr on failure)
+int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out) {
+  hipGraph_t graph = nullptr;
+  RC(capture_updates(h, s, &graph));
+  const hipError_t e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+  hipGraphDestroy(graph);
+  if (e != hipSuccess) { *out = nullptr; return fail("hipGraphInstantiate: %s", hipGetErrorString(e)); }
+  return 0;
+}
+
+// n updates per replay.  Two consecutive hipGraphLaunch calls leave the GPU idle for ~8.4 us between the last kernel of one and the
+// first kernel of the next (kernel trace, profiles/r04_graph_gap.txt; two instances of the graph launched alternately: the same) -
+// 2.8 % of a 300-us update; inside a graph the same boundary is a plain kernel boundary, and the gather of update u + 1 rides in
+// update u's last launch (adam_launch, DevState::gbase).
+static CaptureSpec multi_spec(int n) { CaptureSpec s; s.updates = n; s.multi = true; s.of = n; return s; }
+
+// what each slot of graph_exec captures.  idx_dev: the pipelined slots' index buffer (already on the device)
+static CaptureSpec slot_spec(const H* h, GraphSlot slot, const int* idx_dev) {
+  CaptureSpec s;
+  switch (slot) {
+    case kGraphExplicit: s.idx_dev = h->idx_pinned_dev; break;
+    case kGraphPipe0: case kGraphPipe1: s.idx_dev = idx_dev; break;
+    case kGraphMulti: s = multi_spec(kMultiU); break;
+    // dqnhip_update_chained: ONE update captured as position 0 (head: own gather), 1 or 2 (continued at parity 1 / 0) of a
+    // multi-update graph, its riders reading the next update's explicit indices
+    case kGraphChainHead: s.chain_pos = 0; s.idx_dev = h->idx_pinned_dev; break;
+    case kGraphChainPar1: s.chain_pos = 1; break;
+    case kGraphChainPar0: s.chain_pos = 2; break;
+    default: break;     // kGraphSampled: one update, indices sampled on the device
+  }
+  return s;
+}
+
+// *g, captured from `s` on first use; nullptr where graphs are off, kernel timing is on, or a capture has failed (which turns
+// graphs off for this learner)
+static hipGraphExec_t graph_of(H* h, hipGraphExec_t* g, const CaptureSpec& s) {
+  if (!h->cfg.use_graph || h->timing || h->graph_failed) return nullptr;
+  if (!*g && capture_exec(h, s, g)) h->graph_failed = true;
+  return *g;
+}
+static hipGraphExec_t graph_of(H* h, GraphSlot slot, const int* idx_dev = nullptr) {
+  return graph_of(h, &h->graph_exec[slot], slot_spec(h, slot, idx_dev));
+}
+static int replay(H* h, hipGraphExec_t g, int updates) {
+  HIPCHK(hipGraphLaunch(g, h->stream));
+  h->h_actor_iter += updates; h->h_critic_iter += updates;
+  return 0;
+}
+// one update: the slot's graph, or the three phases eagerly
+static int replay_or_run(H* h, GraphSlot slot, const int* idx_dev) {
+  if (hipGraphExec_t g = graph_of(h, slot, idx_dev)) return replay(h, g, 1);
+  return run_update(h, idx_dev);
+}
+
+// kernel nodes of a captured sequence
+static int count_kernel_nodes(hipGraph_t g, int* out) {
+  size_t cnt = 0;
+  HIPCHK(hipGraphGetNodes(g, nullptr, &cnt));
+  std::vector<hipGraphNode_t> nodes(cnt);
+  if (cnt) HIPCHK(hipGraphGetNodes(g, nodes.data(), &cnt));
+  int k = 0;
+  for (hipGraphNode_t nd : nodes) {
+    hipGraphNodeType t;
+    HIPCHK(hipGraphNodeGetType(nd, &t));
+    if (t == hipGraphNodeTypeKernel) ++k;
+  }
+  *out = k;
+  return 0;
+}
+// the kernels `updates` consecutive updates launch — as a multi-update graph captures them (multi) or stand-alone.  A capture that
+// is thrown away: nothing executes, nothing is instantiated.
+static int count_launches(H* h, bool multi, int updates, int* out) {
+  CaptureSpec s; s.updates = updates; s.multi = multi;
+  hipGraph_t graph = nullptr;
+  RC(capture_updates(h, s, &graph));
+  const int rc = count_kernel_nodes(graph, out);
+  hipGraphDestroy(graph);
+  return rc;
+}
+
+}  // namespace dqnhip_host
+
+extern "C" {
+
+int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
+  if (!h || !out) return fail("null argument");
+  if (out->struct_size != (int32_t)sizeof(dqnhip_update_plan)) return fail("dqnhip_update_plan.struct_size %d != %zu (ABI mismatch)", out->struct_size, sizeof(dqnhip_update_plan));
+  if (h->next_phase != 0) return fail("dqnhip_get_update_plan: a phased update is in progress (next phase %d)", h->next_phase);
+  if (h->timing) return fail("dqnhip_get_update_plan: kernel timing is on (timed launches are not captured)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const UpdatePlan p = plan_of(h);
+  memset(out, 0, sizeof *out);
+  out->struct_size = (int32_t)sizeof *out;
+  out->forms = (p.fp16 ? DQNHIP_PLAN_FP16 : 0) | (p.dp ? DQNHIP_PLAN_DATA_PARALLEL : 0) | (p.shifted_c ? DQNHIP_PLAN_BWD_SHIFTED_CRITIC : 0) |
+               (p.shifted_a ? DQNHIP_PLAN_BWD_SHIFTED_ACTOR : 0) | (p.head_rides_c ? DQNHIP_PLAN_HEAD_WGRAD_RIDES_CRITIC : 0) |
+               (p.head_rides_a ? DQNHIP_PLAN_HEAD_WGRAD_RIDES_ACTOR : 0) | (p.fuse_q ? DQNHIP_PLAN_Q_TRAIN_IN_DGRAD : 0) |
+               (p.fused_seed ? DQNHIP_PLAN_HEAD_SEED_FUSED : 0) | (p.fuse_head ? DQNHIP_PLAN_DQDA_HEAD_BWD : 0) |
+               (p.critic_l0 ? DQNHIP_PLAN_CRITIC_L0_RIDES : 0) | (p.first_layers_merged ? DQNHIP_PLAN_FIRST_LAYERS_MERGED : 0) |
+               (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0);
+  out->updates_per_graph = kMultiU;
+  // per net and update: one all-reduce (per-layer buckets: one per tower layer + the head slice; bf16 exchange: the tails travel in a
+  // second call beside the actor's; sharded optimiser: reduce-scatter + the 4-float all-reduce + 2 (fp16 learner: 4) all-gathers)
+  if (h->comm) out->collectives = h->dp_shard ? 2 * (2 + (h->fp16 ? 4 : 2)) : h->dp_per_layer ? 2 * (h->L + 1) : h->dp_half ? 3 : 2;
+  if (h->dp_shard) return 0;
+  int n1 = 0, nf = 0, n2 = 0;
+  RC(count_launches(h, false, 1, &n1));
+  RC(count_launches(h, true, 1, &nf));
+  RC(count_launches(h, true, 2, &n2));
+  out->launches_single = n1; out->launches_graph_first = nf; out->launches_in_graph = n2 - nf;
+  return 0;
+}
+
+int dqnhip_update_async(dqnhip_handle h, const int32_t* idx_host) {
+  if (!h) return fail("null handle");
+  h->epoch += 1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->cfg.dp_world > 1) return fail("dqnhip_update_async: dp_world > 1 requires dqnhip_update_phase + all-reduce (or dqnhip_dp_update)");
+  if (h->dp_half) return fail("dqnhip_update_async: this learner exchanges bf16 gradients (DQNHIP_DP_HALF_GRADS): use dqnhip_dp_update");
+  if (h->dp_shard) return fail("dqnhip_update_async: this learner's optimiser is sharded over its group (DQNHIP_DP_SHARD_OPT): use dqnhip_dp_update");
+  if (h->next_phase != 0) return fail("dqnhip_update_async: a phased update is in progress (next phase %d)", h->next_phase);
+  RingUse ring_use(h);
+  RC(sync_dirty16(h));
+  const int* idx_dev = nullptr;
+  RC(stage_indices(h, idx_host, &idx_dev));
+  return replay_or_run(h, idx_host ? kGraphExplicit : kGraphSampled, idx_dev);
+}
+
+int dqnhip_update_async_n(dqnhip_handle h, int32_t n) {
+  if (!h) return fail("null handle");
+  h->epoch += 1;
+  if (n < 0) return fail("dqnhip_update_async_n: n must be >= 0");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_async_n: data-parallel learners use dqnhip_dp_update");
+  if (h->next_phase != 0) return fail("dqnhip_update_async_n: a phased update is in progress (next phase %d)", h->next_phase);
+  RingUse ring_use(h);
+  RC(sync_dirty16(h));
+  if (RO(h)->h_size < 1) RC(refresh_ring(h));
+  if (RO(h)->h_size < 1) return fail("replay memory is empty");
+  hipGraphExec_t g;
+  while (n >= kMultiU && (g = graph_of(h, kGraphMulti)) != nullptr) { RC(replay(h, g, kMultiU)); n -= kMultiU; }
+  // the remainder as graphs of 8 / 4 / 2 updates (the same launch sequence as the sixteen-update graph, cut shorter), then one by
+  // one: a remainder of r one-update graphs would pay r gathers, r first-layer launches and the gap between two graph launches
+  // (the driver's 20 timed steps are 16 + 4)
+  for (int k = 0; k < 3; ++k) {
+    const int sz = 8 >> k;
+    if (n >= sz && (g = graph_of(h, &h->graph_small[k], multi_spec(sz))) != nullptr) { RC(replay(h, g, sz)); n -= sz; }
+  }
+  for (; n > 0; --n) RC(replay_or_run(h, kGraphSampled, nullptr));
+  return 0;
+}
+
+int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host) {
+  if (!h) return fail("null handle");
+  h->epoch += 1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // (with DQNHIP_DP_HALF_GRADS the exchange — bf16 image, all-reduce, widening by the clip-norm pass — lives inside
+  // dqnhip_dp_update: a caller-driven exchange between phases would leave phase 1 / 2 reading a stale bf16 image)
+  if (h->dp_half) return fail("dqnhip_update_phase: this learner exchanges bf16 gradients (DQNHIP_DP_HALF_GRADS): use dqnhip_dp_update");
+  if (h->dp_shard) return fail("dqnhip_update_phase: this learner's optimiser is sharded over its group (DQNHIP_DP_SHARD_OPT): use dqnhip_dp_update");
+  // 0 -> 1 -> 2 or 10 -> 11 -> 1 -> 2: a phase run out of order would apply stale gradients
+  // and advance the iteration counters
+  const int expect = h->next_phase;
+  const bool ok = (phase == 0 || phase == 10) ? (expect == 0) : (phase == expect);
+  if (!ok) return fail("dqnhip_update_phase: phase %d out of order (expected %s)", phase,
+                       expect == 0 ? "0 or 10" : expect == 1 ? "1" : expect == 2 ? "2" : "11");
+  const int* idx_dev = nullptr;
+  int rc;
+  if (phase != 0 && phase != 10) rc = run_phase(h, phase, idx_dev);
+  else {
+    RingUse ring_use(h);
+    rc = sync_dirty16(h);
+    if (!rc) rc = stage_indices(h, idx_host, &idx_dev);
+    if (!rc) rc = run_phase(h, phase, idx_dev);
+  }
+  // a failed phase abandons the update: the next one starts from phase 0 / 10 again (one transient error must not
+  // wedge the learner in "out of order" for good)
+  h->next_phase = rc ? 0 : (phase == 0 ? 1 : phase == 10 ? 11 : phase == 11 ? 1 : phase == 1 ? 2 : 0);
+  return rc;
+}
+
+int dqnhip_update_abort(dqnhip_handle h) {
+  if (!h) return fail("null handle");
+  h->next_phase = 0;
+  return 0;
+}
+
+int dqnhip_read_stats(dqnhip_handle h, float* critic_loss, float* avg_q) {
+  if (!h) return fail("null handle");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // {critic_loss, avg_q, flags}: the last block of every update writes them into this pinned, host-mapped buffer itself
+  // (tick_body): no device-to-host copy, the stream sync is the only wait
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (critic_loss) *critic_loss = h->pinned_stats[0];
+  if (avg_q) *avg_q = h->pinned_stats[1];
+  int flags = 0; memcpy(&flags, &h->pinned_stats[2], sizeof flags);
+  if (flags) { HIPCHK(hipMemsetAsync(&h->st->flags, 0, sizeof(int), h->stream)); h->pinned_stats[2] = 0.0f; }   // sticky until reported
+  // CHECK(std::isfinite(target)) (src/dqn.cpp:898) and CHECK(std::isfinite(critic_loss)) (:906) — the
+  // reference aborts; here: an error code from the first read after the offending update, whichever
+  // entry point (blocking, async, phased, hipGraph) ran it
+  if (flags & kFlagTarget) return fail("Target not finite!");
+  if (flags & kFlagGradNorm) return fail("Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale)");
+  if (!std::isfinite(h->pinned_stats[0])) return fail("Critic loss not finite!");
+  return 0;
+}
+
+int dqnhip_skipped_steps(dqnhip_handle h, int64_t* count) {
+  if (!h || !count) return fail("null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  int v = 0;
+  HIPCHK(hipMemcpyAsync(h->pinned_stats + 8, &h->st->skipped_steps, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memcpy(&v, h->pinned_stats + 8, sizeof v);
+  *count = v;
+  return 0;
+}
+
+int dqnhip_update(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, float* avg_q) {
+  RC(dqnhip_update_async(h, idx_host));
+  return dqnhip_read_stats(h, critic_loss, avg_q);
+}
+
+// dqnhip_update with the NEXT update's indices known one call ahead (see dqnhip.h).  The reference's driver runs its updates in
+// bursts (src/dqn_main.cpp:359-361: `for (i < n_updates) dqn->Update()`), one blocking call at a time; with idx_next the burst gets the
+// schedule of a multi-update graph — the next update's gather in this update's critic optimiser launch, its four first layers in the
+// actor's — one graph launch per update.  What rode along is used only if the next call's idx equals idx_next and nothing changed
+// weights, iteration counters or the replay memory in between; otherwise that call starts a fresh chain (own gather, own first
+// layers: what the riders left is overwritten).  Every update computes exactly what dqnhip_update computes on the same indices.
+int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_t* idx_next, float* critic_loss, float* avg_q) {
+  if (!h) return fail("null handle");
+  if (!idx_host) return fail("dqnhip_update_chained: explicit indices required (on-device sampling: dqnhip_update_async_n)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const UpdatePlan P = plan_of(h);
+  const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && h->sharers == 0 && h->w_owner == nullptr;
+  if (!can) { h->chain_valid = false; return dqnhip_update(h, idx_host, critic_loss, avg_q); }
+  if (h->next_phase != 0) return fail("dqnhip_update_chained: a phased update is in progress (next phase %d)", h->next_phase);
+  {
+    RingUse ring_use(h);
+    RC(refresh_ring(h));
+    if (RO(h)->h_size < 1) return fail("replay memory is empty");
+    RC(check_indices(h, idx_host, "sampled"));
+    if (idx_next) RC(check_indices(h, idx_next, "next sampled"));
+    if (!h->idx_next_pinned[0])
+      for (int i = 0; i < 2; ++i) {
+        HIPCHK(hipHostMalloc((void**)&h->idx_next_pinned[i], h->B * sizeof(int), hipHostMallocMapped));
+        memset(h->idx_next_pinned[i], 0, h->B * sizeof(int));
+        void* d = nullptr; HIPCHK(hipHostGetDevicePointer(&d, h->idx_next_pinned[i], 0)); h->idx_next_dev[i] = (const int*)d;
+      }
+    HIPCHK(hipStreamSynchronize(h->stream));       // the pinned index buffers may still be in flight from an earlier (asynchronous) update
+    const bool cont = h->chain_valid && h->chain_epoch == h->epoch && h->chain_ring_epoch == RO(h)->epoch &&
+                      memcmp(h->chain_idx.data(), idx_host, h->B * sizeof(int32_t)) == 0;
+    const int par = cont ? h->chain_par : 0;         // this update's panel parity
+    const GraphSlot slot = !cont ? kGraphChainHead : par ? kGraphChainPar1 : kGraphChainPar0;
+    if (!cont) memcpy(h->idx_pinned, idx_host, h->B * sizeof(int));
+    h->chain_valid = false;
+    if (idx_next) {
+      memcpy(h->idx_next_pinned[par ^ 1], idx_next, h->B * sizeof(int));
+      h->chain_idx.assign(idx_next, idx_next + h->B);
+    }
+    hipGraphExec_t g = graph_of(h, slot);
+    if (!g) return dqnhip_update(h, idx_host, critic_loss, avg_q);
+    RC(replay(h, g, 1));
+    h->epoch += 1;
+    if (idx_next) { h->chain_valid = true; h->chain_par = par ^ 1; h->chain_epoch = h->epoch; h->chain_ring_epoch = RO(h)->epoch; }
+  }
+  // (both null: enqueue only — the caller does its own work while the update runs, e.g. drawing the prediction after next, and
+  // collects the scalars with dqnhip_read_stats)
+  if (critic_loss == nullptr && avg_q == nullptr) return 0;
+  return dqnhip_read_stats(h, critic_loss, avg_q);
+}
+
+// One-deep pipelined form of dqnhip_update: enqueues update t and returns the scalars of update t-1 (zeros on the
+// first call).  The host then waits for update t-1 only, while update t is already queued behind it — the device
+// never idles on the host's index draw, the H2D of the indices or the read-back, which dqnhip_update pays on
+// every call.  Indices and scalars use two pinned slots each (nothing in flight is overwritten).
+int dqnhip_update_pipelined(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, float* avg_q) {
+  if (!h) return fail("null handle");
+  h->epoch += 1;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");
+  if (h->next_phase != 0) return fail("dqnhip_update_pipelined: a phased update is in progress (next phase %d)", h->next_phase);
+  if (!h->pipe_ev[0]) {
+    for (int i = 0; i < 2; ++i) {
+      HIPCHK(hipEventCreateWithFlags(&h->pipe_ev[i], hipEventDisableTiming));
+      HIPCHK(hipHostMalloc((void**)&h->pipe_idx_pinned[i], h->B * sizeof(int), hipHostMallocMapped));
+      { void* d = nullptr; HIPCHK(hipHostGetDevicePointer(&d, h->pipe_idx_pinned[i], 0)); h->pipe_idx_dev[i] = (int*)d; }
+      HIPCHK(hipHostMalloc((void**)&h->pipe_stats[i], 64, hipHostMallocDefault));
+      memset(h->pipe_stats[i], 0, 64);
+    }
+  }
+  const int slot = (int)(h->pipe_count & 1);
+  {
+    RingUse ring_use(h);
+    RC(sync_dirty16(h));
+    const int* idx_dev = nullptr;
+    if (idx_host) {
+      RC(refresh_ring(h));
+      RC(check_indices(h, idx_host, "sampled"));
+      // slot's previous user was update t-2, whose completion the previous call already waited for
+      memcpy(h->pipe_idx_pinned[slot], idx_host, h->B * sizeof(int));
+      idx_dev = h->pipe_idx_dev[slot];      // device alias of the pinned slot (no H2D copy)
+    } else if (RO(h)->h_size < 1) {
+      RC(refresh_ring(h));
+      if (RO(h)->h_size < 1) return fail("replay memory is empty");
+    }
+    RC(replay_or_run(h, !idx_host ? kGraphSampled : slot ? kGraphPipe1 : kGraphPipe0, idx_dev));
+  }
+  HIPCHK(hipMemcpyAsync(h->pipe_stats[slot], &h->st->critic_loss, 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipEventRecord(h->pipe_ev[slot], h->stream));
+  const int prev = slot ^ 1;
+  float loss = 0.f, q = 0.f; int flags = 0;
+  if (h->pipe_count > 0) {
+    HIPCHK(hipEventSynchronize(h->pipe_ev[prev]));
+    loss = h->pipe_stats[prev][0]; q = h->pipe_stats[prev][1];
+    memcpy(&flags, &h->pipe_stats[prev][2], sizeof flags);
+  }
+  h->pipe_count += 1;
+  if (critic_loss) *critic_loss = loss;
+  if (avg_q) *avg_q = q;
+  if (flags) {     // sticky on the device: report through the blocking path, which clears them
+    float l2, q2;
+    const int rc = dqnhip_read_stats(h, &l2, &q2);      // syncs the stream: update t (enqueued above) has completed too
+    // update t's read-back into the other slot was enqueued BEFORE the flags were cleared and still carries them: this
+    // report covers it, so the next call must not raise the same flag again
+    memset(&h->pipe_stats[slot][2], 0, sizeof(float));
+    return rc ? 1 : fail("update flags raised");
+  }
+  if (!std::isfinite(loss)) return fail("Critic loss not finite!");
+  return 0;
+}
+
+int dqnhip_benchmark(dqnhip_handle h, int32_t warmup, int32_t iterations, float* avg_ms) {
+  if (!h) return fail("null handle");
+  if (iterations < 1) return fail("iterations must be >= 1");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (warmup > 0) RC(dqnhip_update_async_n(h, warmup));
+  hipEvent_t a, b;
+  HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventRecord(a, h->stream));
+  RC(dqnhip_update_async_n(h, iterations));
+  HIPCHK(hipEventRecord(b, h->stream));
+  HIPCHK(hipEventSynchronize(b));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, a, b));
+  hipEventDestroy(a); hipEventDestroy(b);
+  if (avg_ms) *avg_ms = ms / iterations;
+  return 0;
+}
+
+
+// What the reference's driver gets from this library (src/dqn_main.cpp:361 -> DQN::Update -> UpdateActorCritic, and
+// DQN::Benchmark, src/dqn.cpp:487-498, which loops over it): host-drawn indices (std::mt19937 +
+// uniform_int_distribution, SampleTransitionsFromMemory :501-509), staged to the device, and a BLOCKING read of
+// (critic_loss, avg_q) after every update.  pipelined != 0: dqnhip_update_pipelined instead.
+int dqnhip_benchmark_blocking(dqnhip_handle h, int32_t warmup, int32_t iterations, uint64_t seed, int32_t pipelined, float* avg_ms) {
+  if (!h) return fail("null handle");
+  if (iterations < 1) return fail("iterations must be >= 1");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  int32_t size = 0;
+  RC(dqnhip_memory_size(h, &size));
+  if (size < 1) return fail("replay memory is empty");
+  std::mt19937 rng((uint32_t)seed);
+  std::vector<int32_t> idx(h->B);
+  float loss = 0, avgq = 0;
+  std::vector<int32_t> nxt(h->B);
+  bool have_next = false;
+  auto one = [&]() -> int {
+    if (pipelined == 2) {
+      // the drop-in's chained form (dqn_dropin.cpp UpdateActorCritic): the next update's indices are drawn one call ahead
+      // (drawing the prediction after next while the update runs — an enqueue-only call, then dqnhip_read_stats — was measured
+      // too: 3 334-3 350 against 3 335-3 347 updates/s, the draw of 256 indices is ~1 us; not kept)
+      if (have_next) idx.swap(nxt); else for (int32_t& i : idx) i = std::uniform_int_distribution<int>(0, size - 1)(rng);
+      for (int32_t& i : nxt) i = std::uniform_int_distribution<int>(0, size - 1)(rng);
+      have_next = true;
+      return dqnhip_update_chained(h, idx.data(), nxt.data(), &loss, &avgq);
+    }
+    for (int32_t& i : idx) i = std::uniform_int_distribution<int>(0, size - 1)(rng);
+    return pipelined ? dqnhip_update_pipelined(h, idx.data(), &loss, &avgq) : dqnhip_update(h, idx.data(), &loss, &avgq);
+  };
+  for (int i = 0; i < warmup; ++i) RC(one());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < iterations; ++i) RC(one());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (pipelined == 1) RC(dqnhip_read_stats(h, &loss, &avgq));      // drains the one outstanding read-back
+  if (avg_ms) *avg_ms = (float)(ms / iterations);
+  return 0;
+}
+
+}  // extern "C"

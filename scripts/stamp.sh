@@ -5,8 +5,8 @@
 cd "$(dirname "$0")/.."
 git rev-parse --short=8 HEAD > .git_head
 python - <<'PY'
-import json, subprocess
-srcs = ["learner.hip", "learner_dp.hip", "learner_io.hip", "learner_env.hip", "learner_internal.hip.h", "gemm_direct.hip.h", "hgemm.hip.h", "small_kernels.hip.h", "env.hip.h"]
+import glob, json, os, subprocess
+srcs = sorted(os.path.basename(f) for pat in ("*.hip", "*.h", "*.cpp") for f in glob.glob("dqn-hfo_amd/csrc/" + pat))
 kv = {s: subprocess.run(["git", "log", "-1", "--format=%h", "--", "dqn-hfo_amd/csrc/" + s], capture_output=True, text=True).stdout.strip() for s in srcs}
 json.dump(kv, open(".kernel_versions.json", "w"))
 print(open(".git_head").read().strip(), kv)

@@ -9,6 +9,7 @@
 
 #include "dqnhip_internal.h"
 #include "gemm_direct.hip.h"
+#include "gemm_experiments.hip.h"
 #include "gemm_mfma.hip.h"
 
 using namespace dqnhip;

@@ -1,5 +1,5 @@
 """dqnhip_get_update_plan: the merged forms a learner's update takes and the kernels it launches, counted from a capture of the
-very sequence dqnhip_update* enqueues.  The merged launches are gated by shape predicates (learner.hip, plan_of); one that
+very sequence dqnhip_update* enqueues.  The merged launches are gated by shape predicates (learner_plan.hip, plan_of); one that
 silently stops matching at a BASELINE shape would pass every parity test and only show up as a slower bench — here it is a
 failed assertion.  Reference work covered by these launches: DQN::UpdateActorCritic, src/dqn.cpp:828-972."""
 import numpy as np
