@@ -1,6 +1,7 @@
 /*
- * dqnhip_internal.h — test / tuning hooks exported by libdqnhip_test.so (csrc/gemm_bench.hip).  Not part of the
- * drop-in boundary (include/dqnhip.h); used by tests/ and scripts/gemm_tune.py only.
+ * dqnhip_internal.h — test / tuning hooks exported by libdqnhip_test.so (csrc/gemm_bench.hip: the timing harness and the
+ * probes; csrc/gemm_forms.hip: dqnhip_test_gemm_form, one launch of a product GEMM form on caller-made buffers).  Not part of
+ * the drop-in boundary (include/dqnhip.h); used by tests/ and scripts/gemm_tune.py only.
  */
 #ifndef DQNHIP_INTERNAL_H_
 #define DQNHIP_INTERNAL_H_
@@ -17,10 +18,47 @@ extern "C" {
  *   variant kernel family / tile (see gemm_bench.hip for the table)
  *   groups  number of independent problems carried by one launch (1..4)
  *   iters   timed back-to-back launches on one stream (after 3 warm-up launches)
- * Returns 0 on success; avg_us = mean time per launch, max_abs_err vs the reference,
+ * Returns 0 on success; avg_us = mean time per launch, max_abs_err vs the reference (+inf when a difference is not finite:
+ * outputs are prefilled with NaN, so an element the kernel never wrote — or wrote as NaN — cannot pass as "no error"),
  * max_ref = max |reference| (for scaling the error). */
 int dqnhip_test_gemm(int32_t mode, int32_t variant, int32_t rows, int32_t n_out, int32_t k_in,
                      int32_t groups, int32_t iters, float* avg_us, float* max_abs_err, float* max_ref);
+
+/* ---- dqnhip_test_gemm_form (csrc/gemm_forms.hip): the GEMM forms learner.hip launches, one launch, host-visible results ----
+ * The caller (tests/test_gpu_gemm_forms.py with tests/gemm_ref.py) makes every buffer, guard rows and pad columns included,
+ * and judges every element in float64; the entry only uploads, launches ONCE through the product's own *_launch helper
+ * (gemm_direct.hip.h) on one stream, synchronises and downloads.  No timing, no iterations, no device-side reference. */
+typedef struct dqnhip_test_buf {
+  float* host;       /* the whole buffer as uploaded (in/out buffers: and downloaded again, whole); null: operand absent */
+  int64_t count;     /* floats in it */
+  int64_t offset;    /* float index of the operand's element [0][0] inside it (guard rows in front, an offset panel column) */
+} dqnhip_test_buf;
+/* One GemmProblem (gemm_common.hip.h: C[q][p] = sum_k Pop(p,k) Qop(q,k), p contiguous).  mode 0 FWD / 1 DGRAD / 2 WGRAD. */
+typedef struct dqnhip_test_problem {
+  int32_t mode, Pdim, Qdim, Kred, ldp, ldq, ldc, ldm;
+  int32_t relu;                                         /* FWD: leaky ReLU in the epilogue */
+  int32_t xcopy_col, xcopy_n;                           /* FWD (direct forms): xcopy_dst[j][p] = P[p][xcopy_col + j], j < xcopy_n */
+  int32_t reserved;
+  dqnhip_test_buf P, Q, bias, mask, seed_w, dot_w;      /* inputs */
+  dqnhip_test_buf C, db, partial, C2, dot_out, xcopy_dst; /* in/out: arrive prefilled with the caller's sentinel */
+} dqnhip_test_problem;
+/* form: one id per launcher template instance learner.hip reaches for the fp32 tower (riders aside) */
+enum dqnhip_test_form {
+  DQNHIP_FORM_FWD_DIRECT_2x2 = 0, DQNHIP_FORM_FWD_DIRECT_4x2 = 1,
+  DQNHIP_FORM_FWD_LDS_1x1 = 2, DQNHIP_FORM_FWD_LDS_2x2 = 3, DQNHIP_FORM_FWD_LDS_4x2 = 4, DQNHIP_FORM_FWD_LDS_4x2_ONE_IMAGE = 5,
+  DQNHIP_FORM_DGRAD_DIRECT = 6, DQNHIP_FORM_DGRAD_LDS = 7, DQNHIP_FORM_DGRAD_NARROW = 8, DQNHIP_FORM_WGRAD_NARROW = 9,
+  DQNHIP_FORM_BWD_SEQ = 10, DQNHIP_FORM_BWD_SEQ_LDS = 11,            /* probs[0] dgrad, probs[1] wgrad */
+  DQNHIP_FORM_BWD_PAIR = 12, DQNHIP_FORM_BWD_PAIR_LDS = 13,          /* probs[0] dgrad, probs[1] wgrad */
+  DQNHIP_FORM_WGRAD_TAIL_1 = 14, DQNHIP_FORM_WGRAD_TAIL_NO = 15,     /* probs[0] wgrad on 64x64 tiles, probs[1] on 64x16 tiles; no riders */
+  DQNHIP_FORM_COUNT = 16
+};
+/* Returns 0 on success.
+ * Returns 1, before anything is uploaded or launched, when the form id, the problem count, a shape, a leading dimension or an
+ * alignment does not satisfy what the launcher and the kernel body assume, or when an operand does not lie wholly inside the
+ * buffer it was given in: after a return of 0 or 2 every address the kernel formed was inside the caller's buffers.
+ * Returns 2 on a HIP error.
+ * Not thread-safe (the one-time dynamic-LDS opt-in is a plain static flag): call it from one thread, as pytest does. */
+int dqnhip_test_gemm_form(int32_t form, int32_t n_problems, const dqnhip_test_problem* probs);
 
 /* fp16-input / fp32-accumulate GEMM family (csrc/hgemm.hip.h) on random data against a naive device
  * reference.  C[m][n] = sum_k A[m][k] B[n][k], A [M][K], B [N][K] fp16.
