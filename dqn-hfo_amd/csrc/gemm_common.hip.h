@@ -13,6 +13,7 @@
 // epilogues.  A launch may carry up to 4 independent problems (grouped GEMM).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 namespace dqnhip {
@@ -55,6 +56,23 @@ struct GemmBatch {
   int n;
   int total_tiles;
 };
+
+// Where ONE kernel launch goes: a stream and, in the learner's timing mode, the event pair that brackets it.  Every launcher takes a
+// LaunchOn where it would take a stream (a bare hipStream_t converts: untimed) and hands it to exactly one launch().
+struct LaunchOn {
+  hipStream_t stream;
+  hipEvent_t start = nullptr, stop = nullptr;
+  LaunchOn(hipStream_t s) : stream(s) {}
+  LaunchOn(hipStream_t s, hipEvent_t t0, hipEvent_t t1) : stream(s), start(t0), stop(t1) {}
+};
+// The one place a kernel is launched from.  With events: hipExtLaunchKernelGGL, which stamps them with the dispatch packet's own
+// start / stop timestamps — the kernel duration rocprofv3 reports, without the cost of separate event records.
+template <typename K, typename... A>
+inline hipError_t launch(const LaunchOn& on, K kernel, dim3 grid, dim3 block, size_t lds, const A&... args) {
+  if (on.start) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, on.stream, on.start, on.stop, 0, args...);
+  else hipLaunchKernelGGL(kernel, grid, block, lds, on.stream, args...);
+  return hipGetLastError();
+}
 
 __device__ __forceinline__ float lrelu_fwd(float x) {
   // Caffe ReLULayer::Forward: max(x,0) + slope*min(x,0)

@@ -27,7 +27,6 @@
 // gemm_mfma.hip.h (C[q][p] = sum_k P(p,k) Q(q,k), p contiguous).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <cstdlib>
 
@@ -1214,15 +1213,14 @@ __global__ __launch_bounds__(256) void gemm_wgrad_tail(const GemmBatch batch, co
 }
 
 // ---- launchers ------------------------------------------------------------------------
+// Each fills the tile accounting of its problems and makes ONE launch() on the LaunchOn it is handed (gemm_common.hip.h).
+// Dynamic-LDS sizes have a name next to their launcher; direct_prepare_all() raises the limit of those above 64 KB.
 
-// When set (by the learner's timing mode), the next launch is bracketed by these events through
-// hipExtLaunchKernelGGL: they carry the dispatch packet's own start/stop timestamps, i.e. the
-// same kernel duration rocprofv3 reports, without the cost of separate event records.
-struct LaunchTimer { hipEvent_t start = nullptr, stop = nullptr; };
-inline LaunchTimer& launch_timer() { static thread_local LaunchTimer t; return t; }
+constexpr int kBwdTileLds = 4 * 16 * 64 * 16 + 4 * 16 * 16;   // the 64 x 64 backward tile: 64 KB of operand panels + 1 KB of bias-gradient partials
+constexpr int kWgradTailLdsMax = 80 * 1024;                   // gemm_wgrad_tail with its head rider: still two workgroups per CU
 
-template <typename K>
-inline hipError_t direct_launch(K kernel, GemmBatch& batch, int BP, int BQ, int lds_bytes, hipStream_t stream) {
+// tiles of BP x BQ for every problem of the batch; returns (and stores) their number
+inline int tile_batch(GemmBatch& batch, int BP, int BQ) {
   int base = 0;
   for (int i = 0; i < batch.n; ++i) {
     GemmProblem& p = batch.prob[i];
@@ -1231,45 +1229,49 @@ inline hipError_t direct_launch(K kernel, GemmBatch& batch, int BP, int BQ, int 
     p.tile_base = base;
     base += p.tiles_p * p.tiles_q;
   }
-  batch.total_tiles = base;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL(kernel, dim3(base), dim3(256), lds_bytes, stream, lt.start, lt.stop, 0, batch); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL(kernel, dim3(base), dim3(256), lds_bytes, stream, batch);
-  return hipGetLastError();
+  return batch.total_tiles = base;
+}
+template <typename K>
+inline hipError_t direct_launch(K kernel, GemmBatch& batch, int BP, int BQ, int lds_bytes, const LaunchOn& on) {
+  return launch(on, kernel, dim3(tile_batch(batch, BP, BQ)), dim3(256), lds_bytes, batch);
 }
 
 template <int TP, int TQ>
-inline hipError_t fwd_direct_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_fwd_direct<TP, TQ>, b, 16 * TP, 16 * TQ, 4 * TP * TQ * 64 * 16, s);
+constexpr int fwd_direct_lds_bytes() { return 4 * TP * TQ * 64 * 16; }
+template <int TP, int TQ>
+inline hipError_t fwd_direct_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_fwd_direct<TP, TQ>, b, 16 * TP, 16 * TQ, fwd_direct_lds_bytes<TP, TQ>(), on);
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
 constexpr int fwd_lds_bytes() {
   return 4 * 4 * ((NSLOT * (TP + TQ) * 512 > TP * TQ * 256) ? NSLOT * (TP + TQ) * 512 : TP * TQ * 256);
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
-inline hipError_t fwd_lds_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), s);
+inline hipError_t fwd_lds_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), on);
 }
 template <int TPB, int TQ>
-inline hipError_t dgrad_direct_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_dgrad_direct<TPB, TQ>, b, 64 * TPB, 16 * TQ, 4 * TPB * 4 * TQ * 64 * 16, s);
+constexpr int dgrad_direct_lds_bytes() { return 4 * TPB * 4 * TQ * 64 * 16; }
+template <int TPB, int TQ>
+inline hipError_t dgrad_direct_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_dgrad_direct<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_direct_lds_bytes<TPB, TQ>(), on);
 }
 template <int TPB, int TQ>
 constexpr int dgrad_lds_bytes() { return 4 * ((2 * TQ * 512 > TPB * 4 * TQ * 256) ? 2 * TQ * 512 : TPB * 4 * TQ * 256) * 4; }
 template <int TPB, int TQ>
-inline hipError_t dgrad_lds_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), s);
+inline hipError_t dgrad_lds_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), on);
 }
 template <int TPB, int TQB>
-inline hipError_t wgrad_direct_launch(GemmBatch& b, hipStream_t s) {
+inline hipError_t wgrad_direct_launch(GemmBatch& b, const LaunchOn& on) {
   return direct_launch(gemm_wgrad_direct<TPB, TQB>, b, 64 * TPB, 64 * TQB,
-                       4 * TPB * 4 * TQB * 4 * 64 * 16 + 4 * TQB * 16 * 16, s);
+                       4 * TPB * 4 * TQB * 4 * 64 * 16 + 4 * TQB * 16 * 16, on);
 }
 // mixed dgrad(64x16)/wgrad(64x64) launch; every problem carries its own mode
 template <int TQD, bool DLDS = false>
-inline hipError_t bwd_pair_direct_launch(GemmBatch& batch, hipStream_t stream) {
+inline hipError_t bwd_pair_direct_launch(GemmBatch& batch, const LaunchOn& on) {
   int base = 0;
-  for (int i = 0; i < batch.n; ++i) {
+  for (int i = 0; i < batch.n; ++i) {          // (not tile_batch: the tile height goes by the problem's mode)
     GemmProblem& p = batch.prob[i];
     p.tiles_p = p.Pdim / 64;
     p.tiles_q = p.Qdim / (p.mode == GEMM_WGRAD ? 64 : 16 * TQD);
@@ -1277,67 +1279,45 @@ inline hipError_t bwd_pair_direct_launch(GemmBatch& batch, hipStream_t stream) {
     base += p.tiles_p * p.tiles_q;
   }
   batch.total_tiles = base;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL((gemm_bwd_pair_direct<TQD, DLDS>), dim3(base), dim3(256), 4 * 16 * 64 * 16 + 4 * 16 * 16, stream, lt.start, lt.stop, 0, batch); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL((gemm_bwd_pair_direct<TQD, DLDS>), dim3(base), dim3(256), 4 * 16 * 64 * 16 + 4 * 16 * 16, stream, batch);
-  return hipGetLastError();
+  return launch(on, gemm_bwd_pair_direct<TQD, DLDS>, dim3(base), dim3(256), kBwdTileLds, batch);
 }
-inline hipError_t dgrad_narrow_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_dgrad_narrow<0>, b, 16, 16, 4 * 64 * 16, s);
+constexpr int kNarrowDgradLds = 4 * 64 * 16;
+inline hipError_t dgrad_narrow_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_dgrad_narrow<0>, b, 16, 16, kNarrowDgradLds, on);
 }
-inline hipError_t dgrad_narrow_qrider_launch(GemmBatch& batch, const QHeadRider& rider, hipStream_t stream) {
-  int base = 0;
-  for (int i = 0; i < batch.n; ++i) {
-    GemmProblem& p = batch.prob[i];
-    p.tiles_p = p.Pdim / 16; p.tiles_q = p.Qdim / 16; p.tile_base = base;
-    base += p.tiles_p * p.tiles_q;
-  }
-  batch.total_tiles = base;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL(gemm_dgrad_narrow_qrider<0>, dim3(base + rider.blocks), dim3(256), 4 * 64 * 16, stream, lt.start, lt.stop, 0, batch, rider); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL(gemm_dgrad_narrow_qrider<0>, dim3(base + rider.blocks), dim3(256), 4 * 64 * 16, stream, batch, rider);
-  return hipGetLastError();
+inline hipError_t dgrad_narrow_qrider_launch(GemmBatch& batch, const QHeadRider& rider, const LaunchOn& on) {
+  return launch(on, gemm_dgrad_narrow_qrider<0>, dim3(tile_batch(batch, 16, 16) + rider.blocks), dim3(256), kNarrowDgradLds, batch, rider);
 }
 template <int TPB>
-inline hipError_t wgrad_narrow_launch(GemmBatch& b, hipStream_t s) {
-  return direct_launch(gemm_wgrad_narrow<TPB>, b, 64 * TPB, 16, 4 * TPB * 4 * 64 * 16 + 4 * 16 * 4, s);
+constexpr int wgrad_narrow_lds_bytes() { return 4 * TPB * 4 * 64 * 16 + 4 * 16 * 4; }
+template <int TPB>
+inline hipError_t wgrad_narrow_launch(GemmBatch& b, const LaunchOn& on) {
+  return direct_launch(gemm_wgrad_narrow<TPB>, b, 64 * TPB, 16, wgrad_narrow_lds_bytes<TPB>(), on);
 }
+// what the head's dW / db rider blocks need
 template <int NH>
-inline hipError_t wgrad_narrow_rider_launch(GemmBatch& batch, const HeadWgradRider& rider, hipStream_t stream) {
-  int base = 0;
-  for (int i = 0; i < batch.n; ++i) {
-    GemmProblem& p = batch.prob[i];
-    p.tiles_p = p.Pdim / 64; p.tiles_q = p.Qdim / 16; p.tile_base = base;
-    base += p.tiles_p * p.tiles_q;
-  }
-  batch.total_tiles = base;
-  const size_t need = (size_t)(rider.rows * NH + 16 * NH * 16) * sizeof(float);
-  const size_t lds = need > (size_t)(4 * 4 * 64 * 16 + 4 * 16 * 4) ? need : (size_t)(4 * 4 * 64 * 16 + 4 * 16 * 4);
+inline size_t head_rider_lds_bytes(const HeadWgradRider& rider) { return (size_t)(rider.rows * NH + 16 * NH * 16) * sizeof(float); }
+template <int NH>
+inline hipError_t wgrad_narrow_rider_launch(GemmBatch& batch, const HeadWgradRider& rider, const LaunchOn& on) {
+  const size_t lds = std::max(head_rider_lds_bytes<NH>(rider), (size_t)wgrad_narrow_lds_bytes<1>());
   if (lds > 64 * 1024) return hipErrorInvalidValue;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL((gemm_wgrad_narrow_rider<NH>), dim3(base + rider.blocks), dim3(256), lds, stream, lt.start, lt.stop, 0, batch, rider); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL((gemm_wgrad_narrow_rider<NH>), dim3(base + rider.blocks), dim3(256), lds, stream, batch, rider);
-  return hipGetLastError();
+  return launch(on, gemm_wgrad_narrow_rider<NH>, dim3(tile_batch(batch, 64, 16) + rider.blocks), dim3(256), lds, batch, rider);
 }
 // prob[0]: wgrad on 64 x 64 tiles, prob[1]: narrow wgrad on 64 x 16 tiles; rider.blocks may be 0
 template <int NH>
-inline hipError_t wgrad_tail_launch(GemmBatch& batch, const HeadWgradRider& rider, hipStream_t stream, const TailsArgs* tails_in = nullptr) {
+inline hipError_t wgrad_tail_launch(GemmBatch& batch, const HeadWgradRider& rider, const LaunchOn& on, const TailsArgs* tails_in = nullptr) {
   TailsArgs tails{}; if (tails_in != nullptr) { tails = *tails_in; tails.on = 1; }
   GemmProblem& w1 = batch.prob[0]; GemmProblem& w0 = batch.prob[1];
   w1.tiles_p = w1.Pdim / 64; w1.tiles_q = w1.Qdim / 64; w1.tile_base = 0;
   w0.tiles_p = w0.Pdim / 64; w0.tiles_q = w0.Qdim / 16; w0.tile_base = w1.tiles_p * w1.tiles_q;
   const int grid = w0.tile_base + w0.tiles_p * w0.tiles_q + rider.blocks + (tails.on ? 1 : 0);
   batch.total_tiles = grid;
-  const size_t need = rider.blocks ? (size_t)(rider.rows * NH + 16 * NH * 16) * sizeof(float) : 0;
-  const size_t lds = std::max(need, (size_t)(4 * 16 * 64 * 16 + 4 * 16 * 16));
-  if (lds > 80 * 1024) return hipErrorInvalidValue;          // two workgroups per CU
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL((gemm_wgrad_tail<NH>), dim3(grid), dim3(256), lds, stream, lt.start, lt.stop, 0, batch, rider, tails); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL((gemm_wgrad_tail<NH>), dim3(grid), dim3(256), lds, stream, batch, rider, tails);
-  return hipGetLastError();
+  const size_t lds = std::max(rider.blocks ? head_rider_lds_bytes<NH>(rider) : (size_t)0, (size_t)kBwdTileLds);
+  if (lds > (size_t)kWgradTailLdsMax) return hipErrorInvalidValue;
+  return launch(on, gemm_wgrad_tail<NH>, dim3(grid), dim3(256), lds, batch, rider, tails);
 }
 template <bool DLDS>
-inline hipError_t bwd_seq_launch(GemmBatch& batch, hipStream_t stream) {
+inline hipError_t bwd_seq_launch(GemmBatch& batch, const LaunchOn& on) {
   // prob[0] dgrad (64 x 16 tiles), prob[1] wgrad (64 x 64 tiles)
   GemmProblem& d = batch.prob[0]; GemmProblem& w = batch.prob[1];
   d.tiles_p = d.Pdim / 64; d.tiles_q = d.Qdim / 16; d.tile_base = 0;
@@ -1345,15 +1325,25 @@ inline hipError_t bwd_seq_launch(GemmBatch& batch, hipStream_t stream) {
   const int nd = d.tiles_p * d.tiles_q, nw = w.tiles_p * w.tiles_q;
   const int grid = nd > nw ? nd : nw;
   batch.total_tiles = grid;
-  constexpr int lds = 4 * 16 * 64 * 16 + 4 * 16 * 16;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL((gemm_bwd_seq<DLDS>), dim3(grid), dim3(256), lds, stream, lt.start, lt.stop, 0, batch); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL((gemm_bwd_seq<DLDS>), dim3(grid), dim3(256), lds, stream, batch);
-  return hipGetLastError();
+  return launch(on, gemm_bwd_seq<DLDS>, dim3(grid), dim3(256), kBwdTileLds, batch);
 }
 template <typename K>
 inline hipError_t direct_prepare(K kernel, int lds_bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+}
+// The fp32 kernels the learner launches with more than 64 KB of dynamic LDS.  Kernels have internal linkage: this sets the
+// attribute on the CALLING translation unit's copies, so the unit that launches them calls it (the fp16 family: hgemm_prepare_all).
+// (A template, so that only a unit that calls it instantiates — and embeds — the kernels it names.)
+template <int UNUSED = 0>
+inline hipError_t direct_prepare_all() {
+  hipError_t e = direct_prepare(gemm_bwd_seq<true>, kBwdTileLds);
+  if (e == hipSuccess) e = direct_prepare(gemm_bwd_seq<false>, kBwdTileLds);
+  if (e == hipSuccess) e = direct_prepare(gemm_wgrad_tail<1>, kWgradTailLdsMax);
+  if (e == hipSuccess) e = direct_prepare(gemm_wgrad_tail<10>, kWgradTailLdsMax);      // (the actor's ten heads)
+  if (e == hipSuccess) e = direct_prepare(gemm_bwd_pair_direct<1, true>, kBwdTileLds);
+  if (e == hipSuccess) e = direct_prepare(gemm_bwd_pair_direct<1, false>, kBwdTileLds);
+  if (e == hipSuccess) e = direct_prepare(gemm_fwd_lds<4, 2, true>, fwd_lds_bytes<4, 2, true>());
+  return e;
 }
 
 }  // namespace dqnhip

@@ -589,7 +589,7 @@ inline hipError_t hgemm_plan(const HGemm* gs, int n, int force, HGemmBatch& b, i
   return hipSuccess;
 }
 
-inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, hipStream_t st, int force = 0, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, const LaunchOn& on, int force = 0) {
   HGemmBatch b; int wm, wn; long blocks;
   hipError_t e = hgemm_plan(gs, n, force, b, wm, wn, blocks);
   if (e != hipSuccess) return e;
@@ -598,28 +598,18 @@ inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, hipStream_t st, int
   if (force == 4) {
 #ifdef HG_WITH_CT16
     if (m0 != 0 || m1 != 0) return hipErrorInvalidValue;
-    if (t0) hipExtLaunchKernelGGL(hgemm_nt_tall, dim3((unsigned)blocks), dim3(256), (HGCfg<2, 2, 2>::LDS_BYTES), st, t0, t1, 0, b);
-    else hipLaunchKernelGGL(hgemm_nt_tall, dim3((unsigned)blocks), dim3(256), (HGCfg<2, 2, 2>::LDS_BYTES), st, b);
-    return hipGetLastError();
+    return launch(on, hgemm_nt_tall, dim3((unsigned)blocks), dim3(256), HGCfg<2, 2, 2>::LDS_BYTES, b);
 #else
     return hipErrorInvalidValue;
 #endif
   }
-  bool launched = false;
-#define HG_TRY(WM, WN, M0, M1)                                                                                                          \
-  if (!launched && wm == WM && wn == WN && m0 == M0 && m1 == M1) {                                                                      \
-    launched = true;                                                                                                                    \
-    if (t0) hipExtLaunchKernelGGL((hgemm_nt<WM, WN, M0, M1>), dim3((unsigned)blocks), dim3(HGCfg<WM, WN>::NT), (HGCfg<WM, WN>::LDS_BYTES), st, t0, t1, 0, b); \
-    else hipLaunchKernelGGL((hgemm_nt<WM, WN, M0, M1>), dim3((unsigned)blocks), dim3(HGCfg<WM, WN>::NT), (HGCfg<WM, WN>::LDS_BYTES), st, b);         \
-  }
+#define HG_TRY(WM, WN, M0, M1) \
+  if (wm == WM && wn == WN && m0 == M0 && m1 == M1) return launch(on, hgemm_nt<WM, WN, M0, M1>, dim3((unsigned)blocks), dim3(HGCfg<WM, WN>::NT), HGCfg<WM, WN>::LDS_BYTES, b);
   HG_FOR_EACH_KERNEL(HG_TRY)
 #undef HG_TRY
-  if (!launched) return hipErrorInvalidValue;          // an orientation pair no kernel was built for
-  return hipGetLastError();
+  return hipErrorInvalidValue;          // an orientation pair no kernel was built for
 }
-inline hipError_t hgemm_launch(const HGemm& g, hipStream_t st, int force = 0, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-  return hgemm_launch_batch(&g, 1, st, force, t0, t1);
-}
+inline hipError_t hgemm_launch(const HGemm& g, const LaunchOn& on, int force = 0) { return hgemm_launch_batch(&g, 1, on, force); }
 // would a stand-alone launch of g use the 64x64 split-K tile?
 inline bool hgemm_uses_small_tile(const HGemm& g) { return !(hgemm_big_ok(g) && hgemm_tiles(g, true) >= 192); }
 
@@ -668,11 +658,10 @@ inline void cvt16_add(Cvt16Batch& b, const float* src, int ld_src, int rows, int
   d.tile_base = b.n ? b.d[b.n - 1].tile_base + b.d[b.n - 1].tiles_r * b.d[b.n - 1].tiles_c : 0;
   b.n += 1;
 }
-inline hipError_t cvt16_launch(const Cvt16Batch& b, hipStream_t st) {
+inline hipError_t cvt16_launch(const Cvt16Batch& b, const LaunchOn& on) {
   if (!b.n) return hipSuccess;
   const Cvt16& l = b.d[b.n - 1];
-  hipLaunchKernelGGL(k_cvt16<0>, dim3(l.tile_base + l.tiles_r * l.tiles_c), dim3(256), 0, st, b);
-  return hipGetLastError();
+  return launch(on, k_cvt16<0>, dim3(l.tile_base + l.tiles_r * l.tiles_c), dim3(256), 0, b);
 }
 
 #ifdef HG_WITH_CT16
@@ -907,8 +896,8 @@ inline hipError_t hgemm_group_db_prepare() {
 }
 // gs: n reduction-major wgrads (mode 3); db_blocks = 64-column blocks of db (0: none).  big: 128 x 128 tiles
 // (every M, N a multiple of 128), else 64 x 64 split-K tiles.
-inline hipError_t hgemm_group_db_launch(const HGemm* gs, int n, bool big, const Db16Batch& db, int db_blocks, hipStream_t st,
-                                        hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, const HeadWsum* head_in = nullptr, const TailsArgs* tails_in = nullptr) {
+inline hipError_t hgemm_group_db_launch(const HGemm* gs, int n, bool big, const Db16Batch& db, int db_blocks, const LaunchOn& on,
+                                        const HeadWsum* head_in = nullptr, const TailsArgs* tails_in = nullptr) {
   for (int i = 0; i < n; ++i) if (hgemm_mode(gs[i]) != 3) return hipErrorInvalidValue;
   HGemmBatch b; int wm, wn; long blocks;
   hipError_t e = hgemm_plan(gs, n, big ? 1 : 2, b, wm, wn, blocks);
@@ -917,15 +906,9 @@ inline hipError_t hgemm_group_db_launch(const HGemm* gs, int n, bool big, const 
   if (head_in != nullptr) head = *head_in;
   if (head.nh != 0 && ((head.nh != 1 && head.nh != 10) || head.blocks * 64 != head.H)) return hipErrorInvalidValue;
   if (tails_in != nullptr) { tails = *tails_in; tails.on = 1; }
-  const unsigned grid = (unsigned)(blocks + db_blocks + (head.nh ? head.blocks : 0) + (tails.on ? 1 : 0));
-  if (big) {
-    if (t0) hipExtLaunchKernelGGL((hgemm_group_db<2, 2>), dim3(grid), dim3(256), (HGCfg<2, 2>::LDS_BYTES), st, t0, t1, 0, b, db, db_blocks, head, tails);
-    else hipLaunchKernelGGL((hgemm_group_db<2, 2>), dim3(grid), dim3(256), (HGCfg<2, 2>::LDS_BYTES), st, b, db, db_blocks, head, tails);
-  } else {
-    if (t0) hipExtLaunchKernelGGL((hgemm_group_db<1, 1>), dim3(grid), dim3(256), (HGCfg<1, 1>::LDS_BYTES), st, t0, t1, 0, b, db, db_blocks, head, tails);
-    else hipLaunchKernelGGL((hgemm_group_db<1, 1>), dim3(grid), dim3(256), (HGCfg<1, 1>::LDS_BYTES), st, b, db, db_blocks, head, tails);
-  }
-  return hipGetLastError();
+  const dim3 grid((unsigned)(blocks + db_blocks + (head.nh ? head.blocks : 0) + (tails.on ? 1 : 0)));
+  if (big) return launch(on, hgemm_group_db<2, 2>, grid, dim3(256), HGCfg<2, 2>::LDS_BYTES, b, db, db_blocks, head, tails);
+  return launch(on, hgemm_group_db<1, 1>, grid, dim3(256), HGCfg<1, 1>::LDS_BYTES, b, db, db_blocks, head, tails);
 }
 
 }  // namespace dqnhip

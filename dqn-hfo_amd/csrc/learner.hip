@@ -14,8 +14,8 @@ using namespace dqnhip_host;
 
 namespace dqnhip_host {
 
-const char* const kFamily[] = {"gemm_fwd_lds_4x2", "gemm_dgrad", "gemm_wgrad", "adam", "gemm_bwd_pair", "gemm_fwd_lds_2x2", "gemm_fwd_direct",
-                               "hgemm_fwd", "hgemm_dgrad", "hgemm_wgrad"};
+const char* const kFamily[kNumFamily] = {"gemm_fwd_lds_4x2", "gemm_dgrad", "gemm_wgrad", "adam", "gemm_bwd_pair", "gemm_fwd_lds_2x2", "gemm_fwd_direct",
+                                         "hgemm_fwd", "hgemm_dgrad", "hgemm_wgrad"};      // by Family
 
 // ---- forward / backward building blocks ----------------------------------------
 
@@ -37,12 +37,12 @@ int layer_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, 
   // layer, narrow towers) the plain direct kernel.  One problem: 32x32 tiles (256 workgroups
   // for a 256x1024 layer); grouped: 64x32.
   const bool lds_ok = (l.kp[i] >= 512) && (l.kp[i] % 256 == 0);
-  ScopedTiming t(h, !lds_ok ? 6 : (n == 1 ? 5 : 0), st);
+  const LaunchOn on = timed(h, !lds_ok ? kFamFwdDirect : (n == 1 ? kFamFwdLds2x2 : kFamFwdLds4x2), st);
   // acting-time batches (<= 128 rows, e.g. 64 env workers): 16x16 tiles so that one layer still spreads
   // over 256 workgroups (64 rows x 1024 outputs = 256 tiles) instead of 64
-  if (n == 1 && rows <= 128 && lds_ok) HIPCHK((fwd_lds_launch<1, 1, true>(b, st)));
-  else if (n == 1 && rows >= 512 && lds_ok && l.dims[i + 1] % 64 == 0) HIPCHK((fwd_lds_launch<4, 2, true>(b, st)));   // enough rows to fill the chip with 64x32 tiles (fewer bytes per FLOP)
-  else if (n == 1) { if (lds_ok) HIPCHK((fwd_lds_launch<2, 2, true>(b, st))); else HIPCHK((fwd_direct_launch<2, 2>(b, st))); }
+  if (n == 1 && rows <= 128 && lds_ok) HIPCHK((fwd_lds_launch<1, 1, true>(b, on)));
+  else if (n == 1 && rows >= 512 && lds_ok && l.dims[i + 1] % 64 == 0) HIPCHK((fwd_lds_launch<4, 2, true>(b, on)));   // enough rows to fill the chip with 64x32 tiles (fewer bytes per FLOP)
+  else if (n == 1) { if (lds_ok) HIPCHK((fwd_lds_launch<2, 2, true>(b, on))); else HIPCHK((fwd_direct_launch<2, 2>(b, on))); }
   else {
     // grouped launches: 64x32 tiles when they still give the chip something to do; small minibatches / narrow layers
     // (the reference's defaults: 32 rows into 512 outputs = 16 such tiles for two problems, one long chain each) take
@@ -50,12 +50,12 @@ int layer_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, 
     const long P = l.dims[i + 1];
     const long t42 = (long)n * (P / 64) * (rows / 32), t22 = (long)n * (P / 32) * (rows / 32);
     if (lds_ok) {
-      if (t42 >= 192) HIPCHK((fwd_lds_launch<4, 2, true, 1>(b, st)));   // one LDS image per wave (48 KiB): both tiles of a CU resident at once — same-box A/B +0.6 %
-      else if (t22 >= 128 || rows > 128 || rows % 16) HIPCHK((fwd_lds_launch<2, 2, true>(b, st)));
-      else HIPCHK((fwd_lds_launch<1, 1, true>(b, st)));
+      if (t42 >= 192) HIPCHK((fwd_lds_launch<4, 2, true, 1>(b, on)));   // one LDS image per wave (48 KiB): both tiles of a CU resident at once — same-box A/B +0.6 %
+      else if (t22 >= 128 || rows > 128 || rows % 16) HIPCHK((fwd_lds_launch<2, 2, true>(b, on)));
+      else HIPCHK((fwd_lds_launch<1, 1, true>(b, on)));
     } else {
-      if (t42 >= 64) HIPCHK((fwd_direct_launch<4, 2>(b, st)));
-      else HIPCHK((fwd_direct_launch<2, 2>(b, st)));
+      if (t42 >= 64) HIPCHK((fwd_direct_launch<4, 2>(b, on)));
+      else HIPCHK((fwd_direct_launch<2, 2>(b, on)));
     }
   }
   return 0;
@@ -85,9 +85,7 @@ struct BwdRiders {
 };
 int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* garena, float* partial,
                    float** act, float** dZ, int rows, bool want_w, bool input_grad, const BwdRiders& r = BwdRiders{}) {
-  const int in_lo = r.in_lo, in_hi = r.in_hi;
-  const HeadWgradRider* rider = r.rider; const QHeadRider* qrider = r.qrider; DqdaHeadArgs* fuse = r.fuse;
-  const HeadTrainArgs* qtrain = r.qtrain; const float* qtrain_seed = r.qtrain_seed; const TailsArgs* tails = r.tails;
+  const QHeadRider* qrider = r.qrider;     // (cleared by the launch that carries it)
   auto dgrad_of = [&](int i) {             // dZ[i] = (dZ[i+1] . W_i) * lrelu'(act[i])
     GemmProblem p{};
     p.mode = GEMM_DGRAD;
@@ -118,31 +116,31 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
   // count, same workgroups, same arithmetic: the chain's last launch — 64-128 short workgroups, 6 us of launch floor —
   // is absorbed into a full wgrad launch (+~1 us), at the price of splitting one pair (8.3 + 7.9 instead of 14.5 us).
   const bool shifted = want_w && !input_grad && bwd_is_shifted(h, l, rows);
-  if (qtrain != nullptr && !(shifted && lds_ok_of(l.L - 1))) return fail("internal: k_dgrad_qtrain needs the shifted schedule and an LDS-staged top layer");
+  if (r.qtrain != nullptr && !(shifted && lds_ok_of(l.L - 1))) return fail("internal: k_dgrad_qtrain needs the shifted schedule and an LDS-staged top layer");
   if (shifted) {
     {
       GemmBatch bd{}; bd.n = 1; bd.prob[0] = dgrad_of(l.L - 1);
-      ScopedTiming t(h, 1, st);
-      if (qtrain != nullptr) { bd.prob[0].Q = qtrain_seed; HIPCHK(dgrad_qtrain_launch(bd, *qtrain, st)); }
-      else if (lds_ok_of(l.L - 1)) HIPCHK((dgrad_lds_launch<1, 1>(bd, st))); else HIPCHK((dgrad_direct_launch<1, 1>(bd, st)));
+      const LaunchOn on = timed(h, kFamDgrad, st);
+      if (r.qtrain != nullptr) { bd.prob[0].Q = r.qtrain_seed; HIPCHK(dgrad_qtrain_launch(bd, *r.qtrain, on)); }
+      else if (lds_ok_of(l.L - 1)) HIPCHK((dgrad_lds_launch<1, 1>(bd, on))); else HIPCHK((dgrad_direct_launch<1, 1>(bd, on)));
     }
     for (int i = l.L - 2; i >= 1; --i) {
       GemmBatch b{}; b.n = 2; b.prob[0] = dgrad_of(i); b.prob[1] = wgrad_of(i + 1);
-      ScopedTiming t(h, 4, st);
-      if (lds_ok_of(i)) HIPCHK((bwd_seq_launch<true>(b, st))); else HIPCHK((bwd_seq_launch<false>(b, st)));
+      const LaunchOn on = timed(h, kFamBwdPair, st);
+      if (lds_ok_of(i)) HIPCHK((bwd_seq_launch<true>(b, on))); else HIPCHK((bwd_seq_launch<false>(b, on)));
       if (h->comm && h->dp_per_layer) RC(dp_reduce_slice(h, st, net, l.w_off[i + 1], layer_slice(i + 1)));
     }
     {
       GemmBatch b{}; b.n = 2; b.prob[0] = wgrad_of(1); b.prob[1] = wgrad_of(0);
       const HeadWgradRider none{};
-      ScopedTiming t(h, 2, st);
-      if (l.NH == 1) HIPCHK((wgrad_tail_launch<1>(b, rider ? *rider : none, st, tails))); else HIPCHK((wgrad_tail_launch<kNO>(b, rider ? *rider : none, st, tails)));
+      const LaunchOn on = timed(h, kFamWgrad, st);
+      if (l.NH == 1) HIPCHK((wgrad_tail_launch<1>(b, r.rider ? *r.rider : none, on, r.tails))); else HIPCHK((wgrad_tail_launch<kNO>(b, r.rider ? *r.rider : none, on, r.tails)));
       if (h->comm && h->dp_per_layer) RC(dp_reduce_slice(h, st, net, l.w_off[0], layer_slice(0) + layer_slice(1)));
     }
     if (qrider) return fail("internal: the q-head rider found no carrier launch");
     return 0;
   }
-  if (tails != nullptr) return fail("internal: the tails block rides in the shifted schedule's last launch only");
+  if (r.tails != nullptr) return fail("internal: the tails block rides in the shifted schedule's last launch only");
   for (int i = l.L - 1; i >= 0; --i) {
     GemmBatch bd{}, bw{};
     const bool need_dx = (i > 0 || input_grad);
@@ -151,39 +149,38 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
     const bool lds_ok = lds_ok_of(i);
     if (need_dx && want_w) {               // ONE workgroup type: its wgrad tile, then its dgrad tile (gemm_bwd_seq)
       GemmBatch b{}; b.n = 2; b.prob[0] = bd.prob[0]; b.prob[1] = bw.prob[0];
-      ScopedTiming t(h, 4, st);
+      const LaunchOn on = timed(h, kFamBwdPair, st);
       // small minibatches / narrow layers: when the dgrad's 64x16 tiles and the wgrad's 64x64 tiles together still fit
       // the chip in one round, they run side by side on their own workgroups (one tile's chain per launch, not two)
       if (bwd_layer_is_pair(l, i, rows)) {
-        if (lds_ok) HIPCHK((bwd_pair_direct_launch<1, true>(b, st))); else HIPCHK((bwd_pair_direct_launch<1, false>(b, st)));
-      } else if (lds_ok) HIPCHK((bwd_seq_launch<true>(b, st)));
-      else HIPCHK((bwd_seq_launch<false>(b, st)));
-    } else if (need_dx && i == 0 && fuse != nullptr) {
+        if (lds_ok) HIPCHK((bwd_pair_direct_launch<1, true>(b, on))); else HIPCHK((bwd_pair_direct_launch<1, false>(b, on)));
+      } else if (lds_ok) HIPCHK((bwd_seq_launch<true>(b, on)));
+      else HIPCHK((bwd_seq_launch<false>(b, on)));
+    } else if (need_dx && i == 0 && r.fuse != nullptr) {
       GemmProblem p = bd.prob[0];
-      p.P += in_lo; p.C = nullptr; p.Pdim = 16; p.mask = nullptr;
-      fuse->pr = p;
+      p.P += r.in_lo; p.C = nullptr; p.Pdim = 16; p.mask = nullptr;
+      r.fuse->pr = p;
       const QHeadRider none{};
-      ScopedTiming t(h, 1, st);
-      HIPCHK(dqda_head_bwd_launch(*fuse, qrider ? *qrider : none, st));
+      HIPCHK(dqda_head_bwd_launch(*r.fuse, qrider ? *qrider : none, timed(h, kFamDgrad, st)));
       qrider = nullptr;
-    } else if (need_dx && i == 0 && in_hi > in_lo && rows % 16 == 0) {
+    } else if (need_dx && i == 0 && r.in_hi > r.in_lo && rows % 16 == 0) {
       GemmProblem& p = bd.prob[0];
-      const int c0 = (in_lo / 16) * 16, c1 = std::min(l.kp[0], (in_hi + 15) / 16 * 16);
+      const int c0 = (r.in_lo / 16) * 16, c1 = std::min(l.kp[0], (r.in_hi + 15) / 16 * 16);
       p.P += c0; p.C += c0; p.Pdim = c1 - c0;
       if (p.mask) p.mask += c0;
-      ScopedTiming t(h, 1, st);
-      if (qrider) { HIPCHK(dgrad_narrow_qrider_launch(bd, *qrider, st)); qrider = nullptr; }
-      else HIPCHK(dgrad_narrow_launch(bd, st));
+      const LaunchOn on = timed(h, kFamDgrad, st);
+      if (qrider) { HIPCHK(dgrad_narrow_qrider_launch(bd, *qrider, on)); qrider = nullptr; }
+      else HIPCHK(dgrad_narrow_launch(bd, on));
     } else if (need_dx) {
-      ScopedTiming t(h, 1, st);
-      if (lds_ok) HIPCHK((dgrad_lds_launch<1, 1>(bd, st)));
-      else HIPCHK((dgrad_direct_launch<1, 1>(bd, st)));
+      const LaunchOn on = timed(h, kFamDgrad, st);
+      if (lds_ok) HIPCHK((dgrad_lds_launch<1, 1>(bd, on)));
+      else HIPCHK((dgrad_direct_launch<1, 1>(bd, on)));
     } else {
       // wgrad alone = the first layer (K_in = 64 / 128 columns): 16-output tiles, 4x the workgroups
-      ScopedTiming t(h, 2, st);
-      if (rider) {                                    // + the head's dW / db as rider blocks (head_wgrad_can_ride)
-        if (l.NH == 1) HIPCHK((wgrad_narrow_rider_launch<1>(bw, *rider, st))); else HIPCHK((wgrad_narrow_rider_launch<kNO>(bw, *rider, st)));
-      } else HIPCHK((wgrad_narrow_launch<1>(bw, st)));
+      const LaunchOn on = timed(h, kFamWgrad, st);
+      if (r.rider) {                                    // + the head's dW / db as rider blocks (head_wgrad_can_ride)
+        if (l.NH == 1) HIPCHK((wgrad_narrow_rider_launch<1>(bw, *r.rider, on))); else HIPCHK((wgrad_narrow_rider_launch<kNO>(bw, *r.rider, on)));
+      } else HIPCHK((wgrad_narrow_launch<1>(bw, on)));
     }
     // data parallel, bucketed: layer i's dW/db are final once this launch has run -> start their
     // all-reduce on the communication stream while the chain continues with layer i-1
@@ -195,20 +192,15 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
 
 // rows >= 1024: the bandwidth-tiled kernel pair; optionally emits the scaled fp16 panels itself
 template <int NH>
+constexpr size_t head_bwd_big_lds_bytes() { return (size_t)(64 * NH + 4 * NH * 256) * sizeof(float); }
+template <int NH>
 int head_backward_big(H* h, hipStream_t st, HeadBwdArgs a, h16* dZ16, float scale16) {
   HeadBwdBigArgs b{}; b.a = a; b.dZ16 = dZ16; b.scale16 = scale16; b.slab2 = h->head_slab2;
   const int chunks = a.rows / 64;
   const int riders = a.q_out != nullptr ? chunks : 0;     // as many rider blocks again: 4 rows per block and round
   b.chunks = riders ? chunks : 0;
-  const size_t lds = (size_t)(64 * NH + 4 * NH * 256) * sizeof(float);
-  static bool prepared = false;
-  if (!prepared) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_bwd_big<NH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); prepared = true; }
-  hipLaunchKernelGGL((k_head_bwd_big<NH>), dim3(chunks + riders, a.H / 256), dim3(256), lds, st, b);
-  HIPCHK(hipGetLastError());
-  if (a.dW != nullptr) {
-    hipLaunchKernelGGL((k_head_wred<NH>), dim3(a.H / 64, NH), dim3(256), 0, st, b, chunks);
-    HIPCHK(hipGetLastError());
-  }
+  HIPCHK(launch(st, k_head_bwd_big<NH>, dim3(chunks + riders, a.H / 256), dim3(256), head_bwd_big_lds_bytes<NH>(), b));
+  if (a.dW != nullptr) HIPCHK(launch(st, k_head_wred<NH>, dim3(a.H / 64, NH), dim3(256), 0, b, chunks));
   return 0;
 }
 
@@ -222,8 +214,7 @@ int head_backward(H* h, hipStream_t st, HeadBwdArgs a) {
   a.slab = h->head_slab; a.ticket = h->head_ticket;
   int ry = 0;                                               // extra grid rows for the q rider (16 rows per block)
   if (a.q_out != nullptr) { a.rc_blocks = RC; ry = ((a.rows + 15) / 16 + a.H / 64 - 1) / (a.H / 64); }
-  hipLaunchKernelGGL((k_head_bwd<NH>), dim3(a.H / 64, RC + ry), dim3(1024), lds, st, a);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_head_bwd<NH>, dim3(a.H / 64, RC + ry), dim3(1024), lds, a));
   return 0;
 }
 
@@ -274,8 +265,10 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
     if (!corr_pre) return fail("adam_launch: the update's bookkeeping needs the scalars k_gather leaves in DevState");
     a.tick_on = 1; a.tick = *tick;
   }
-  ScopedTiming t(h, 3, st);
-  LaunchTimer& lt = launch_timer();
+  // k_adam_soft_l0, k_adam_soft_fwd1_gather and k_adam_soft_gather below are launched while a multi-update or chain graph is being
+  // captured (cap_u >= 0) and never otherwise; a learner with kernel timing on does not capture, so their LaunchOn carries no events
+  if (h->timing && h->cap_u >= 0) return fail("internal: adam_launch inside a graph capture with kernel timing on");
+  const LaunchOn on = timed(h, kFamAdam, st);
   // 1536 blocks = 6 per CU, all resident at once (68 VGPRs: 7 waves per SIMD): with the loads hoisted above the prologue
   // same-box A/B gives 18.4 us per launch against 19.3 at 2048 (a second, short round of blocks), 19.4 at 1792, 18.7 at
   // 1280, 21.5 at 4096 (round 2, before the hoist: 512 .. 8192 within +-3 %, profiles/r02_adam_probe.txt)
@@ -289,20 +282,18 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
     if (tick == nullptr) return fail("adam_launch: the next update's first layers ride in the update's last launch");
     const int riders = next_l0->a.blocks + next_l0->c.blocks + next_l0->ct.blocks;
     const int ablocks = std::min(blocks, std::max(1536 - riders, 1280));
-    hipLaunchKernelGGL(k_adam_soft_l0, dim3(riders + ablocks), dim3(256), 0, st, a, next_l0->a, next_l0->c, next_l0->ct);
+    HIPCHK(launch(on, k_adam_soft_l0, dim3(riders + ablocks), dim3(256), 0, a, next_l0->a, next_l0->c, next_l0->ct));
   }
   else if (fl != nullptr && early_gather != nullptr) {
     if (blocks <= fl->blocks) return fail("adam_launch: no optimiser workgroups beside the first-layer riders");
     const int ablocks = std::min(blocks, std::max(1536 - early_gather->blocks, 1280));
-    if (fl->Kp == 64) hipLaunchKernelGGL(k_adam_soft_fwd1_gather<1>, dim3(early_gather->blocks + ablocks), dim3(256), 0, st, a, *fl, *early_gather);
-    else hipLaunchKernelGGL(k_adam_soft_fwd1_gather<2>, dim3(early_gather->blocks + ablocks), dim3(256), 0, st, a, *fl, *early_gather);
+    if (fl->Kp == 64) HIPCHK(launch(on, k_adam_soft_fwd1_gather<1>, dim3(early_gather->blocks + ablocks), dim3(256), 0, a, *fl, *early_gather));
+    else HIPCHK(launch(on, k_adam_soft_fwd1_gather<2>, dim3(early_gather->blocks + ablocks), dim3(256), 0, a, *fl, *early_gather));
   }
   else if (fl != nullptr) {
     if (blocks <= fl->blocks) return fail("adam_launch: no optimiser workgroups beside the first-layer riders");
-    const bool timed = lt.start != nullptr;
-    if (fl->Kp == 64) { if (timed) hipExtLaunchKernelGGL(k_adam_soft_fwd1<1>, dim3(blocks), dim3(256), 0, st, lt.start, lt.stop, 0, a, *fl); else hipLaunchKernelGGL(k_adam_soft_fwd1<1>, dim3(blocks), dim3(256), 0, st, a, *fl); }
-    else { if (timed) hipExtLaunchKernelGGL(k_adam_soft_fwd1<2>, dim3(blocks), dim3(256), 0, st, lt.start, lt.stop, 0, a, *fl); else hipLaunchKernelGGL(k_adam_soft_fwd1<2>, dim3(blocks), dim3(256), 0, st, a, *fl); }
-    if (timed) lt.start = lt.stop = nullptr;
+    if (fl->Kp == 64) HIPCHK(launch(on, k_adam_soft_fwd1<1>, dim3(blocks), dim3(256), 0, a, *fl));
+    else HIPCHK(launch(on, k_adam_soft_fwd1<2>, dim3(blocks), dim3(256), 0, a, *fl));
   }
   else if (tick && h->cap_u >= 0 && h->cap_u + 1 < h->cap_n && !early_l0(h)) {
     // inside a multi-update graph: the next update's gather rides in this, the update's last launch (k_adam_soft_gather).
@@ -311,11 +302,9 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
     // (511 optimiser blocks beside it: 35.4 against 27.3 us per launch at 4096 rows)
     const GatherArgs g = gather_args(h, nullptr, h->cap_u + 1);
     const int ablocks = std::min(blocks, std::max(1536 - g.blocks, 1280));
-    hipLaunchKernelGGL(k_adam_soft_gather, dim3(g.blocks + ablocks), dim3(256), 0, st, a, g);
+    HIPCHK(launch(on, k_adam_soft_gather, dim3(g.blocks + ablocks), dim3(256), 0, a, g));
   }
-  else if (lt.start) { hipExtLaunchKernelGGL(k_adam_soft, dim3(blocks), dim3(256), 0, st, lt.start, lt.stop, 0, a); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL(k_adam_soft, dim3(blocks), dim3(256), 0, st, a);
-  HIPCHK(hipGetLastError());
+  else HIPCHK(launch(on, k_adam_soft, dim3(blocks), dim3(256), 0, a));
   return 0;
 }
 
@@ -324,9 +313,8 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
 int sumsq_launch(H* h, int net, size_t begin, size_t end) {
   const NetLayout& l = layout_of(h, net);
   if (end == 0) end = l.arena;
-  if (h->dp_half) hipLaunchKernelGGL(k_sumsq_bf16, dim3(h->n_part_dp), dim3(256), 0, h->stream, (const uint16_t*)h->g16[net] + begin, h->g[net] + begin, (end - begin) / 4, h->part_dp);
-  else hipLaunchKernelGGL(k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->stream, h->g[net] + begin, (end - begin) / 4, h->part_dp);
-  HIPCHK(hipGetLastError());
+  if (h->dp_half) HIPCHK(launch(h->stream, k_sumsq_bf16, dim3(h->n_part_dp), dim3(256), 0, (const uint16_t*)h->g16[net] + begin, h->g[net] + begin, (end - begin) / 4, h->part_dp));
+  else HIPCHK(launch(h->stream, k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->g[net] + begin, (end - begin) / 4, h->part_dp));
   return 0;
 }
 // a net's [loss, q, flag, sum of squares] tail: behind its gradient arena (one all-reduce carries both), or in dp_tails
@@ -354,15 +342,11 @@ static int optimiser_step(H* h, hipStream_t st, int net, bool dp, const TickArgs
 
 // ---- mixed-precision building blocks (hgemm.hip.h) --------------------------------------------
 
-int hgemm_timed(H* h, hipStream_t st, const HGemm* gs, int n, int fam, int force = 0) {
-  ScopedTiming t(h, fam, st);
-  LaunchTimer& lt = launch_timer();
-  hipEvent_t a = lt.start, b = lt.stop;
-  lt.start = lt.stop = nullptr;
-  HIPCHK(hgemm_launch_batch(gs, n, st, force, a, b));
+int hgemm_timed(H* h, hipStream_t st, const HGemm* gs, int n, Family fam, int force = 0) {
+  HIPCHK(hgemm_launch_batch(gs, n, timed(h, fam, st), force));
   return 0;
 }
-int hgemm_timed(H* h, hipStream_t st, const HGemm& g, int fam) { return hgemm_timed(h, st, &g, 1, fam); }
+int hgemm_timed(H* h, hipStream_t st, const HGemm& g, Family fam) { return hgemm_timed(h, st, &g, 1, fam); }
 
 // fp32 master weights of `net` -> fp16 mirror [N][kp].  The Adam pass keeps the mirrors current by itself; this
 // runs after host-side weight changes (w16_dirty).
@@ -393,7 +377,7 @@ HGemm fwd16_problem(H* h, int p, int net, int rows, int i) {
 }
 int tower_forward16(H* h, hipStream_t st, int p, int net, int rows) {
   const NetLayout& l = layout_of(h, net);
-  for (int i = 0; i < l.L; ++i) RC(hgemm_timed(h, st, fwd16_problem(h, p, net, rows, i), 7));
+  for (int i = 0; i < l.L; ++i) RC(hgemm_timed(h, st, fwd16_problem(h, p, net, rows, i), kFamHgemmFwd));
   return 0;
 }
 // two independent passes of the same net kind, layer by layer in ONE launch each (the target and
@@ -402,7 +386,7 @@ int tower_forward16_pair(H* h, hipStream_t st, int p0, int net0, int p1, int net
   const NetLayout& l = layout_of(h, net0);
   for (int i = 0; i < l.L; ++i) {
     const HGemm gs[2] = {fwd16_problem(h, p0, net0, rows, i), fwd16_problem(h, p1, net1, rows, i)};
-    RC(hgemm_timed(h, st, gs, 2, 7));
+    RC(hgemm_timed(h, st, gs, 2, kFamHgemmFwd));
   }
   return 0;
 }
@@ -419,7 +403,6 @@ int tower_forward16_pair(H* h, hipStream_t st, int p0, int net0, int p1, int net
 struct Bwd16Riders { float* partial = nullptr; const HeadWsum* rider = nullptr; const TailsArgs* tails = nullptr; };
 int tower_backward16(H* h, hipStream_t st, int net, int p, float* garena, float* dZ32_0, int rows,
                      bool want_w, bool input_grad, float ls, const Bwd16Riders& r = Bwd16Riders{}) {
-  float* partial = r.partial; const HeadWsum* rider = r.rider; const TailsArgs* tails = r.tails;
   const NetLayout& l = layout_of(h, net);
   const int kind = net & 1;
   h16** dZ = h->dZ16[kind];
@@ -450,40 +433,36 @@ int tower_backward16(H* h, hipStream_t st, int net, int p, float* garena, float*
       g.B = h->act16[p][i]; g.ldb = h->k16[kind][i]; g.tb = 1;
       g.M = l.dims[i + 1]; g.N = h->k16[kind][i]; g.K = rows;
       g.C32 = garena + l.w_off[i]; g.ldc32 = l.kp[i]; g.n_valid32 = l.kp[i]; g.scale32 = 1.0f / ls;
-      if (partial) g.sumsq_partial = partial + l.part_off[i];      // clip-norm share of this layer's dW (unscaled)
+      if (r.partial) g.sumsq_partial = r.partial + l.part_off[i];      // clip-norm share of this layer's dW (unscaled)
     }
-    if (grouped) { if (need_dx) RC(hgemm_timed(h, st, gd, 8)); continue; }
+    if (grouped) { if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad)); continue; }
     // per-layer form: both read dZ[i+1] and neither reads the other's output — at small minibatches (both on the
     // 64x64 split-K tile) they share one launch
     if (need_dx && want_w && hgemm_uses_small_tile(gd) && hgemm_uses_small_tile(gw) && gd.K % 128 == 0 && gw.K % 128 == 0) {
       const HGemm gs[2] = {gd, gw};
-      RC(hgemm_timed(h, st, gs, 2, 8, 2));      // both on the 64x64 tile, as each would be alone
+      RC(hgemm_timed(h, st, gs, 2, kFamHgemmDgrad, 2));      // both on the 64x64 tile, as each would be alone
     } else {
-      if (need_dx) RC(hgemm_timed(h, st, gd, 8));
-      if (want_w && (i > 0 || need_dx)) RC(hgemm_timed(h, st, gw, 9));
+      if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad));
+      if (want_w && (i > 0 || need_dx)) RC(hgemm_timed(h, st, gw, kFamHgemmWgrad));
     }
   }
   if (!want_w) return 0;
   // db_i = column sums of dZ[i+1] [rows][n_out], one workgroup per 64 columns
-  Db16Batch db{}; db.scale = 1.0f / ls; db.sumsq_partial = partial ? partial + l.part_db : nullptr;
+  Db16Batch db{}; db.scale = 1.0f / ls; db.sumsq_partial = r.partial ? r.partial + l.part_db : nullptr;
   int db_blocks = 0;
   for (int i = 0; i < l.L; ++i) { db.d[db.n++] = Db16{dZ[i + 1], l.dims[i + 1], l.dims[i + 1], rows, garena + l.b_off[i], db_blocks}; db_blocks += l.dims[i + 1] / 64; }
-  ScopedTiming t(h, 9, st);
-  LaunchTimer& lt = launch_timer();
-  hipEvent_t e0 = lt.start, e1 = lt.stop;
-  lt.start = lt.stop = nullptr;
+  const LaunchOn on = timed(h, kFamHgemmWgrad, st);
   if (grouped) {
     // 128x128 tiles: a quarter of the operand bytes per FLOP of the 64x64 split-K tile (fp16 mode guarantees
     // hidden % 128 == 0, minibatch % 128 == 0 and a 128-wide first panel, so every wgrad tiles)
-    HIPCHK(hgemm_group_db_launch(gws, l.L, true, db, db_blocks, st, e0, e1, rider, tails));
+    HIPCHK(hgemm_group_db_launch(gws, l.L, true, db, db_blocks, on, r.rider, r.tails));
   } else if (!input_grad && hgemm_uses_small_tile(gws[0]) && gws[0].K % 128 == 0) {
     // per-layer form: the first layer's wgrad (few tiles, long reduction) carries the column sums
-    HIPCHK(hgemm_group_db_launch(gws, 1, false, db, db_blocks, st, e0, e1, rider, tails));
+    HIPCHK(hgemm_group_db_launch(gws, 1, false, db, db_blocks, on, r.rider, r.tails));
   } else {
-    if (rider != nullptr || tails != nullptr) return fail("internal: the fp16 backward found no carrier launch for its riders");
-    if (!input_grad) HIPCHK(hgemm_launch(gws[0], st, 0, e0, e1));
-    hipLaunchKernelGGL(k_db16_cols<0>, dim3(db_blocks), dim3(256), 0, st, db);
-    HIPCHK(hipGetLastError());
+    if (r.rider != nullptr || r.tails != nullptr) return fail("internal: the fp16 backward found no carrier launch for its riders");
+    if (!input_grad) HIPCHK(hgemm_launch(gws[0], on));
+    HIPCHK(launch(st, k_db16_cols<0>, dim3(db_blocks), dim3(256), 0, db));
   }
   return 0;
 }
@@ -520,8 +499,7 @@ static TailsArgs actor_tails(const H* h) {
   return TailsArgs{(const float*)nullptr, 0, (const double*)h->q_partial, h->B, inv_batch_of(h), (float*)nullptr, grad_tail(h, DQNHIP_ACTOR), &h->st->flags, 0};
 }
 static int tails_launch(hipStream_t st, const TailsArgs& t) {
-  hipLaunchKernelGGL(k_tails, dim3(1), dim3(256), 0, st, t);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_tails, dim3(1), dim3(256), 0, t));
   return 0;
 }
 // the bookkeeping block of the update's last launch: publishes (critic_loss, avg_q), advances the iteration / sampling counters
@@ -533,8 +511,7 @@ static TickArgs tick_args(const H* h, bool dp) {
 static int gather_launch(H* h, hipStream_t st, const int* idx_dev) {
   if (h->cap_u > 0) return 0;
   const GatherArgs g = gather_args(h, idx_dev, h->cap_u);
-  hipLaunchKernelGGL(k_gather, dim3(g.blocks), dim3(256), 0, st, g);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_gather, dim3(g.blocks), dim3(256), 0, g));
   return 0;
 }
 
@@ -568,8 +545,7 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       // with the head's dW / db riding in the net's last backward launch, the scaled fp16 tower-top gradient comes out of
       // this launch too (HeadTrainArgs::dZ16) — Step(1) has no head-backward launch (as on the fp32 path)
       if (P.fuse_q) { t.dZ16 = h->dZ16[1][L]; t.scale16 = h->ls_c; }
-      hipLaunchKernelGGL(k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, st, t);
-      HIPCHK(hipGetLastError());
+      HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
     }
     const TailsArgs tails_c = critic_tails(h);
     {
@@ -598,7 +574,7 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
     for (int i = 0; i < L; ++i) {
       HGemm g = fwd16_problem(h, 4, DQNHIP_CRITIC, B, i);
       if (fused_seed && i == L - 1) { g.seed_w = wat(h, DQNHIP_CRITIC, lc.hw_off); g.CS16 = h->dZ16[1][L]; g.ldcs16 = Hc; g.seed_scale = h->ls_q; }
-      RC(hgemm_timed(h, st, g, 7));
+      RC(hgemm_timed(h, st, g, kFamHgemmFwd));
     }
     if (!fused_seed) {
       // q(s, mu(s)) rides in the dq = -1 head launch (rider blocks)
@@ -676,8 +652,7 @@ int first_layers_launch(H* h, hipStream_t st, int rows, bool with_actor) {
   fill(b.prob[2], DQNHIP_CRITIC_TARGET, lc, h->act[2][0], h->Zs, round_up(h->S, 64), false);
   b.prob[2].xcopy_dst = h->Wact_t; b.prob[2].xcopy_col = h->S; b.prob[2].xcopy_n = kNO;
   if (with_actor) fill(b.prob[3], DQNHIP_ACTOR, la, h->act[1][0], h->act[1][1], la.kp[0], true);
-  ScopedTiming t(h, 6, st);
-  HIPCHK((fwd_direct_launch<4, 2>(b, st)));
+  HIPCHK((fwd_direct_launch<4, 2>(b, timed(h, kFamFwdDirect, st))));
   return 0;
 }
 int run_phase(H* h, int phase, const int* idx_dev) {
@@ -737,10 +712,7 @@ int run_phase(H* h, int phase, const int* idx_dev) {
     // with the head's dW / db riding in the net's last backward launch, the head's dZ comes out of this launch too
     if (P.head_rides_c) qt_args.dZ = h->dZc[L];
     qt_args.pdt = h->qdot[0]; qt_args.pd = h->qdot[1];
-    if (!fuse_q) {
-      hipLaunchKernelGGL(k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, st, qt_args);
-      HIPCHK(hipGetLastError());
-    }
+    if (!fuse_q) HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, qt_args));
     // critic backward (rest of Step(1)): head (dgrad + ReLU' + wgrad fused), then tower; wgrad
     // writes (beta=0) so ClearParamDiffs/ZeroGradParameters (src/dqn.cpp:63-78, 908-909) vanish
     {
@@ -844,26 +816,21 @@ int run_phase(H* h, int phase, const int* idx_dev) {
 }
 
 int to_bf16_launch(H* h, int net) {
-  hipLaunchKernelGGL(k_to_bf16, dim3(1024), dim3(256), 0, h->stream, (const float*)h->g[net], layout_of(h, net).arena / 4, h->g16[net]);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_to_bf16, dim3(1024), dim3(256), 0, (const float*)h->g[net], layout_of(h, net).arena / 4, h->g16[net]));
   return 0;
 }
 int shard_scal_launch(H* h, float* tail) {
-  hipLaunchKernelGGL(k_shard_scal, dim3(1), dim3(256), 0, h->stream, (const float*)h->part_dp, h->n_part_dp, tail);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_shard_scal, dim3(1), dim3(256), 0, (const float*)h->part_dp, h->n_part_dp, tail));
   return 0;
 }
-// dynamic LDS above the 64 KB default, for THIS unit's copies of the kernels (k_head_bwd_big: head_backward_big, on first use)
+// dynamic-LDS limits, for THIS unit's copies of the kernels (it launches every kernel of the update)
 int prepare_kernels(const H* h) {
   if (h->fp16) HIPCHK(hgemm_prepare_all());
-  HIPCHK(direct_prepare(gemm_bwd_seq<true>, 4 * 16 * 64 * 16 + 4 * 16 * 16));
-  HIPCHK(direct_prepare(gemm_bwd_seq<false>, 4 * 16 * 64 * 16 + 4 * 16 * 16));
-  HIPCHK(direct_prepare(gemm_wgrad_tail<1>, 80 * 1024));
-  HIPCHK(direct_prepare(gemm_wgrad_tail<kNO>, 80 * 1024));
-  HIPCHK(direct_prepare((gemm_bwd_pair_direct<1, true>), 4 * 16 * 64 * 16 + 4 * 16 * 16));
-  HIPCHK(direct_prepare((gemm_bwd_pair_direct<1, false>), 4 * 16 * 64 * 16 + 4 * 16 * 16));
-  HIPCHK(direct_prepare(gemm_fwd_lds<4, 2, false>, 4 * 2 * 6 * 512 * 4));
-  HIPCHK(direct_prepare(gemm_fwd_lds<4, 2, true>, 4 * 2 * 6 * 512 * 4));
+  HIPCHK(direct_prepare_all());
+  if (h->head_slab2 != nullptr) {                          // head_big_ok
+    HIPCHK(direct_prepare(k_head_bwd_big<1>, (int)head_bwd_big_lds_bytes<1>()));
+    HIPCHK(direct_prepare(k_head_bwd_big<kNO>, (int)head_bwd_big_lds_bytes<kNO>()));
+  }
   return 0;
 }
 
@@ -884,11 +851,9 @@ int dqnhip_apply_update(dqnhip_handle h, int32_t net) {
   HIPCHK(hipSetDevice(h->cfg.device));
   RC(sync_dirty16(h));
   const NetLayout& l = layout_of(h, net);
-  hipLaunchKernelGGL(k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->stream, h->g[net], l.arena / 4, h->part_dp);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->g[net], l.arena / 4, h->part_dp));
   RC(adam_launch(h, h->stream, net, h->part_dp, h->n_part_dp, 0, l.arena, nullptr, false));   // no gather ran: the pass evaluates its own correction
-  hipLaunchKernelGGL(k_advance_iter, dim3(1), dim3(1), 0, h->stream, h->st, (int)net, h->stats_dev);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_advance_iter, dim3(1), dim3(1), 0, h->st, (int)net, h->stats_dev));
   if (net == DQNHIP_ACTOR) h->h_actor_iter += 1; else h->h_critic_iter += 1;
   return 0;
 }
@@ -913,14 +878,12 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world) {
   const size_t slice = l.arena / (size_t)world;
   float* tail = h->shard_total + 4;
   for (int r = 0; r < world; ++r) {
-    hipLaunchKernelGGL(k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->stream, h->g[net] + r * slice, slice / 4, h->part_dp);
-    hipLaunchKernelGGL(k_shard_scal, dim3(1), dim3(256), 0, h->stream, (const float*)h->part_dp, h->n_part_dp, tail);
-    hipLaunchKernelGGL(k_shard_accumulate, dim3(1), dim3(1), 0, h->stream, h->shard_total, (const float*)tail, r == 0 ? 1 : 0);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch(h->stream, k_sumsq, dim3(h->n_part_dp), dim3(256), 0, h->g[net] + r * slice, slice / 4, h->part_dp));
+    HIPCHK(launch(h->stream, k_shard_scal, dim3(1), dim3(256), 0, (const float*)h->part_dp, h->n_part_dp, tail));
+    HIPCHK(launch(h->stream, k_shard_accumulate, dim3(1), dim3(1), 0, h->shard_total, (const float*)tail, r == 0 ? 1 : 0));
   }
   for (int r = 0; r < world; ++r) RC(adam_launch(h, h->stream, net, h->shard_total, 1, r * slice, (r + 1) * slice, nullptr, false));
-  hipLaunchKernelGGL(k_advance_iter, dim3(1), dim3(1), 0, h->stream, h->st, (int)net, h->stats_dev);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_advance_iter, dim3(1), dim3(1), 0, h->st, (int)net, h->stats_dev));
   if (net == DQNHIP_ACTOR) h->h_actor_iter += 1; else h->h_critic_iter += 1;
   return 0;
 }

@@ -71,8 +71,7 @@ static int env_create_impl(dqnhip_env* e) {
   for (int i = 1; i <= h->L; ++i) RC(env_alloc(e, &e->acts[i], Np * h->la.kp[i]));
   RC(env_alloc(e, &e->eps_dev, 16)); d.eps = e->eps_dev;
   RC(env_alloc(e, &e->commit_ticket, 32));
-  hipLaunchKernelGGL(k_env_init, dim3(d.N), dim3(64), d.SP * sizeof(float), h->stream, d);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_env_init, dim3(d.N), dim3(64), d.SP * sizeof(float), d));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -135,9 +134,8 @@ static int env_one_step(dqnhip_env* e, bool more_follow) {
     p.tiles_p = p.Pdim / 32; p.tiles_q = p.Qdim / 32; p.tile_base = 0;
     b.total_tiles = p.tiles_p * p.tiles_q;
     const size_t lds = std::max<size_t>(4 * 2 * 2 * 64 * 16, d.T * sizeof(float));
-    hipLaunchKernelGGL(k_env_l0_flush, dim3(b.total_tiles + d.N), dim3(256), lds, st, b, d, RO(h)->ring,
-                       (const DevState*)RO(h)->st, h->cfg.gamma);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch(st, k_env_l0_flush, dim3(b.total_tiles + d.N), dim3(256), lds, b, d, RO(h)->ring,
+                       (const DevState*)RO(h)->st, h->cfg.gamma));
     e->flush_deferred = false;
     first = 1;
   }
@@ -147,15 +145,12 @@ static int env_one_step(dqnhip_env* e, bool more_follow) {
     a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.b = wat(h, DQNHIP_ACTOR, la.hb_off); a.out16 = d.out16;
     RC((head_forward<kNO, HEAD_ACTOR>(h, st, a)));
   }
-  hipLaunchKernelGGL(k_env_step, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), st, d);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_env_step, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), d));
   if (more_follow && fused && l0_direct && !h->timing) { e->flush_deferred = true; return 0; }
-  hipLaunchKernelGGL(k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), st, d, RO(h)->ring,
-                     (const DevState*)RO(h)->st, h->cfg.gamma);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring,
+                     (const DevState*)RO(h)->st, h->cfg.gamma));
   if (d.commit_ticket == nullptr) {
-    hipLaunchKernelGGL(k_env_commit, dim3(1), dim3(256), 0, st, d, RO(h)->ring, RO(h)->st);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch(st, k_env_commit, dim3(1), dim3(256), 0, d, RO(h)->ring, RO(h)->st));
   }
   return 0;
 }
@@ -186,8 +181,7 @@ int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
   RingUse ring_use(h);
-  hipLaunchKernelGGL(k_set_float<0>, dim3(1), dim3(1), 0, st, e->eps_dev, epsilon);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(st, k_set_float<0>, dim3(1), dim3(1), 0, e->eps_dev, epsilon));
   // the step is a fixed launch sequence (9 launches at L = 4, ~6 us each when launch-bound): replay it
   // as a hipGraph unless the learner's layers may be re-pointed (sharing) or graphs are off
   const bool use_graph = h->cfg.use_graph && !e->graph_failed && !h->timing && !h->w_owner && !h->ring_owner;

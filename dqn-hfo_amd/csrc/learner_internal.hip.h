@@ -90,7 +90,10 @@ struct NetLayout {
 
 void layout_init(NetLayout& l, int in_dim, const dqnhip_config& c, bool actor);
 
-struct TimingRec { int family; hipEvent_t a, b; };
+// the kernel families of timing mode (dqnhip_get_kernel_timing), named by kFamily[] (learner.hip)
+enum Family { kFamFwdLds4x2, kFamDgrad, kFamWgrad, kFamAdam, kFamBwdPair, kFamFwdLds2x2, kFamFwdDirect, kFamHgemmFwd, kFamHgemmDgrad, kFamHgemmWgrad, kNumFamily };
+extern const char* const kFamily[kNumFamily];
+struct TimingRec { Family family; hipEvent_t a, b; };
 
 // the captured launch sequences a single learner replays (dqnhip_learner::graph_exec)
 enum GraphSlot {
@@ -250,21 +253,15 @@ struct RingUse {
   }
 };
 
-extern const char* const kFamily[];
-constexpr int kNumFamily = 10;
-
-// Timing mode: the NEXT kernel launch (through direct_launch / adam_launch) is bracketed by the
-// dispatch packet's own timestamps (hipExtLaunchKernelGGL start/stop events).
-struct ScopedTiming {
-  ScopedTiming(H* h, int fam, hipStream_t) {
-    if (h->timing) {
-      hipEvent_t a = nullptr, b = nullptr;
-      hipEventCreate(&a); hipEventCreate(&b);
-      launch_timer().start = a; launch_timer().stop = b;
-      h->recs.push_back({fam, a, b});
-    }
-  }
-};
+// Where one launch of family `fam` goes: `st`, and in timing mode a fresh event pair, filed in h->recs, that launch() has the
+// dispatch packet stamp.  The caller hands the result to exactly ONE launcher: events that no launch records cannot be read back.
+inline LaunchOn timed(H* h, Family fam, hipStream_t st) {
+  if (!h->timing) return st;
+  hipEvent_t a = nullptr, b = nullptr;
+  hipEventCreate(&a); hipEventCreate(&b);
+  h->recs.push_back({fam, a, b});
+  return {st, a, b};
+}
 
 // ---- dense (Caffe order) <-> internal arena ----------------------------------
 void dense_to_arena(const NetLayout& l, const float* dense, std::vector<float>& arena);
@@ -289,12 +286,11 @@ template <int NH, int MODE>
 int head_forward(H* h, hipStream_t st, const HeadArgs& a, const HeadArgs* b = nullptr) {
   HeadArgs2 a2{}; a2.p[0] = a; if (b) a2.p[1] = *b;
   if (NH > 1 && a.rows >= 1024 && a.H <= 1024 && a.H % 4 == 0)   // (single-head: the block-per-row form measured faster, 6.6 vs 8.8 us)
-    hipLaunchKernelGGL((k_head_fwd_rows<NH, MODE>), dim3(256, b ? 2 : 1), dim3(256), 0, st, a2);
+    HIPCHK(launch(st, k_head_fwd_rows<NH, MODE>, dim3(256, b ? 2 : 1), dim3(256), 0, a2));
   else if (a.l1_y != nullptr || (b && b->l1_y != nullptr))      // Step(1): the target actor's head also finishes critic_target's first layer
-    hipLaunchKernelGGL((k_head_fwd<NH, MODE, true>), dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, st, a2);
+    HIPCHK(launch(st, k_head_fwd<NH, MODE, true>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
   else
-    hipLaunchKernelGGL((k_head_fwd<NH, MODE, false>), dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, st, a2);
-  HIPCHK(hipGetLastError());
+    HIPCHK(launch(st, k_head_fwd<NH, MODE, false>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
   return 0;
 }
 constexpr int kMultiU = 16;    // updates per replay of the multi-update graph (dqnhip_update_async_n; see learner_update.hip)
@@ -332,7 +328,7 @@ int to_bf16_launch(H* h, int net);                       // k_to_bf16: the bf16 
 int shard_scal_launch(H* h, float* tail);                // k_shard_scal: this rank's share of the clip norm -> tail[3]
 int run_phase(H* h, int phase, const int* idx_dev);
 int sync_dirty16(H* h);
-int prepare_kernels(const H* h);                         // the launch attributes (dynamic LDS above 64 KB) of the update's kernels
+int prepare_kernels(const H* h);                         // the launch attributes (dynamic-LDS limits) of the update's kernels
 // learner_update.hip
 int refresh_ring(H* h);
 int stage_indices(H* h, const int32_t* idx_host, const int** idx_dev);

@@ -19,16 +19,14 @@ static int actor_forward_dev(H* h, int net, const float* states_dev, int n, floa
   float* p = h->act_buf;
   for (int i = 0; i <= l.L; ++i) { acts[i] = p; p += (size_t)rows * std::max(h->la.kp[i], h->lc.kp[i]); }
   float* out16 = p;
-  hipLaunchKernelGGL(k_pack_rows, dim3((rows * l.kp[0] + 255) / 256), dim3(256), 0, h->stream, states_dev, n,
-                     h->S, acts[0], rows, l.kp[0]);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_pack_rows, dim3((rows * l.kp[0] + 255) / 256), dim3(256), 0, states_dev, n,
+                     h->S, acts[0], rows, l.kp[0]));
   FwdPass fp[1] = {{net, &l, acts}};
   RC(tower_forward(h, h->stream, fp, 1, rows));
   HeadArgs a{}; a.X = acts[l.L]; a.ldx = l.dims[l.L]; a.H = l.dims[l.L]; a.rows = rows;
   a.W = wat(h, net, l.hw_off); a.b = wat(h, net, l.hb_off); a.out16 = out16;
   RC((head_forward<kNO, HEAD_ACTOR>(h, h->stream, a)));
-  hipLaunchKernelGGL(k_unpack_out, dim3((n * kNO + 255) / 256), dim3(256), 0, h->stream, (const float*)out16, n, out_dev);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_unpack_out, dim3((n * kNO + 255) / 256), dim3(256), 0, (const float*)out16, n, out_dev));
   return 0;
 }
 
@@ -76,9 +74,8 @@ int dqnhip_critic_forward(dqnhip_handle h, int32_t net, const float* states_host
   float* acts[kMaxL + 1];
   float* p = h->act_buf;
   for (int i = 0; i <= l.L; ++i) { acts[i] = p; p += (size_t)rows * std::max(h->la.kp[i], h->lc.kp[i]); }
-  hipLaunchKernelGGL(k_pack_critic, dim3((rows * l.kp[0] + 255) / 256), dim3(256), 0, h->stream, (const float*)sdev,
-                     (const float*)adev, n, h->S, acts[0], rows, l.kp[0]);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_pack_critic, dim3((rows * l.kp[0] + 255) / 256), dim3(256), 0, (const float*)sdev,
+                     (const float*)adev, n, h->S, acts[0], rows, l.kp[0]));
   FwdPass fp[1] = {{net, &l, acts}};
   RC(tower_forward(h, h->stream, fp, 1, rows));
   HeadArgs a{}; a.X = acts[l.L]; a.ldx = l.dims[l.L]; a.H = l.dims[l.L]; a.rows = rows;
@@ -102,9 +99,8 @@ static int add_dev(H* h, const float* s, const float* a, const float* r, const f
   const long long cap = RO(h)->ring.cap;
   if (single == 0 && n >= cap) return fail("AddTransitions: batch of %d does not fit capacity %lld (the reference would pop an empty deque)", n, cap);
   if (single == 2 && RO(h)->h_size + n > cap) return fail("LoadReplayMemory: %lld transitions exceed the capacity %lld", RO(h)->h_size + n, cap);
-  hipLaunchKernelGGL(k_add_transitions, dim3(std::max(1, (n + 3) / 4)), dim3(256), 0, h->stream, RO(h)->ring, RO(h)->st, s, a, r, mc, nx,
-                     term, n, single, RO(h)->done_counter);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_add_transitions, dim3(std::max(1, (n + 3) / 4)), dim3(256), 0, RO(h)->ring, RO(h)->st, s, a, r, mc, nx,
+                     term, n, single, RO(h)->done_counter));
   // host mirror of the same deque arithmetic (src/dqn.cpp:768-781)
   if (single == 2) { }
   else if (single) { if (RO(h)->h_size == cap) { RO(h)->h_head = (RO(h)->h_head + 1) % cap; RO(h)->h_size -= 1; } }
@@ -198,9 +194,8 @@ static int read_memory_impl(H* h, int32_t first, int32_t n, float* states, float
   float* ds = (float*)base; float* dn = (float*)(base + sb); float* da = (float*)(base + 2 * sb);
   float* dr = (float*)(base + 2 * sb + ab); float* dm = (float*)(base + 2 * sb + ab + vb);
   uint8_t* dt = (uint8_t*)(base + 2 * sb + ab + 2 * vb);
-  hipLaunchKernelGGL(k_read_memory, dim3((n + 3) / 4), dim3(256), 0, h->stream, RO(h)->ring, (const DevState*)RO(h)->st, first, n,
-                     ds, da, dr, dm, dn, dt);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_read_memory, dim3((n + 3) / 4), dim3(256), 0, RO(h)->ring, (const DevState*)RO(h)->st, first, n,
+                     ds, da, dr, dm, dn, dt));
   if (states) HIPCHK(hipMemcpyAsync(states, ds, (size_t)n * h->S * 4, hipMemcpyDeviceToHost, h->stream));
   if (next_states) HIPCHK(hipMemcpyAsync(next_states, dn, (size_t)n * h->S * 4, hipMemcpyDeviceToHost, h->stream));
   if (actor_out) HIPCHK(hipMemcpyAsync(actor_out, da, (size_t)n * kNO * 4, hipMemcpyDeviceToHost, h->stream));
@@ -240,9 +235,8 @@ int dqnhip_sample_states(dqnhip_handle h, const int32_t* idx_host, int32_t n, fl
       if (idx_host[i] < 0 || idx_host[i] >= size) return fail("sampled index %d = %d out of range [0,%lld)", i, idx_host[i], size);
     HIPCHK(hipMemcpyAsync(di, idx_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
   }
-  hipLaunchKernelGGL(k_sample_states, dim3((n + 3) / 4), dim3(256), 0, h->stream, RO(h)->ring, (const DevState*)RO(h)->st,
-                     idx_host ? (const int*)di : (const int*)nullptr, sample_key(h) ^ 0x5354415445535F5Full, h->sample_states_calls, n, ds);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(h->stream, k_sample_states, dim3((n + 3) / 4), dim3(256), 0, RO(h)->ring, (const DevState*)RO(h)->st,
+                     idx_host ? (const int*)di : (const int*)nullptr, sample_key(h) ^ 0x5354415445535F5Full, h->sample_states_calls, n, ds));
   if (!idx_host) h->sample_states_calls += 1;
   HIPCHK(hipMemcpyAsync(states_host, ds, sb, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -279,8 +273,7 @@ int dqnhip_reduce_gradients_local(dqnhip_handle* hs, int32_t n, int32_t net) {
   a.n4 = (layout_of(hs[0], net).arena + 4) / 4;
   HIPCHK(hipSetDevice(hs[0]->cfg.device));
   for (int i = 1; i < n; ++i) HIPCHK(hipStreamSynchronize(hs[i]->stream));   // their phase must be complete
-  hipLaunchKernelGGL(k_local_reduce, dim3(1024), dim3(256), 0, hs[0]->stream, a);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(hs[0]->stream, k_local_reduce, dim3(1024), dim3(256), 0, a));
   HIPCHK(hipStreamSynchronize(hs[0]->stream));
   return 0;
 }
@@ -579,8 +572,9 @@ int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
   if (!h || !family) return fail("null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   int fam = -1;
-  for (int i = 0; i < kNumFamily; ++i) if (!strcmp(family, kFamily[i])) fam = i;
-  if (fam < 0) return fail("unknown kernel family '%s' (gemm_fwd_lds_4x2|gemm_fwd_lds_2x2|gemm_fwd_direct|gemm_dgrad|gemm_wgrad|gemm_bwd_pair|adam|hgemm_fwd|hgemm_dgrad|hgemm_wgrad)", family);
+  std::string names;
+  for (int i = 0; i < kNumFamily; ++i) { if (!strcmp(family, kFamily[i])) fam = i; names += (i ? "|" : ""); names += kFamily[i]; }
+  if (fam < 0) return fail("unknown kernel family '%s' (%s)", family, names.c_str());
   HIPCHK(hipStreamSynchronize(h->stream));
   double total = 0; int64_t cnt = 0;
   for (auto& r : h->recs) {

@@ -674,14 +674,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     *reinterpret_cast<f32x4*>(a.dZ + x0) = dz;
   }
 }
-inline hipError_t dgrad_qtrain_launch(GemmBatch& batch, const HeadTrainArgs& a, hipStream_t stream) {
-  GemmProblem& p = batch.prob[0];
-  p.tiles_p = p.Pdim / 64; p.tiles_q = p.Qdim / 16; p.tile_base = 0;
-  batch.n = 1; batch.total_tiles = p.tiles_p * p.tiles_q;
-  LaunchTimer& lt = launch_timer();
-  if (lt.start) { hipExtLaunchKernelGGL(k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), (dgrad_lds_bytes<1, 1>()), stream, lt.start, lt.stop, 0, batch, a); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL(k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), (dgrad_lds_bytes<1, 1>()), stream, batch, a);
-  return hipGetLastError();
+inline hipError_t dgrad_qtrain_launch(GemmBatch& batch, const HeadTrainArgs& a, const LaunchOn& on) {
+  batch.n = 1;
+  return launch(on, k_dgrad_qtrain<0>, dim3(tile_batch(batch, 64, 16)), dim3(256), dgrad_lds_bytes<1, 1>(), batch, a);
 }
 
 // Fused head backward: in one pass over the tower top X4[rows][H]
@@ -960,18 +955,12 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
     else a.dZ[(size_t)(q0 + r) * a.H + k] = dz;
   }
 }
-inline hipError_t dqda_head_bwd_launch(DqdaHeadArgs& a, const QHeadRider& rider, hipStream_t stream) {
+inline hipError_t dqda_head_bwd_launch(DqdaHeadArgs& a, const QHeadRider& rider, const LaunchOn& on) {
   a.row_tiles = a.rows / 16;
   a.pr.tiles_p = 1; a.pr.tiles_q = a.row_tiles; a.pr.tile_base = 0;
-  const int grid = a.row_tiles * ((a.H + 255) / 256) + rider.blocks;
-  LaunchTimer& lt = launch_timer();
-  if (a.dZ16 != nullptr) {
-    if (lt.start) { hipExtLaunchKernelGGL(k_dqda_head_bwd<true>, dim3(grid), dim3(256), 4 * 64 * 16, stream, lt.start, lt.stop, 0, a, rider); lt.start = lt.stop = nullptr; }
-    else hipLaunchKernelGGL(k_dqda_head_bwd<true>, dim3(grid), dim3(256), 4 * 64 * 16, stream, a, rider);
-  }
-  else if (lt.start) { hipExtLaunchKernelGGL(k_dqda_head_bwd<false>, dim3(grid), dim3(256), 4 * 64 * 16, stream, lt.start, lt.stop, 0, a, rider); lt.start = lt.stop = nullptr; }
-  else hipLaunchKernelGGL(k_dqda_head_bwd<false>, dim3(grid), dim3(256), 4 * 64 * 16, stream, a, rider);
-  return hipGetLastError();
+  const dim3 grid(a.row_tiles * ((a.H + 255) / 256) + rider.blocks);
+  if (a.dZ16 != nullptr) return launch(on, k_dqda_head_bwd<true>, grid, dim3(256), kNarrowDgradLds, a, rider);
+  return launch(on, k_dqda_head_bwd<false>, grid, dim3(256), kNarrowDgradLds, a, rider);
 }
 
 // ---- head backward for large minibatches (rows >= 1024) -------------------------------------

@@ -186,18 +186,15 @@ extern "C" int dqnhip_test_gemm(int32_t mode, int32_t variant, int32_t rows, int
     return 0;
   }
   if (groups < 1 || groups > kMaxGroup || iters < 1) return 1;
-  static bool prepared = false;
-  if (!prepared) {
-    CK((gemm_prepare<GEMM_FWD, 64, 32, 2, 2>())); CK((gemm_prepare<GEMM_DGRAD, 64, 32, 2, 2>()));
-    CK((gemm_prepare<GEMM_WGRAD, 64, 64, 2, 2>()));
-    CK(direct_prepare(gemm_wgrad_direct<1, 1>, 4 * 16 * 64 * 16 + 4 * 16 * 16));
-    CK(direct_prepare(gemm_fwd_direct<4, 4>, 4 * 16 * 64 * 16));
-    CK(direct_prepare(gemm_fwd_lds<4, 2, false>, 4 * 2 * 6 * 512 * 4)); CK(direct_prepare(gemm_fwd_lds<4, 2, true>, 4 * 2 * 6 * 512 * 4));
-    CK(direct_prepare(gemm_fwd_lds<4, 4, false>, 4 * 2 * 8 * 512 * 4));
-    CK(direct_prepare((gemm_fwd_lds<4, 4, false, 1>), (fwd_lds_bytes<4, 4, false, 1>())));
-    CK(direct_prepare(gemm_dgrad_direct<1, 4>, 4 * 16 * 64 * 16));
-    prepared = true;
-  }
+  // the dynamic-LDS limits of this unit's kernel copies (the variants this harness launches)
+  CK((gemm_prepare<GEMM_FWD, 64, 32, 2, 2>())); CK((gemm_prepare<GEMM_DGRAD, 64, 32, 2, 2>()));
+  CK((gemm_prepare<GEMM_WGRAD, 64, 64, 2, 2>()));
+  CK(direct_prepare(gemm_wgrad_direct<1, 1>, kBwdTileLds));
+  CK(direct_prepare(gemm_fwd_direct<4, 4>, (fwd_direct_lds_bytes<4, 4>())));
+  CK(direct_prepare(gemm_fwd_lds<4, 2, false>, (fwd_lds_bytes<4, 2, false>()))); CK(direct_prepare(gemm_fwd_lds<4, 2, true>, (fwd_lds_bytes<4, 2, true>())));
+  CK(direct_prepare(gemm_fwd_lds<4, 4, false>, (fwd_lds_bytes<4, 4, false>())));
+  CK(direct_prepare((gemm_fwd_lds<4, 4, false, 1>), (fwd_lds_bytes<4, 4, false, 1>())));
+  CK(direct_prepare(gemm_dgrad_direct<1, 4>, (dgrad_direct_lds_bytes<1, 4>())));
   hipStream_t s; CK(hipStreamCreate(&s));
   const int M = rows, N = n_out, K = k_in;
   const size_t nX = (size_t)M * K, nW = (size_t)N * K, nY = (size_t)M * N;
@@ -346,8 +343,7 @@ __global__ void k_cmp_h(const float* ref, int M, int N, const h16* C16, int ldc1
 extern "C" int dqnhip_test_hgemm(int32_t mode, int32_t tile, int32_t M, int32_t N, int32_t K, int32_t iters,
                                  float* avg_us, float* max_abs_err, float* max_ref) {
   if (iters < 1 || M % 64 || N % 64 || K % 64) return 1;
-  static bool prepared = false;
-  if (!prepared) { CK(hgemm_prepare_all()); prepared = true; }
+  CK(hgemm_prepare_all());
   hipStream_t s; CK(hipStreamCreate(&s));
   float* dres; CK(hipMalloc(&dres, 8)); CK(hipMemsetAsync(dres, 0, 8, s));
   float hres[2] = {0, 0};
@@ -460,8 +456,7 @@ extern "C" int dqnhip_test_hgemm(int32_t mode, int32_t tile, int32_t M, int32_t 
 //   rows = minibatch B, n_out, k_in (multiples of 128).  us[3] = dgrad alone, wgrad alone, pair.
 extern "C" int dqnhip_test_hgemm_backward(int32_t rows, int32_t n_out, int32_t k_in, int32_t iters, float* us, float* max_abs_err, float* max_ref) {
   if (iters < 1 || rows % 128 || n_out % 128 || k_in % 128) return 1;
-  static bool prepared = false;
-  if (!prepared) { CK(hgemm_prepare_all()); prepared = true; }
+  CK(hgemm_prepare_all());
   hipStream_t s; CK(hipStreamCreate(&s));
   h16 *dY, *W, *X, *mask, *dX16; float *dX32, *dW32, *refd, *refw, *dres;
   CK(hipMalloc(&dY, (size_t)rows * n_out * 2)); CK(hipMalloc(&W, (size_t)n_out * k_in * 2)); CK(hipMalloc(&X, (size_t)rows * k_in * 2));

@@ -154,18 +154,6 @@ struct DeviceBufs {
 
 #define CKF(e) do { hipError_t e__ = (e); if (e__ != hipSuccess) { fprintf(stderr, "dqnhip_test_gemm_form: %s -> %s\n", #e, hipGetErrorString(e__)); return 2; } } while (0)
 
-// dynamic LDS above the 64 KiB default, for THIS unit's copies of the kernels: what prepare_kernels (learner.hip) opts in
-hipError_t prepare_forms() {
-  hipError_t e;
-  if ((e = direct_prepare(gemm_bwd_seq<true>, 4 * 16 * 64 * 16 + 4 * 16 * 16)) != hipSuccess) return e;
-  if ((e = direct_prepare(gemm_bwd_seq<false>, 4 * 16 * 64 * 16 + 4 * 16 * 16)) != hipSuccess) return e;
-  if ((e = direct_prepare(gemm_wgrad_tail<1>, 80 * 1024)) != hipSuccess) return e;
-  if ((e = direct_prepare(gemm_wgrad_tail<kNO>, 80 * 1024)) != hipSuccess) return e;
-  if ((e = direct_prepare((gemm_bwd_pair_direct<1, true>), 4 * 16 * 64 * 16 + 4 * 16 * 16)) != hipSuccess) return e;
-  if ((e = direct_prepare((gemm_bwd_pair_direct<1, false>), 4 * 16 * 64 * 16 + 4 * 16 * 16)) != hipSuccess) return e;
-  return direct_prepare(gemm_fwd_lds<4, 2, true>, 4 * 2 * 6 * 512 * 4);
-}
-
 hipError_t launch_form(int form, GemmBatch& b, hipStream_t s) {
   const HeadWgradRider no_rider{};     // blocks = 0: no head rider, and no tails block
   switch (form) {
@@ -193,8 +181,7 @@ hipError_t launch_form(int form, GemmBatch& b, hipStream_t s) {
 
 extern "C" int dqnhip_test_gemm_form(int32_t form, int32_t n_problems, const dqnhip_test_problem* probs) {
   if (!validate(form, n_problems, probs)) return 1;
-  static bool prepared = false;
-  if (!prepared) { CKF(prepare_forms()); prepared = true; }
+  CKF(direct_prepare_all());     // the dynamic-LDS limits of THIS unit's copies of the kernels: the list the learner's prepare_kernels sets
   DeviceBufs bufs;
   GemmBatch b{}; b.n = n_problems;
   hipError_t err = hipSuccess;
