@@ -57,6 +57,41 @@ struct GemmBatch {
   int total_tiles;
 };
 
+// ---- what the fp32 GEMM kernels receive ----------------------------------------------------------------------------------------
+// GemmBatch stays the host-side description; its launcher packs it (pack_args, gemm_direct.hip.h) into a GemmArgs laid out by when
+// a wave needs each field.  A wave's first operand load used to wait for five dependent scalar loads of the 640-byte GemmBatch
+// (tile_base, then tiles_p / tiles_q of prob[pi], ... then P / Q of prob[pi]); with this layout everything the first load needs is
+// requested at constant kernarg offsets in ONE round: the header (first 64 bytes) and the hot record of every problem, selected
+// with scalar selects.  The cold record (epilogue fields) is indexed by pi, so its request goes out after that round and nothing
+// waits for it before the operand loads are in flight.
+struct alignas(64) GemmHeader {
+  int tile_base[kMaxGroup];    // entries >= n: INT_MAX (so the problem search needs no `n`)
+  int tiles_p[kMaxGroup], tiles_q[kMaxGroup];
+  int n, total_tiles, pad[2];
+};
+struct alignas(64) GemmHot {   // one 64-byte line; what every body's first loads need comes first, in whole 16-byte pieces
+  const float* P; const float* Q;
+  int ldp, ldq, Kred, ldc;
+  float* C;
+  int mode;                    // (mixed-mode launches choose their body by it)
+  int Pdim, Qdim;
+  int pad[3];
+};
+struct GemmCold {
+  const float* bias; const float* mask; float* db; float* partial;
+  const float* seed_w; float* C2; const float* dot_w; float* dot_out; float* xcopy_dst;
+  int ldm, relu, xcopy_col, xcopy_n;
+};
+// N: the records the kernel carries (kMaxGroup for the grouped kernels; the kernels with a fixed number of problems carry — and
+// index — exactly theirs)
+template <int N>
+struct GemmArgs {
+  GemmHeader head;
+  GemmHot hot[N];
+  GemmCold cold[N];
+};
+static_assert(sizeof(GemmHeader) == 64 && sizeof(GemmHot) == 64, "one 16-dword scalar load each");
+
 // Where ONE kernel launch goes: a stream and, in the learner's timing mode, the event pair that brackets it.  Every launcher takes a
 // LaunchOn where it would take a stream (a bare hipStream_t converts: untimed) and hands it to exactly one launch().
 struct LaunchOn {
@@ -109,7 +144,7 @@ constexpr int kFlagGradNorm = 2;   // a gradient L2 norm was not finite: that cl
 struct TailsArgs {
   const float* loss_partial; int n_loss; const double* q_partial; int n_q;
   float inv_batch; float* critic_tail; float* actor_tail; const int* flags;
-  int on;                          // rider form: 1 = the launch's last block runs tails_block
+  int on;                          // rider form: not 0 = the launch's last block runs tails_block (gemm_wgrad_tail: that block's index + 1)
 };
 __device__ __forceinline__ void tails_block(const TailsArgs& a, float* sdot /*[4]*/, double* sq /*[4]*/) {
   const int t = threadIdx.x;

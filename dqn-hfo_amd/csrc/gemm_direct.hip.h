@@ -28,6 +28,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 
 #include "gemm_common.hip.h"
@@ -36,15 +38,18 @@ namespace dqnhip {
 
 // ---- shared pieces ----------------------------------------------------------------
 
+__host__ __device__ __forceinline__ void tile_of_counts(int tiles_p, int tiles_q, int b, int& tile_p, int& tile_q) {
+  // tiles_p % 8 == 0: same P panel (weight slice) -> same XCD L2 (b % 8): xcd = b & 7, j = b >> 3, tile (8 (j / tiles_q) + xcd,
+  // j % tiles_q); else tile (b / tiles_q, b % tiles_q).  One division for both, no branch: the prologue stays one basic block,
+  // so that the scalar loads in front of it are issued together.
+  const bool xmap = (tiles_p & 7) == 0;
+  const int j = xmap ? b >> 3 : b;
+  const int d = j / tiles_q;
+  tile_q = j - d * tiles_q;
+  tile_p = xmap ? d * 8 + (b & 7) : d;
+}
 __device__ __forceinline__ void tile_of_problem(const GemmProblem& pr, int b, int& tile_p, int& tile_q) {
-  if ((pr.tiles_p & 7) == 0) {       // same P panel (weight slice) -> same XCD L2 (b % 8)
-    const int xcd = b & 7, j = b >> 3;
-    tile_q = j % pr.tiles_q;
-    tile_p = (j / pr.tiles_q) * 8 + xcd;
-  } else {
-    tile_q = b % pr.tiles_q;
-    tile_p = b / pr.tiles_q;
-  }
+  tile_of_counts(pr.tiles_p, pr.tiles_q, b, tile_p, tile_q);
 }
 __device__ __forceinline__ void tile_of_block(const GemmBatch& batch, int& pi, int& tile_p, int& tile_q) {
   int b = blockIdx.x;
@@ -54,6 +59,83 @@ __device__ __forceinline__ void tile_of_block(const GemmBatch& batch, int& pi, i
     if (i < batch.n && b >= batch.prob[i].tile_base) pi = i;
   const GemmProblem& pr = batch.prob[pi];
   tile_of_problem(pr, b - pr.tile_base, tile_p, tile_q);
+}
+
+// ---- the packed form (GemmArgs, gemm_common.hip.h) ----
+// f(0) .. f(N - 1) are read at constant kernarg offsets — one round of scalar loads, whatever pi turns out to be — and the
+// (workgroup-uniform) pi chooses among the values with scalar selects.
+template <int N, typename F>
+__device__ __forceinline__ auto pick(int pi, F f) -> decltype(f(0)) {
+  const auto v0 = f(0);
+  if constexpr (N == 1) return v0;
+  else {
+    const auto v1 = f(1), v2 = f(N > 2 ? 2 : 0), v3 = f(N > 3 ? 3 : 0);
+    auto v = v0;
+    v = (pi == 1) ? v1 : v;
+    if constexpr (N > 2) v = (pi == 2) ? v2 : v;
+    if constexpr (N > 3) v = (pi == 3) ? v3 : v;
+    return v;
+  }
+}
+// The GemmProblem a body takes, assembled in registers.  `cold` may be indexed by pi: its loads are the epilogue's.
+__device__ __forceinline__ GemmProblem make_problem(const float* P, const float* Q, float* C, int ldp, int ldq, int ldc, int Pdim, int Qdim, int Kred,
+                                                    int mode, const GemmCold& c, int tiles_p, int tiles_q, int tile_base) {
+  GemmProblem pr;
+  pr.P = P; pr.ldp = ldp; pr.Q = Q; pr.ldq = ldq; pr.C = C; pr.ldc = ldc; pr.Pdim = Pdim; pr.Qdim = Qdim; pr.Kred = Kred;
+  pr.bias = c.bias; pr.mask = c.mask; pr.ldm = c.ldm; pr.db = c.db; pr.partial = c.partial; pr.relu = c.relu;
+  pr.seed_w = c.seed_w; pr.C2 = c.C2; pr.dot_w = c.dot_w; pr.dot_out = c.dot_out;
+  pr.xcopy_dst = c.xcopy_dst; pr.xcopy_col = c.xcopy_col; pr.xcopy_n = c.xcopy_n;
+  pr.mode = mode; pr.tiles_p = tiles_p; pr.tiles_q = tiles_q; pr.tile_base = tile_base;
+  return pr;
+}
+// One wait for a launch's scalar arguments.  The (empty) statement reads one value of every 16-byte piece of the header and of the
+// hot records (and up to two values of a rider struct, x0 / x1) and hands back the block index, from which everything else is
+// computed: the compiler has to request all of them before it and cannot compute anything behind its back in between — left alone
+// it requests the header, waits, does the tile arithmetic, requests the records, waits again.
+template <int N>
+struct HotArgs { GemmHeader hd; GemmHot hot[N]; };
+template <int N>
+__device__ __forceinline__ int request_args(const GemmArgs<N>& a, HotArgs<N>& r, int b, int x0 = 0, int x1 = 0) {
+  r.hd = a.head;
+#pragma unroll
+  for (int i = 0; i < N; ++i) r.hot[i] = a.hot[i];
+  const GemmHot &h0 = r.hot[0], &h1 = r.hot[N > 1 ? 1 : 0], &h2 = r.hot[N > 2 ? 2 : 0], &h3 = r.hot[N > 3 ? 3 : 0];
+  asm volatile("" : "+s"(b) : "s"(r.hd.tile_base[1]), "s"(r.hd.tiles_p[0]), "s"(r.hd.tiles_q[0]), "s"(x0), "s"(x1),
+               "s"(h0.P), "s"(h0.ldp), "s"(h0.C), "s"(h1.P), "s"(h1.ldp), "s"(h1.C), "s"(h2.P), "s"(h2.ldp), "s"(h2.C), "s"(h3.P), "s"(h3.ldp), "s"(h3.C));
+  return b;
+}
+// problem I of a kernel whose problems are a compile-time fact (gemm_bwd_seq, gemm_wgrad_tail, k_dgrad_qtrain): no select at all
+template <int I, int N>
+__device__ __forceinline__ GemmProblem problem_at(const GemmArgs<N>& a, const HotArgs<N>& r) {
+  static_assert(I < N, "record not carried");
+  const GemmHot& h = r.hot[I];
+  return make_problem(h.P, h.Q, h.C, h.ldp, h.ldq, h.ldc, h.Pdim, h.Qdim, h.Kred, h.mode, a.cold[I], r.hd.tiles_p[I], r.hd.tiles_q[I], r.hd.tile_base[I]);
+}
+// GEMM tile b (request_args' return value) of a grouped launch: its problem and tile coordinates from the header alone, the hot
+// fields by select
+template <int N>
+__device__ __forceinline__ GemmProblem problem_of_tile(const GemmArgs<N>& a, const HotArgs<N>& r, const int b, int& tile_p, int& tile_q) {
+  const GemmHeader& hd = r.hd;
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < N; ++i)
+    if (b >= hd.tile_base[i]) pi = i;
+  const int tiles_p = pick<N>(pi, [&](int i) { return hd.tiles_p[i]; });
+  const int tiles_q = pick<N>(pi, [&](int i) { return hd.tiles_q[i]; });
+  const int tile_base = pick<N>(pi, [&](int i) { return hd.tile_base[i]; });
+  tile_of_counts(tiles_p, tiles_q, b - tile_base, tile_p, tile_q);
+  return make_problem(pick<N>(pi, [&](int i) { return r.hot[i].P; }), pick<N>(pi, [&](int i) { return r.hot[i].Q; }),
+                      pick<N>(pi, [&](int i) { return r.hot[i].C; }), pick<N>(pi, [&](int i) { return r.hot[i].ldp; }),
+                      pick<N>(pi, [&](int i) { return r.hot[i].ldq; }), pick<N>(pi, [&](int i) { return r.hot[i].ldc; }),
+                      pick<N>(pi, [&](int i) { return r.hot[i].Pdim; }), pick<N>(pi, [&](int i) { return r.hot[i].Qdim; }),
+                      pick<N>(pi, [&](int i) { return r.hot[i].Kred; }), pick<N>(pi, [&](int i) { return r.hot[i].mode; }),
+                      a.cold[N == 1 ? 0 : pi], tiles_p, tiles_q, tile_base);
+}
+template <int N>
+__device__ __forceinline__ GemmProblem problem_of_block(const GemmArgs<N>& a, int& tile_p, int& tile_q) {
+  HotArgs<N> r;
+  const int b = request_args(a, r, (int)blockIdx.x);
+  return problem_of_tile(a, r, b, tile_p, tile_q);
 }
 
 // Each wave parks its NACC accumulators in LDS (lane-linear: conflict free), then wave w
@@ -855,16 +937,7 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) roff[kb] = li * 32 + ((((kb << 2) + lg) ^ (li & 7)) << 2);
 
-  // this lane's pieces of the ReLU' mask (one per (a,b): the r this wave owns in the epilogue),
-  // requested before the reduction loop so that their latency is not exposed after it
   f32x4 mk[TQ * TPB];
-  if (pr.mask != nullptr) {
-#pragma unroll
-    for (int ab = 0; ab < TQ * TPB; ++ab) {
-      const int r = (wave - ab) & 3;
-      mk[ab] = *reinterpret_cast<const f32x4*>(pr.mask + (size_t)(q0 + (ab / TPB) * 16 + li) * pr.ldm + p0 + (ab % TPB) * 64 + (lg << 4) + (r << 2));
-    }
-  }
   f32x4 acc[NACC];
 #pragma unroll
   for (int e = 0; e < NACC; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -916,6 +989,17 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
     DQN_PIN(); }
 
   D_GLOADQ(G0, 0) D_PIN() D_GLOADQ(G1, 1) D_PIN() D_GLOADP(P0, 0) D_PIN()
+  // this lane's pieces of the ReLU' mask (one per (a,b): the r this wave owns in the epilogue), requested ahead of the main loop so
+  // that their latency is not exposed after it — and behind the first operand requests: pr.mask / pr.ldm are cold launch arguments,
+  // a scalar round trip of their own that the operand loads above do not wait for
+  if (pr.mask != nullptr) {
+#pragma unroll
+    for (int ab = 0; ab < TQ * TPB; ++ab) {
+      const int r = (wave - ab) & 3;
+      mk[ab] = *reinterpret_cast<const f32x4*>(pr.mask + (size_t)(q0 + (ab / TPB) * 16 + li) * pr.ldm + p0 + (ab % TPB) * 64 + (lg << 4) + (r << 2));
+    }
+  }
+  D_PIN()
   hook.after_prologue(); D_PIN()      // (with the first, cold round of operand requests: later, its cold misses hold up the in-order vmcnt of the loop's loads)
   D_SWRITE(0, G0) D_PIN() D_GLOADQ(G0, 2) D_PIN() D_SREAD(F, 0) D_PIN() D_GLOADP(P1, 1) D_PIN()
   int t = 0;
@@ -975,25 +1059,25 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
 
 // ---- kernels: thin wrappers over the bodies --------------------------------------------
 template <int TP, int TQ>
-__global__ __launch_bounds__(256) void gemm_fwd_direct(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_fwd_direct(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  fwd_direct_body<TP, TQ>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  fwd_direct_body<TP, TQ>(pr, tile_p, tile_q, smem);
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
-__global__ __launch_bounds__(256) void gemm_fwd_lds(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_fwd_lds(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  fwd_lds_body<TP, TQ, PIN, NSLOT>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  fwd_lds_body<TP, TQ, PIN, NSLOT>(pr, tile_p, tile_q, smem);
 }
 template <int TPB, int TQ>
-__global__ __launch_bounds__(256) void gemm_dgrad_direct(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_dgrad_direct(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  dgrad_direct_body<TPB, TQ>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  dgrad_direct_body<TPB, TQ>(pr, tile_p, tile_q, smem);
 }
 template <int TPB, int TQ, bool SCH = true>
 __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p, int tile_q, float* smem) {
@@ -1001,25 +1085,25 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
   dgrad_lds_body<TPB, TQ, SCH, DgradNoHook>(pr, tile_p, tile_q, smem, nullptr, none);
 }
 template <int TPB, int TQ>
-__global__ __launch_bounds__(256) void gemm_dgrad_lds(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_dgrad_lds(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  dgrad_lds_body<TPB, TQ>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  dgrad_lds_body<TPB, TQ>(pr, tile_p, tile_q, smem);
 }
 template <int TPB, int TQB>
-__global__ __launch_bounds__(256) void gemm_wgrad_direct(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_wgrad_direct(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  wgrad_direct_body<TPB, TQB>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  wgrad_direct_body<TPB, TQB>(pr, tile_p, tile_q, smem);
 }
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void gemm_dgrad_narrow(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_dgrad_narrow(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  dgrad_narrow_body(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  dgrad_narrow_body(pr, tile_p, tile_q, smem);
 }
 // q(s, mu(s)) = q_values(critic tower top) and its avg-Q partials (src/dqn.cpp:913-916) as RIDER blocks of the narrow dgrad
 // launch: a handful of 16 x 16 tiles (16 workgroups at 256 rows) that leaves most of the chip idle.  Nothing on the
@@ -1053,29 +1137,30 @@ __device__ __forceinline__ void q_head_rider(const QHeadRider& r, const int blk)
   if (lane == 0) { const float v = acc + r.bias[0]; r.q_out[row] = v; r.qsum_partial[row] = (double)v; }
 }
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void gemm_dgrad_narrow_qrider(const GemmBatch batch, const QHeadRider rider) {
+__global__ __launch_bounds__(256) void gemm_dgrad_narrow_qrider(const GemmArgs<kMaxGroup> args, const QHeadRider rider) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if ((int)blockIdx.x >= batch.total_tiles) { q_head_rider(rider, (int)blockIdx.x - batch.total_tiles); return; }
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  dgrad_narrow_body(batch.prob[pi], tile_p, tile_q, smem);
+  HotArgs<kMaxGroup> r;
+  const int b = request_args(args, r, (int)blockIdx.x, args.head.total_tiles);
+  if (b >= r.hd.total_tiles) { q_head_rider(rider, b - r.hd.total_tiles); return; }
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_tile(args, r, b, tile_p, tile_q);
+  dgrad_narrow_body(pr, tile_p, tile_q, smem);
 }
 template <int TPB>
-__global__ __launch_bounds__(256) void gemm_wgrad_narrow(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_wgrad_narrow(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  wgrad_narrow_body<TPB>(batch.prob[pi], tile_p, tile_q, smem);
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  wgrad_narrow_body<TPB>(pr, tile_p, tile_q, smem);
 }
 // One layer's backward in ONE launch: problems with mode GEMM_DGRAD (64x16 tiles) and
 // GEMM_WGRAD (64x64 tiles) side by side.  dX_{l-1} = dZ_l W_l and dW_l = dZ_l^T X_{l-1} only
 // share their input dZ_l, so a 256x1024x1024 layer offers 256 + 256 workgroups = 2 per CU.
 template <int TQD = 1, bool DLDS = false>
-__global__ __launch_bounds__(256) void gemm_bwd_pair_direct(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_bwd_pair_direct(const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  const GemmProblem& pr = batch.prob[pi];
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
   if (pr.mode == GEMM_WGRAD) wgrad_direct_body<1, 1>(pr, tile_p, tile_q, smem);
   else if constexpr (DLDS) dgrad_lds_body<1, TQD, false>(pr, tile_p, tile_q, smem);   // (scheduled form measured 0.5 us slower beside the co-resident wgrad wave)
   else dgrad_direct_body<1, TQD>(pr, tile_p, tile_q, smem);
@@ -1086,19 +1171,21 @@ __global__ __launch_bounds__(256) void gemm_bwd_pair_direct(const GemmBatch batc
 // per CU measured ~ the SUM of their stand-alone times (the pair kernel above: 15.5 us for 2 x 4.2 us
 // of MFMA); one workgroup doing both pays the per-launch fixed cost once and keeps one wave per SIMD.
 template <bool DLDS>
-__device__ __forceinline__ void bwd_seq_block(const GemmBatch& batch, const int b, float* smem) {
+__device__ __forceinline__ void bwd_seq_block(const GemmArgs<2>& args, const int block, float* smem) {
   int tile_p, tile_q;
+  HotArgs<2> r;
+  const int b = request_args(args, r, block);
   // wgrad first (measured 14.9 us; dgrad first 15.3, also with the wgrad ring pre-issued under the
   // dgrad epilogue; round 5: wgrad first with the dgrad tile's first operand requests issued BEFORE the wgrad tile parks /
   // reduces / stores — 15.0-15.1 against 14.7 us; the same requests issued before the WHOLE wgrad tile — 14.9: three cold loads
   // in flight do not pay for the registers and wait counts they hold through the other tile)
-  const GemmProblem& pw = batch.prob[1];
+  const GemmProblem pw = problem_at<1>(args, r);
   if (b < pw.tiles_p * pw.tiles_q) {
     tile_of_problem(pw, b, tile_p, tile_q);
     wgrad_direct_body<1, 1>(pw, tile_p, tile_q, smem);
   }
   __syncthreads();
-  const GemmProblem& pd = batch.prob[0];
+  const GemmProblem pd = problem_at<0>(args, r);
   if (b < pd.tiles_p * pd.tiles_q) {
     tile_of_problem(pd, b, tile_p, tile_q);
     if constexpr (DLDS) dgrad_lds_body<1, 1, true>(pd, tile_p, tile_q, smem);
@@ -1106,9 +1193,9 @@ __device__ __forceinline__ void bwd_seq_block(const GemmBatch& batch, const int 
   }
 }
 template <bool DLDS>
-__global__ __launch_bounds__(256) void gemm_bwd_seq(const GemmBatch batch) {
+__global__ __launch_bounds__(256) void gemm_bwd_seq(const GemmArgs<2> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  bwd_seq_block<DLDS>(batch, (int)blockIdx.x, smem);
+  bwd_seq_block<DLDS>(args, (int)blockIdx.x, smem);
 }
 
 // The head layer's weight / bias gradients (dWh[j][k] = sum_m dYh[m][j] X4[m][k], dbh[j] = sum_m dYh[m][j]) as RIDER blocks of a
@@ -1180,16 +1267,14 @@ __device__ __forceinline__ void head_wgrad_rider(const HeadWgradRider& r, const 
 // The carrier is the FIRST tower layer's narrow wgrad launch (the last launch before the optimiser pass): 64-128 tiles, so the rider
 // blocks land on CUs of their own instead of beside a GEMM wave (as riders of the top layer's gemm_bwd_seq: +0.9 us on that launch)
 template <int NH>
-__global__ __launch_bounds__(256) void gemm_wgrad_narrow_rider(const GemmBatch batch, const HeadWgradRider rider) {
+__global__ __launch_bounds__(256) void gemm_wgrad_narrow_rider(const GemmArgs<kMaxGroup> args, const HeadWgradRider rider) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if ((int)blockIdx.x < rider.blocks) { head_wgrad_rider<NH>(rider, (int)blockIdx.x, smem); return; }
-  int pi, tile_p, tile_q;
-  const int blk = (int)blockIdx.x - rider.blocks;
-  pi = 0;
-#pragma unroll
-  for (int i = 1; i < kMaxGroup; ++i) if (i < batch.n && blk >= batch.prob[i].tile_base) pi = i;
-  tile_of_problem(batch.prob[pi], blk - batch.prob[pi].tile_base, tile_p, tile_q);
-  wgrad_narrow_body<1>(batch.prob[pi], tile_p, tile_q, smem);
+  HotArgs<kMaxGroup> r;
+  const int b = request_args(args, r, (int)blockIdx.x, rider.blocks);
+  if (b < rider.blocks) { head_wgrad_rider<NH>(rider, b, smem); return; }
+  int tile_p, tile_q;
+  const GemmProblem pr = problem_of_tile(args, r, b - rider.blocks, tile_p, tile_q);
+  wgrad_narrow_body<1>(pr, tile_p, tile_q, smem);
 }
 
 // The LAST launch of a net's backward under the shifted schedule (learner.hip tower_backward): layer 1's wgrad (prob[0]:
@@ -1197,18 +1282,18 @@ __global__ __launch_bounds__(256) void gemm_wgrad_narrow_rider(const GemmBatch b
 // first layer's wgrad alone is 64-128 short workgroups — a 6-us launch of launch floor; beside a full wgrad it costs ~1.
 // Long workgroups first in the grid.
 template <int NH>
-__global__ __launch_bounds__(256) void gemm_wgrad_tail(const GemmBatch batch, const HeadWgradRider rider, const TailsArgs tails) {
+__global__ __launch_bounds__(256) void gemm_wgrad_tail(const GemmArgs<2> args, const HeadWgradRider rider, const TailsArgs tails) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int blk = (int)blockIdx.x;
+  HotArgs<2> r;
+  int blk = request_args(args, r, (int)blockIdx.x, tails.on, rider.blocks);
   int tile_p, tile_q;
-  if (tails.on && blk == (int)gridDim.x - 1) { tails_block(tails, smem, reinterpret_cast<double*>(smem + 8)); return; }   // data-parallel learners: one more block, last in the grid
+  if (tails.on && blk == tails.on - 1) { tails_block(tails, smem, reinterpret_cast<double*>(smem + 8)); return; }   // data-parallel learners: one more block, last in the grid
   if (blk < rider.blocks) { head_wgrad_rider<NH>(rider, blk, smem); return; }
   blk -= rider.blocks;
-  const GemmProblem& p0 = batch.prob[1];
-  const int n0 = p0.tiles_p * p0.tiles_q;
-  if (blk < n0) { tile_of_problem(p0, blk, tile_p, tile_q); wgrad_narrow_body<1>(p0, tile_p, tile_q, smem); return; }
+  const int n0 = r.hd.tiles_p[1] * r.hd.tiles_q[1];
+  if (blk < n0) { const GemmProblem p0 = problem_at<1>(args, r); tile_of_problem(p0, blk, tile_p, tile_q); wgrad_narrow_body<1>(p0, tile_p, tile_q, smem); return; }
   blk -= n0;
-  const GemmProblem& p1 = batch.prob[0];
+  const GemmProblem p1 = problem_at<0>(args, r);
   tile_of_problem(p1, blk, tile_p, tile_q); wgrad_direct_body<1, 1>(p1, tile_p, tile_q, smem);
 }
 
@@ -1235,12 +1320,51 @@ template <typename K>
 inline hipError_t direct_launch(K kernel, GemmBatch& batch, int BP, int BQ, int lds_bytes, const LaunchOn& on) {
   return launch(on, kernel, dim3(tile_batch(batch, BP, BQ)), dim3(256), lds_bytes, batch);
 }
+// What the product's kernels receive: the GemmArgs of a batch whose tile accounting is filled (gemm_common.hip.h).  false: the
+// accounting does not hold together — the kernel carries no record for a problem, a problem has no tiles, or the tile_base values
+// are not the running sum of the tile counts, so that a workgroup would be handed a tile of a problem it does not belong to, i.e. an
+// operand pointer out of range.  (Inside a problem tile_of_counts is a bijection onto its tiles: tests/cpp/packed_args_host.cpp.)
+// grouped: the problems' tiles follow each other in the grid (tile_base = running sum); else each problem's tiles count from 0.
+template <int N>
+inline bool pack_args(const GemmBatch& b, GemmArgs<N>& a, bool grouped = true) {
+  a = GemmArgs<N>{};
+  if (b.n < 1 || b.n > N) return false;
+  a.head.n = b.n; a.head.total_tiles = b.total_tiles;
+  int base = 0;
+  for (int i = 0; i < kMaxGroup; ++i) {
+    a.head.tile_base[i] = INT32_MAX; a.head.tiles_p[i] = 1; a.head.tiles_q[i] = 1;
+    if (i >= b.n) continue;
+    const GemmProblem& p = b.prob[i];
+    if (p.tiles_p < 1 || p.tiles_q < 1 || p.tile_base != (grouped ? base : 0)) return false;
+    const int count = p.tiles_p * p.tiles_q;
+    base += count;
+    a.head.tile_base[i] = p.tile_base; a.head.tiles_p[i] = p.tiles_p; a.head.tiles_q[i] = p.tiles_q;
+    GemmHot& h = a.hot[i];
+    h.P = p.P; h.Q = p.Q; h.C = p.C; h.ldp = p.ldp; h.ldq = p.ldq; h.ldc = p.ldc; h.Pdim = p.Pdim; h.Qdim = p.Qdim; h.Kred = p.Kred; h.mode = p.mode;
+    GemmCold& c = a.cold[i];
+    c.bias = p.bias; c.mask = p.mask; c.db = p.db; c.partial = p.partial; c.seed_w = p.seed_w; c.C2 = p.C2; c.dot_w = p.dot_w; c.dot_out = p.dot_out;
+    c.xcopy_dst = p.xcopy_dst; c.ldm = p.ldm; c.relu = p.relu; c.xcopy_col = p.xcopy_col; c.xcopy_n = p.xcopy_n;
+  }
+  return true;
+}
+// a grouped launch of `tiles` GEMM tiles and `extra` rider blocks; R: the rider structs the kernel takes after its GemmArgs
+template <typename K, typename... R>
+inline hipError_t packed_launch(K kernel, const GemmBatch& batch, int extra, int lds_bytes, const LaunchOn& on, const R&... riders) {
+  GemmArgs<kMaxGroup> args;
+  if (!pack_args(batch, args)) return hipErrorInvalidValue;
+  return launch(on, kernel, dim3(batch.total_tiles + extra), dim3(256), lds_bytes, args, riders...);
+}
+template <typename K>
+inline hipError_t packed_launch(K kernel, GemmBatch& batch, int BP, int BQ, int lds_bytes, const LaunchOn& on) {
+  tile_batch(batch, BP, BQ);
+  return packed_launch(kernel, batch, 0, lds_bytes, on);
+}
 
 template <int TP, int TQ>
 constexpr int fwd_direct_lds_bytes() { return 4 * TP * TQ * 64 * 16; }
 template <int TP, int TQ>
 inline hipError_t fwd_direct_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_fwd_direct<TP, TQ>, b, 16 * TP, 16 * TQ, fwd_direct_lds_bytes<TP, TQ>(), on);
+  return packed_launch(gemm_fwd_direct<TP, TQ>, b, 16 * TP, 16 * TQ, fwd_direct_lds_bytes<TP, TQ>(), on);
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
 constexpr int fwd_lds_bytes() {
@@ -1248,23 +1372,23 @@ constexpr int fwd_lds_bytes() {
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
 inline hipError_t fwd_lds_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), on);
+  return packed_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), on);
 }
 template <int TPB, int TQ>
 constexpr int dgrad_direct_lds_bytes() { return 4 * TPB * 4 * TQ * 64 * 16; }
 template <int TPB, int TQ>
 inline hipError_t dgrad_direct_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_dgrad_direct<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_direct_lds_bytes<TPB, TQ>(), on);
+  return packed_launch(gemm_dgrad_direct<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_direct_lds_bytes<TPB, TQ>(), on);
 }
 template <int TPB, int TQ>
 constexpr int dgrad_lds_bytes() { return 4 * ((2 * TQ * 512 > TPB * 4 * TQ * 256) ? 2 * TQ * 512 : TPB * 4 * TQ * 256) * 4; }
 template <int TPB, int TQ>
 inline hipError_t dgrad_lds_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), on);
+  return packed_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), on);
 }
 template <int TPB, int TQB>
 inline hipError_t wgrad_direct_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_wgrad_direct<TPB, TQB>, b, 64 * TPB, 64 * TQB,
+  return packed_launch(gemm_wgrad_direct<TPB, TQB>, b, 64 * TPB, 64 * TQB,
                        4 * TPB * 4 * TQB * 4 * 64 * 16 + 4 * TQB * 16 * 16, on);
 }
 // mixed dgrad(64x16)/wgrad(64x64) launch; every problem carries its own mode
@@ -1279,20 +1403,21 @@ inline hipError_t bwd_pair_direct_launch(GemmBatch& batch, const LaunchOn& on) {
     base += p.tiles_p * p.tiles_q;
   }
   batch.total_tiles = base;
-  return launch(on, gemm_bwd_pair_direct<TQD, DLDS>, dim3(base), dim3(256), kBwdTileLds, batch);
+  return packed_launch(gemm_bwd_pair_direct<TQD, DLDS>, batch, 0, kBwdTileLds, on);
 }
 constexpr int kNarrowDgradLds = 4 * 64 * 16;
 inline hipError_t dgrad_narrow_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_dgrad_narrow<0>, b, 16, 16, kNarrowDgradLds, on);
+  return packed_launch(gemm_dgrad_narrow<0>, b, 16, 16, kNarrowDgradLds, on);
 }
 inline hipError_t dgrad_narrow_qrider_launch(GemmBatch& batch, const QHeadRider& rider, const LaunchOn& on) {
-  return launch(on, gemm_dgrad_narrow_qrider<0>, dim3(tile_batch(batch, 16, 16) + rider.blocks), dim3(256), kNarrowDgradLds, batch, rider);
+  tile_batch(batch, 16, 16);
+  return packed_launch(gemm_dgrad_narrow_qrider<0>, batch, rider.blocks, kNarrowDgradLds, on, rider);
 }
 template <int TPB>
 constexpr int wgrad_narrow_lds_bytes() { return 4 * TPB * 4 * 64 * 16 + 4 * 16 * 4; }
 template <int TPB>
 inline hipError_t wgrad_narrow_launch(GemmBatch& b, const LaunchOn& on) {
-  return direct_launch(gemm_wgrad_narrow<TPB>, b, 64 * TPB, 16, wgrad_narrow_lds_bytes<TPB>(), on);
+  return packed_launch(gemm_wgrad_narrow<TPB>, b, 64 * TPB, 16, wgrad_narrow_lds_bytes<TPB>(), on);
 }
 // what the head's dW / db rider blocks need
 template <int NH>
@@ -1301,7 +1426,8 @@ template <int NH>
 inline hipError_t wgrad_narrow_rider_launch(GemmBatch& batch, const HeadWgradRider& rider, const LaunchOn& on) {
   const size_t lds = std::max(head_rider_lds_bytes<NH>(rider), (size_t)wgrad_narrow_lds_bytes<1>());
   if (lds > 64 * 1024) return hipErrorInvalidValue;
-  return launch(on, gemm_wgrad_narrow_rider<NH>, dim3(tile_batch(batch, 64, 16) + rider.blocks), dim3(256), lds, batch, rider);
+  tile_batch(batch, 64, 16);
+  return packed_launch(gemm_wgrad_narrow_rider<NH>, batch, rider.blocks, (int)lds, on, rider);
 }
 // prob[0]: wgrad on 64 x 64 tiles, prob[1]: narrow wgrad on 64 x 16 tiles; rider.blocks may be 0
 template <int NH>
@@ -1312,9 +1438,12 @@ inline hipError_t wgrad_tail_launch(GemmBatch& batch, const HeadWgradRider& ride
   w0.tiles_p = w0.Pdim / 64; w0.tiles_q = w0.Qdim / 16; w0.tile_base = w1.tiles_p * w1.tiles_q;
   const int grid = w0.tile_base + w0.tiles_p * w0.tiles_q + rider.blocks + (tails.on ? 1 : 0);
   batch.total_tiles = grid;
+  if (tails.on) tails.on = grid;         // (the tails block's index + 1: the kernel needs no gridDim, which is a scalar load of its own)
   const size_t lds = std::max(rider.blocks ? head_rider_lds_bytes<NH>(rider) : (size_t)0, (size_t)kBwdTileLds);
   if (lds > (size_t)kWgradTailLdsMax) return hipErrorInvalidValue;
-  return launch(on, gemm_wgrad_tail<NH>, dim3(grid), dim3(256), lds, batch, rider, tails);
+  GemmArgs<2> args;
+  if (batch.n != 2 || !pack_args(batch, args)) return hipErrorInvalidValue;
+  return launch(on, gemm_wgrad_tail<NH>, dim3(grid), dim3(256), lds, args, rider, tails);
 }
 template <bool DLDS>
 inline hipError_t bwd_seq_launch(GemmBatch& batch, const LaunchOn& on) {
@@ -1325,7 +1454,9 @@ inline hipError_t bwd_seq_launch(GemmBatch& batch, const LaunchOn& on) {
   const int nd = d.tiles_p * d.tiles_q, nw = w.tiles_p * w.tiles_q;
   const int grid = nd > nw ? nd : nw;
   batch.total_tiles = grid;
-  return launch(on, gemm_bwd_seq<DLDS>, dim3(grid), dim3(256), kBwdTileLds, batch);
+  GemmArgs<2> args;
+  if (batch.n != 2 || !pack_args(batch, args, false)) return hipErrorInvalidValue;
+  return launch(on, gemm_bwd_seq<DLDS>, dim3(grid), dim3(256), kBwdTileLds, args);
 }
 template <typename K>
 inline hipError_t direct_prepare(K kernel, int lds_bytes) {

@@ -651,12 +651,14 @@ struct QTrainHook {
   }
 };
 template <int UNUSED = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dgrad_qtrain(const GemmBatch batch, const HeadTrainArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dgrad_qtrain(const GemmArgs<1> args, const HeadTrainArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float s_scale[16], s_dq[16];
-  int pi, tile_p, tile_q;
-  tile_of_block(batch, pi, tile_p, tile_q);
-  const GemmProblem& pr = batch.prob[0];
+  int tile_p, tile_q;
+  HotArgs<1> r;
+  const int b = request_args(args, r, (int)blockIdx.x);
+  const GemmProblem pr = problem_at<0>(args, r);
+  tile_of_problem(pr, b, tile_p, tile_q);
   const int q0 = tile_q * 16;
   QTrainHook hook(a, s_scale, s_dq, q0, tile_p);
   dgrad_lds_body<1, 1, true, QTrainHook>(pr, tile_p, tile_q, smem, s_scale, hook);
@@ -676,7 +678,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 inline hipError_t dgrad_qtrain_launch(GemmBatch& batch, const HeadTrainArgs& a, const LaunchOn& on) {
   batch.n = 1;
-  return launch(on, k_dgrad_qtrain<0>, dim3(tile_batch(batch, 64, 16)), dim3(256), dgrad_lds_bytes<1, 1>(), batch, a);
+  tile_batch(batch, 64, 16);
+  GemmArgs<1> args;
+  if (!pack_args(batch, args)) return hipErrorInvalidValue;
+  return launch(on, k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), dgrad_lds_bytes<1, 1>(), args, a);
 }
 
 // Fused head backward: in one pass over the tower top X4[rows][H]
@@ -902,9 +907,14 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
   extern __shared__ __attribute__((aligned(16))) float smem[];     // the narrow dgrad's parking area (4 waves x 64 lanes x 16 B)
   __shared__ float s_d[16][17];
   __shared__ float s_dy[16 * kNO];
+  // what routes the workgroup, what the head part's first loads need and the narrow tile's operands: ONE round of scalar loads
+  // (request_args, gemm_direct.hip.h, has the reasoning; left alone: the tile count, then the head's pointers, then the tile's)
+  int blk = (int)blockIdx.x;
+  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred));
+  else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
   const int tiles = a.row_tiles * ((a.H + 255) >> 8);
-  if ((int)blockIdx.x >= tiles) { q_head_rider(rider, (int)blockIdx.x - tiles); return; }
-  const int rt = (int)blockIdx.x % a.row_tiles, cc = (int)blockIdx.x / a.row_tiles;
+  if (blk >= tiles) { q_head_rider(rider, blk - tiles); return; }
+  const int rt = blk % a.row_tiles, cc = blk / a.row_tiles;
   const int tid = threadIdx.x, q0 = rt * 16;
   // (round 6: any tower-top width — the reference's own tower ends in 128 units; threads beyond it keep column H - 1's loads, take
   // part in the tile and the barriers, and store nothing)
@@ -1314,6 +1324,15 @@ __device__ __forceinline__ void adam_apply1(const AdamArgs& a, float scale, floa
   m = mi; v = vi; w = wi;
   if (soft) wt = fmaf(tau, wi, omt * wt);
 }
+// The optimiser launches that carry rider blocks: the block counts that route a workgroup (up to three) and what the strided pass's
+// first loads need (the arena pointers and lengths) are requested in ONE round of scalar loads — the (empty) statement reads
+// them and hands back the block index everything is routed by (request_args, gemm_direct.hip.h, has the reasoning).  Left alone
+// the compiler requests each rider's count only once the one before it has ruled the block out: up to four dependent rounds
+// before a strided block's first load.
+__device__ __forceinline__ int adam_routed_block(const AdamArgs& a, int b, int c0, int c1 = 0, int c2 = 0) {
+  asm volatile("" : "+s"(b) : "s"(c0), "s"(c1), "s"(c2), "s"(a.w), "s"(a.wt), "s"(a.wt_sh), "s"(a.n4), "s"(a.partial));
+  return b;
+}
 template <int U = 1, int NT = 0, bool PRE = false>
 __device__ __forceinline__ void adam_soft_body(const AdamArgs& a, int blk, int nblk, float* s /*>= 8 floats*/) {
   // U float4 per array in flight per thread (U * 5 x 16-B loads before the first use); NT: the gradient is
@@ -1395,10 +1414,11 @@ static __global__ __launch_bounds__(256) void k_adam_soft(AdamArgs a) {
 // forward, its scalars go to the other DevState slot, its counters come from DevState::gbase), the rest is k_adam_soft.
 // Takes the gather (a ~5-us launch of two dependent HBM round trips) off the chain of all but the first update of such a graph.
 static __global__ __launch_bounds__(256) void k_adam_soft_gather(AdamArgs a, GatherArgs g) {
+  const int b0 = adam_routed_block(a, (int)blockIdx.x, g.blocks);
   __shared__ float s[8];
   __shared__ double sq[4];
-  if ((int)blockIdx.x < g.blocks) { gather_block(g, (int)blockIdx.x); return; }
-  const int blk = (int)blockIdx.x - g.blocks;
+  if (b0 < g.blocks) { gather_block(g, b0); return; }
+  const int blk = b0 - g.blocks;
   adam_soft_body<1, 0>(a, blk, (int)gridDim.x - g.blocks, s);
   if (a.tick_on && blk == 0) {
     const bool skipped = s[7] != 0.0f;
@@ -1535,15 +1555,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
   __shared__ __attribute__((aligned(16))) float sW[16 * 64 * G];
   __shared__ __attribute__((aligned(16))) float sB[16];
   __shared__ __attribute__((aligned(16))) float park[4096];
-  if ((int)blockIdx.x < r.blocks) {
-    FirstLayerWork<G> work(a, r, (int)blockIdx.x, sW, sB, park);
+  const int b = adam_routed_block(a, (int)blockIdx.x, r.blocks);
+  if (b < r.blocks) {
+    FirstLayerWork<G> work(a, r, b, sW, sB, park);
     work.request();
     adam_scalars<true>(a, -1, s);          // (-1: the strided pass's first workgroup reports a skipped step)
     // (a skipped step — non-finite gradient norm — still runs the layer, on the weights as they are)
     work.run(s[4], s[5], s[6] != 0.0f, s[7] == 0.0f);
     return;
   }
-  adam_soft_body<1, 0, true>(a, (int)blockIdx.x - r.blocks, (int)gridDim.x - r.blocks, s);
+  adam_soft_body<1, 0, true>(a, b - r.blocks, (int)gridDim.x - r.blocks, s);
 }
 
 // ... with the NEXT update's gather in the same launch (multi-update graphs, round 5: the gather moves from the update's last launch
@@ -1554,7 +1575,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
   __shared__ __attribute__((aligned(16))) float sW[16 * 64 * G];
   __shared__ __attribute__((aligned(16))) float sB[16];
   __shared__ __attribute__((aligned(16))) float park[4096];
-  const int b = (int)blockIdx.x;
+  const int b = adam_routed_block(a, (int)blockIdx.x, r.blocks, g.blocks);
   if (b < r.blocks) {
     FirstLayerWork<G> work(a, r, b, sW, sB, park);
     work.request();
@@ -1657,7 +1678,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
   __shared__ __attribute__((aligned(16))) float sW[2 * 16 * 64];
   __shared__ __attribute__((aligned(16))) float sB[32];
   __shared__ __attribute__((aligned(16))) float park[4096];
-  int b = (int)blockIdx.x;
+  int b = adam_routed_block(a, (int)blockIdx.x, ra.blocks, p0.blocks, p1.blocks);
   if (b < ra.blocks) {
     ActorL0Work work(a, ra, b, sW, sB, park);
     work.request();
