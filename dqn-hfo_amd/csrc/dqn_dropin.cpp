@@ -46,6 +46,9 @@ DEFINE_bool(chained_updates, true, "UpdateActorCritic() tells the library which 
             "dqnhip_update_chained): bursts of Update() get the launch schedule of a multi-update graph.  Same results, same RNG order.");
 DEFINE_bool(pipelined_stats, false, "UpdateActorCritic() returns the (loss, avg_q) of the PREVIOUS update (dqnhip_update_pipelined): "
                                     "the device does not idle on the per-update read-back; the logged / smoothed values lag by one update.");
+DEFINE_bool(deferred_updates, false, "Update() draws its indices as always but does not wait for the update: sixteen at a time are enqueued as one "
+            "multi-update graph (dqnhip_update_indexed_n) and the (loss, avg_q) pairs are collected where Update() logs or snapshots "
+            "(dqnhip_collect_stats).  Same weights, same log lines, same snapshots; a non-finite target aborts at the next collection.");
 // Data parallelism for the UNCHANGED driver: start one process of this binary per GPU — each with its own HFO
 // workers, its own replay shard, its own -save prefix and -hip_device — and the ranks' gradients are summed by RCCL inside
 // libdqnhip.so twice per update (after the critic's backward and after the actor's).  Every rank's k-th UpdateActorCritic()
@@ -217,6 +220,8 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   if (caffe::Caffe::mode() != caffe::Caffe::GPU)
     LOG(FATAL) << "[Agent" << tid << "] -gpu=false: Caffe CPU mode (src/dqn_main.cpp:208-212) is not provided by the MI355X drop-in "
                << "(libdqnhip.so has no CPU backend). Run the reference's own Caffe build for the CPU solver, or start this binary with -gpu=true.";
+  CHECK(!(FLAGS_deferred_updates && FLAGS_pipelined_stats)) << "-deferred_updates cannot be combined with -pipelined_stats (both decide when an update's (loss, avg_q) reach the host)";
+  CHECK(!(FLAGS_deferred_updates && FLAGS_device_sampling)) << "-deferred_updates cannot be combined with -device_sampling (deferred updates run on the indices random_engine draws)";
   std::vector<int> wa = TowerWidths(actor_solver_param_.net_param()), wc = TowerWidths(critic_solver_param_.net_param());
   if (wa.empty()) wa = kDefaultTower;
   if (wc.empty()) wc = kDefaultTower;
@@ -249,6 +254,7 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   CHECK(FLAGS_precision == "fp32" || FLAGS_precision == "fp16") << "-precision must be fp32 or fp16";
   c.precision = FLAGS_precision == "fp16" ? DQNHIP_FP16 : DQNHIP_FP32;
   dp_ = !FLAGS_dp_rendezvous.empty();
+  deferred_ = FLAGS_deferred_updates && !dp_;          // (data parallel: every update is a collective the ranks enter together)
   CHECK(dp_ || FLAGS_dp_world == 1) << "-dp_world > 1 needs -dp_rendezvous <path shared by the ranks>";
   if (dp_) {
     CHECK(!FLAGS_pipelined_stats) << "-pipelined_stats is a single-learner option (the data-parallel update reports its own scalars)";
@@ -303,14 +309,63 @@ void DQN::RearmReplicaSync(const char* what) {
   dp_sync_pending_ = true;
 }
 
-DQN::~DQN() { DQNHIP_CK(dqnhip_destroy(h_)); }
+DQN::~DQN() { CollectDeferred(); DQNHIP_CK(dqnhip_destroy(h_)); }
+
+// ---- -deferred_updates ------------------------------------------------------------------------------------------------------
+// The driver calls Update() in bursts and discards the result (src/dqn_main.cpp:340-343, 359-361; Update() is void, src/dqn.hpp:103):
+// between calls it reads max_iter() only.  So Update() draws its indices where the blocking form draws them and returns; every
+// other entry point that touches the learner submits what is pending first and stream order does the rest.  The pairs are collected
+// - and Update()'s bookkeeping replayed in update order, each update with its own iteration numbers - at the Update() whose
+// iteration numbers make a log line or a snapshot due, so both see exactly the updates the blocking form's would; and, so that the
+// library's uncollected pairs (8 bytes each) stay bounded, once kMaxUncollected updates are outstanding (32 KiB).
+namespace { constexpr int kSubmitEvery = 16, kMaxUncollected = 4096; }
+
+void DQN::SubmitPending() {
+  if (pend_n_ == 0) return;
+  static_assert(sizeof(int) == sizeof(int32_t), "indices travel as int32");
+  DQNHIP_CK(dqnhip_update_indexed_n(h_, reinterpret_cast<const int32_t*>(pend_idx_.data()), pend_n_));
+  uncollected_ += pend_n_;
+  pend_n_ = 0;
+}
+
+void DQN::CollectDeferred(bool bookkeep) {
+  SubmitPending();
+  float loss[256], avgq[256];
+  while (uncollected_ > 0) {
+    int32_t n = 0;
+    const int rc = dqnhip_collect_stats(h_, loss, avgq, 256, &n);
+    if (rc != 0) LOG(FATAL) << "[Agent" << tid_ << "] deferred update: " << dqnhip_last_error();
+    CHECK_GT(n, 0) << "dqnhip_collect_stats returned nothing with " << uncollected_ << " updates outstanding";
+    for (int i = 0; i < n; ++i) {
+      book_critic_iter_ += 1; book_actor_iter_ += 1;
+      if (bookkeep) Bookkeep(std::make_pair(loss[i], avgq[i]), book_critic_iter_, book_actor_iter_);
+    }
+    uncollected_ -= n;
+  }
+}
+
+void DQN::StopDeferring() { CollectDeferred(); deferred_ = false; }
 
 // src/dqn.cpp:487-498: a wall-clock timer around `iterations` calls of UpdateActorCritic() — host-drawn
 // indices and a blocking (loss, avg_q) per call, unless -device_sampling / -pipelined_stats say otherwise
 void DQN::Benchmark(int iterations) {
   LOG(INFO) << "*** Benchmark begins ***";
+  CollectDeferred();
   const auto t0 = std::chrono::steady_clock::now();
-  if (FLAGS_device_sampling && !FLAGS_pipelined_stats && !dp_ && iterations > 0) {
+  if (deferred_ && iterations > 0) {
+    // the loop below through the deferred path: the same draws, a submit every sixteen updates, one collection at the end
+    // (UpdateActorCritic() does none of Update()'s bookkeeping: the pairs are dropped)
+    SyncReplicasIfPending();
+    book_actor_iter_ = actor_iter(); book_critic_iter_ = critic_iter();
+    pend_idx_.resize((size_t)kSubmitEvery * minibatch_);
+    for (int i = 0; i < iterations; ++i) {
+      const std::vector<int> idx = SampleTransitionsFromMemory(minibatch_);
+      std::copy(idx.begin(), idx.end(), pend_idx_.begin() + (size_t)pend_n_ * minibatch_);
+      if (++pend_n_ == kSubmitEvery) SubmitPending();
+      if (uncollected_ >= kMaxUncollected) CollectDeferred(false);
+    }
+    CollectDeferred(false);
+  } else if (FLAGS_device_sampling && !FLAGS_pipelined_stats && !dp_ && iterations > 0) {
     // nothing between the updates needs the host: the whole loop is one call (sixteen updates per hipGraph launch)
     float loss = 0.0f, avg_q = 0.0f;
     DQNHIP_CK(dqnhip_update_async_n(h_, iterations));
@@ -322,19 +377,21 @@ void DQN::Benchmark(int iterations) {
   LOG(INFO) << "*** Benchmark ends ***";
 }
 
-void DQN::RestoreActorSolver(const std::string& f) { RearmReplicaSync("RestoreActorSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_ACTOR, f.c_str())); last_snapshot_iter_ = max_iter(); }
-void DQN::RestoreCriticSolver(const std::string& f) { RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter(); }
-void DQN::LoadActorWeights(const std::string& f) { RearmReplicaSync("LoadActorWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_ACTOR, f.c_str())); }
-void DQN::LoadCriticWeights(const std::string& f) { RearmReplicaSync("LoadCriticWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_CRITIC, f.c_str())); }
+void DQN::RestoreActorSolver(const std::string& f) { CollectDeferred(); RearmReplicaSync("RestoreActorSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_ACTOR, f.c_str())); last_snapshot_iter_ = max_iter(); }
+void DQN::RestoreCriticSolver(const std::string& f) { CollectDeferred(); RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter(); }
+void DQN::LoadActorWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadActorWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_ACTOR, f.c_str())); }
+void DQN::LoadCriticWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadCriticWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_CRITIC, f.c_str())); }
 void DQN::LoadReplayMemory(const std::string& f) {
+  SubmitPending();
   LOG(INFO) << "Loading replay memory from " << f;
   DQNHIP_CK(dqnhip_load_replay_memory(h_, f.c_str()));
   LOG(INFO) << "replay_mem_size = " << memory_size();
 }
-void DQN::SnapshotReplayMemory(const std::string& f) { DQNHIP_CK(dqnhip_snapshot_replay_memory(h_, f.c_str())); }
+void DQN::SnapshotReplayMemory(const std::string& f) { SubmitPending(); DQNHIP_CK(dqnhip_snapshot_replay_memory(h_, f.c_str())); }
 
 void DQN::Snapshot() { Snapshot(save_path_, FLAGS_remove_old_snapshots, FLAGS_snapshot_memory); }
 void DQN::Snapshot(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory) {
+  SubmitPending();
   if (snapshot_memory) LOG(INFO) << "Snapshotting memory to " << snapshot_prefix << "_iter_" << max_iter() << ".replaymemory";
   DQNHIP_CK(dqnhip_snapshot(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, snapshot_memory));
   LOG(INFO) << "Snapshotting Finished!";
@@ -359,6 +416,7 @@ ActorOutput DQN::SelectAction(const InputStates& last_states, const double epsil
 
 std::vector<ActorOutput> DQN::SelectActions(const std::vector<InputStates>& states_batch, const double epsilon) {
   CHECK(epsilon >= 0.0 && epsilon <= 1.0);
+  SubmitPending();
   // :699 CHECK_LE(states_batch.size(), kMinibatchSize): the MemoryData layer is that wide there; here the cap is kept as the
   // reference's behaviour with this learner's minibatch, and -select_actions_cap widens it (the device path takes any n)
   const int cap = FLAGS_select_actions_cap == 0 ? minibatch_ : FLAGS_select_actions_cap;
@@ -395,18 +453,21 @@ Action DQN::SampleAction(const ActorOutput& actor_output) {
 }
 
 float DQN::EvaluateAction(const InputStates& input_states, const ActorOutput& action) {
+  SubmitPending();
   float q = 0;
   DQNHIP_CK(dqnhip_critic_forward(h_, DQNHIP_CRITIC, input_states[0]->data(), action.data(), 1, &q));
   return q;
 }
 
 void DQN::AddTransition(const Transition& t) {
+  SubmitPending();
   const auto& next = std::get<4>(t);
   DQNHIP_CK(dqnhip_add_transition(h_, std::get<0>(t)[0]->data(), std::get<1>(t).data(), std::get<2>(t), std::get<3>(t),
                                   next ? (*next)->data() : nullptr, next ? 0 : 1));
 }
 
 void DQN::AddTransitions(const std::vector<Transition>& ts) {
+  SubmitPending();
   const size_t n = ts.size(), S = (size_t)state_size_;
   if (n == 0) { DQNHIP_CK(dqnhip_add_transitions(h_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0)); return; }   // (:776 still evicts one from a full deque)
   std::vector<float> s(n * S), nx(n * S, 0.f), a(n * (kActionSize + kActionParamSize)), r(n), mc(n);
@@ -438,18 +499,37 @@ void DQN::Update() {
   // alone in a collective would wait for ever
   if (dp_ && actor_solver_param_.max_iter() > 0 && max_iter() >= actor_solver_param_.max_iter()) return;
   if (memory_size() < FLAGS_memory_threshold) return;
+  if (deferred_) {
+    if (pend_n_ == 0 && uncollected_ == 0) { book_actor_iter_ = actor_iter(); book_critic_iter_ = critic_iter(); }
+    const std::vector<int> idx = SampleTransitionsFromMemory(minibatch_);      // the draw, where the blocking form draws
+    pend_idx_.resize((size_t)kSubmitEvery * minibatch_);
+    std::copy(idx.begin(), idx.end(), pend_idx_.begin() + (size_t)pend_n_ * minibatch_);
+    pend_n_ += 1;
+    const int c = critic_iter(), a = actor_iter();                             // this update's numbers
+    const bool due = c % FLAGS_loss_display_iter == 0 || a % FLAGS_loss_display_iter == 0 ||
+                     c >= last_snapshot_iter_ + FLAGS_snapshot_freq || a >= last_snapshot_iter_ + FLAGS_snapshot_freq ||
+                     pend_n_ + uncollected_ >= kMaxUncollected;
+    if (due) CollectDeferred();              // (the last replayed Bookkeep is this update's: it logs / snapshots)
+    else if (pend_n_ == kSubmitEvery) SubmitPending();
+    return;
+  }
   const std::pair<float, float> res = UpdateActorCritic();
-  if (critic_iter() % FLAGS_loss_display_iter == 0) {
-    LOG(INFO) << "[Agent" << tid_ << "] Critic Iteration " << critic_iter() << ", loss = " << smoothed_critic_loss_;
+  Bookkeep(res, critic_iter(), actor_iter());
+}
+
+// src/dqn.cpp:806-825 behind UpdateActorCritic(), on the iteration numbers that update left
+void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_it) {
+  if (critic_it % FLAGS_loss_display_iter == 0) {
+    LOG(INFO) << "[Agent" << tid_ << "] Critic Iteration " << critic_it << ", loss = " << smoothed_critic_loss_;
     smoothed_critic_loss_ = 0;
   }
   smoothed_critic_loss_ += res.first / float(FLAGS_loss_display_iter);
-  if (actor_iter() % FLAGS_loss_display_iter == 0) {
-    LOG(INFO) << "[Agent" << tid_ << "] Actor Iteration " << actor_iter() << ", avg_q_value = " << smoothed_actor_loss_;
+  if (actor_it % FLAGS_loss_display_iter == 0) {
+    LOG(INFO) << "[Agent" << tid_ << "] Actor Iteration " << actor_it << ", avg_q_value = " << smoothed_actor_loss_;
     smoothed_actor_loss_ = 0;
   }
   smoothed_actor_loss_ += res.second / float(FLAGS_loss_display_iter);
-  if (critic_iter() >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_iter() >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
+  if (critic_it >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_it >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
     Snapshot();
     last_snapshot_iter_ = max_iter();
   }
@@ -463,6 +543,7 @@ std::vector<int> DQN::SampleTransitionsFromMemory(int n) {
 }
 
 std::vector<InputStates> DQN::SampleStatesFromMemory(int n) {
+  SubmitPending();
   const std::vector<int> idx = SampleTransitionsFromMemory(n);
   std::vector<float> flat((size_t)n * state_size_);
   DQNHIP_CK(dqnhip_sample_states(h_, idx.data(), n, flat.data()));
@@ -473,6 +554,7 @@ std::vector<InputStates> DQN::SampleStatesFromMemory(int n) {
 }
 
 std::pair<float, float> DQN::UpdateActorCritic() {
+  CollectDeferred();
   SyncReplicasIfPending();
   if (FLAGS_device_sampling) {
     float loss = 0, avgq = 0;
@@ -502,6 +584,7 @@ std::pair<float, float> DQN::UpdateActorCritic() {
 
 std::pair<float, float> DQN::UpdateActorCritic(const std::vector<int>& transitions) {
   CHECK_EQ((int)transitions.size(), minibatch_);
+  CollectDeferred();
   SyncReplicasIfPending();
   float loss = 0, avgq = 0;
   static_assert(sizeof(int) == sizeof(int32_t), "indices travel as int32");
@@ -513,12 +596,15 @@ std::pair<float, float> DQN::UpdateActorCritic(const std::vector<int>& transitio
   return std::make_pair(loss, avgq);
 }
 
-void DQN::ClearReplayMemory() { DQNHIP_CK(dqnhip_clear_memory(h_)); }
+void DQN::ClearReplayMemory() { SubmitPending(); DQNHIP_CK(dqnhip_clear_memory(h_)); }
 int DQN::memory_size() const { int32_t n = 0; DQNHIP_CK(dqnhip_memory_size(h_, &n)); return n; }
-int DQN::critic_iter() const { int32_t a = 0, c = 0; DQNHIP_CK(dqnhip_get_iters(h_, &a, &c)); return c; }
-int DQN::actor_iter() const { int32_t a = 0, c = 0; DQNHIP_CK(dqnhip_get_iters(h_, &a, &c)); return a; }
+int DQN::critic_iter() const { int32_t a = 0, c = 0; DQNHIP_CK(dqnhip_get_iters(h_, &a, &c)); return c + pend_n_; }     // (+ drawn, not yet submitted: -deferred_updates)
+int DQN::actor_iter() const { int32_t a = 0, c = 0; DQNHIP_CK(dqnhip_get_iters(h_, &a, &c)); return a + pend_n_; }
 
+// (sharing, either side: the driver's global mutex orders one agent's update burst against another agent's writes, and an update
+// that ran after the mutex was released would see a different ring - deferral is off for both objects from here on)
 void DQN::ShareParameters(DQN& other, int num_actor_layers_to_share, int num_critic_layers_to_share) {
+  StopDeferring(); other.StopDeferring();
   DQNHIP_CK(dqnhip_share_parameters(h_, other.h_, num_actor_layers_to_share, num_critic_layers_to_share));
 }
 // src/dqn.cpp:1037-1045 shares the blobs of two caffe::Layer objects; the nets here are parameter arenas
@@ -530,6 +616,7 @@ void DQN::ShareReplayMemory(DQN& other) {
   // (see the constructor: a shared replay puts the driver's global MTX around collectives of two independent groups)
   CHECK(!dp_ && !other.dp_) << "ShareReplayMemory cannot be combined with -dp_rendezvous: the driver holds one mutex around every agent's "
                             << "Update() burst (src/dqn_main.cpp:358-362) and each agent's updates are collectives of its own group";
+  StopDeferring(); other.StopDeferring();
   DQNHIP_CK(dqnhip_share_replay_memory(h_, other.h_));
 }
 

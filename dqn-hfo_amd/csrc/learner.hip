@@ -237,6 +237,9 @@ GatherArgs gather_args(H* h, const int* idx_dev, int pos) {
   g.beta1 = h->cfg.momentum; g.beta2 = h->cfg.momentum2; g.soft_update_freq = h->cfg.soft_update_freq;
   g.ahead = pos > 0 ? pos : -1; g.store_base = pos == 0 ? 1 : 0;
   if (h->chain_cap && pos > 0) { g.idx_in = h->idx_next_dev[pos & 1]; g.ahead = -2; }      // dqnhip_update_chained: the next update's indices, known one call ahead
+  // dqnhip_update_indexed_n: every rider form (k_adam_soft_fwd1_gather, k_adam_soft_gather) reads slot `pos` of the graph's index bank;
+  // the counters stay gbase + pos, as in a sampled graph
+  if (h->cap_idx != nullptr && pos > 0) g.idx_in = h->cap_idx + (size_t)pos * h->B;
   g.blocks = (h->B + 3) / 4 + 1;
   return g;
 }
@@ -505,7 +508,9 @@ static int tails_launch(hipStream_t st, const TailsArgs& t) {
 // the bookkeeping block of the update's last launch: publishes (critic_loss, avg_q), advances the iteration / sampling counters
 static TickArgs tick_args(const H* h, bool dp) {
   return TickArgs{h->st, grad_tail(h, DQNHIP_CRITIC), grad_tail(h, DQNHIP_ACTOR), (const float*)h->loss_partial, h->n_head_blocks,
-                  dp ? (const double*)nullptr : (const double*)h->q_partial, h->B, (float)(h->B * h->cfg.dp_world), h->stats_dev};
+                  dp ? (const double*)nullptr : (const double*)h->q_partial, h->B, (float)(h->B * h->cfg.dp_world),
+                  // (dqnhip_update_indexed_n: the update's own slot of the graph's stats bank)
+                  h->cap_stats ? h->cap_stats + 4 * std::max(h->cap_u, 0) : h->stats_dev};
 }
 // 1-2: sample + gather (src/dqn.cpp:846-887).  Later updates of a multi-update graph: it rode in the previous update's last launch
 static int gather_launch(H* h, hipStream_t st, const int* idx_dev) {

@@ -30,6 +30,8 @@ int ensure_act(H* h, int rows) {
 void drop_graphs(H* h) {
   for (auto& g : h->graph_exec) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   for (auto& g : h->graph_small) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  for (auto& bank : h->ix_graph) for (auto& g : bank) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  for (int& n : h->ix_nodes) n = 0;
   if (h->dp_graph) { hipGraphExecDestroy(h->dp_graph); h->dp_graph = nullptr; }
   if (h->dp_graph_n) { hipGraphExecDestroy(h->dp_graph_n); h->dp_graph_n = nullptr; }
   h->dp_graph_failed = false; h->dp_graph_n_failed = false; h->graph_failed = false;
@@ -235,6 +237,11 @@ int dqnhip_destroy(dqnhip_handle h) {
     if (h->pipe_ev[i]) hipEventDestroy(h->pipe_ev[i]);
     if (h->pipe_idx_pinned[i]) hipHostFree(h->pipe_idx_pinned[i]);
     if (h->pipe_stats[i]) hipHostFree(h->pipe_stats[i]);
+  }
+  for (int b = 0; b < kIxBanks; ++b) {
+    if (h->ix_ev[b]) hipEventDestroy(h->ix_ev[b]);
+    if (h->ix_idx[b]) hipHostFree(h->ix_idx[b]);
+    if (h->ix_stats[b]) hipHostFree(h->ix_stats[b]);
   }
   for (int i = 0; i < 4; ++i) hipFree(h->w[i]);
   for (int i = 0; i < 2; ++i) { hipFree(h->m[i]); hipFree(h->v[i]); hipFree(h->part[i]); }

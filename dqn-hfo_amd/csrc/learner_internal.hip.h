@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <random>
 #include <string>
 #include <vector>
@@ -66,6 +67,10 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline size_t round_up_z(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 constexpr int kMaxL = DQNHIP_MAX_HIDDEN;
+// dqnhip_update_indexed_n: host-mapped index / stats banks, one multi-update graph in flight per bank (see learner_update.hip), and
+// the graph sizes an n is cut into (16 / 8 / 4 / 2 / 1, as dqnhip_update_async_n cuts it)
+constexpr int kIxBanks = 2;
+constexpr int kIxSizes = 5;
 // fp16 learner: ALL wgrads of a net in one launch of 128x128 tiles from this many minibatch rows (the reduction
 // length); below, the per-layer form (a layer's dgrad + wgrad sharing a launch of 64x64 split-K tiles) is as fast or
 // faster (measured at 256 / 512 / 1024 / 2048 / 4096 rows: +0.7 / -6 / -28 / -37 / -68 us per update)
@@ -224,6 +229,22 @@ struct dqnhip_learner {
   int* pipe_idx_dev[2] = {nullptr, nullptr}; int* pipe_idx_pinned[2] = {nullptr, nullptr};
   float* pipe_stats[2] = {nullptr, nullptr};
   unsigned long long pipe_count = 0;
+  // dqnhip_update_indexed_n / dqnhip_collect_stats.  Bank b: kMultiU index vectors and kMultiU {loss, avg_q, flags, -} slots in pinned,
+  // host-mapped memory; position u of a graph captured for bank b gathers from index slot u and its tick writes stats slot u.
+  // ix_ev[b] is recorded behind whatever was enqueued on the bank; ix_busy[b] is the number of updates of it not yet harvested.
+  int* ix_idx[kIxBanks] = {nullptr}; const int* ix_idx_dev[kIxBanks] = {nullptr};
+  float* ix_stats[kIxBanks] = {nullptr}; float* ix_stats_dev[kIxBanks] = {nullptr};
+  hipEvent_t ix_ev[kIxBanks] = {nullptr};
+  int ix_busy[kIxBanks] = {0};
+  int ix_next = 0;                      // the bank the next graph takes (round robin: the busy banks are the most recent ones, in order)
+  hipGraphExec_t ix_graph[kIxBanks][kIxSizes] = {{nullptr}};   // [bank][16, 8, 4, 2, 1 updates]
+  int ix_nodes[kIxSizes] = {0};         // kernel nodes of the captured graph of each size (dqnhip_debug_read "indexed_graph_launches")
+  const int* cap_idx = nullptr;         // while an indexed graph is captured / an indexed update runs eagerly: the bank's index slots ...
+  float* cap_stats = nullptr;           // ... and its stats slots (device aliases); tick_args / gather_args read them
+  std::deque<float> ix_pairs;           // harvested, uncollected (loss, avg_q) pairs, flat: 8 bytes per update
+  std::deque<std::pair<unsigned long long, int>> ix_flagged;   // (sequence number, flags that update raised) of harvested updates
+  unsigned long long ix_harvested = 0, ix_collected = 0;       // sequence numbers: updates harvested / handed out so far
+  int ix_prev_flags = 0;                // the sticky device flags as the last harvested update left them (a raise = a bit not in here)
 };
 
 namespace dqnhip_host {
@@ -339,10 +360,14 @@ int run_update(H* h, const int* idx_dev);                // phases 0, 1, 2
 struct CaptureSpec {
   int updates = 1; bool multi = false; int of = kMultiU; int chain_pos = -1;
   const int* idx_dev = nullptr;                          // explicit indices (nullptr: sampled on the device)
+  // dqnhip_update_indexed_n: position u gathers from idx_bank + u * B (position 0: idx_dev, the same address) and its tick writes
+  // stats_bank + 4 * u instead of the learner's one pinned triple
+  const int* idx_bank = nullptr; float* stats_bank = nullptr;
   int (*body)(H*, const int*) = run_update;              // (data parallel: dp_sequence, the phases with the exchange between them)
 };
 int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph);
-int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out);      // ... and instantiate
+int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out, int* kernel_nodes = nullptr);      // ... and instantiate
+int ix_harvest_all(H* h);                                // waits for every indexed update enqueued so far and files its scalars
 // learner_create.hip
 int ensure_stage(H* h, size_t bytes);
 int ensure_act(H* h, int rows);

@@ -519,6 +519,11 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t B = h->B;
   const float* src = nullptr; size_t n = B; bool pad16 = false; bool is_int = false;
+  if (!strcmp(name, "indexed_graph_launches")) {
+    if (count < 1) return fail("buffer too small for '%s'", name);
+    host[0] = (float)h->ix_nodes[0];
+    return 0;
+  }
   if (!strcmp(name, "q_target")) src = h->q_t;
   else if (!strcmp(name, "y")) src = h->y;
   else if (!strcmp(name, "q_train")) src = h->q1;

@@ -53,12 +53,14 @@ int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph) {
   const int it_a = h->h_actor_iter, it_c = h->h_critic_iter;
   int rc = 0;
   h->cap_n = s.of;
+  h->cap_idx = s.idx_bank; h->cap_stats = s.stats_bank;
   h->chain_cap = s.chain_pos >= 0;
   for (int u = 0; u < s.updates && !rc; ++u) {
     h->cap_u = s.multi ? u : s.chain_pos;
     rc = s.body(h, s.idx_dev);
   }
   h->cap_u = -1; h->chain_cap = false; h->cap_n = kMultiU;
+  h->cap_idx = nullptr; h->cap_stats = nullptr;
   select_panels(h, 0);
   h->h_actor_iter = it_a; h->h_critic_iter = it_c;
   const std::string msg = g_err;
@@ -67,10 +69,12 @@ int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph) {
   if (e != hipSuccess) return fail("hipStreamEndCapture: %s", hipGetErrorString(e));
   return 0;
 }
-// ... instantiated into *out (nullptr on failure)
-int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out) {
+static int count_kernel_nodes(hipGraph_t g, int* out);
+// ... instantiated into *out (nullptr on failure); kernel_nodes: the number of kernels it launches
+int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out, int* kernel_nodes) {
   hipGraph_t graph = nullptr;
   RC(capture_updates(h, s, &graph));
+  if (kernel_nodes && count_kernel_nodes(graph, kernel_nodes)) { hipGraphDestroy(graph); *out = nullptr; return 1; }
   const hipError_t e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
   hipGraphDestroy(graph);
   if (e != hipSuccess) { *out = nullptr; return fail("hipGraphInstantiate: %s", hipGetErrorString(e)); }
@@ -102,9 +106,9 @@ static CaptureSpec slot_spec(const H* h, GraphSlot slot, const int* idx_dev) {
 
 // *g, captured from `s` on first use; nullptr where graphs are off, kernel timing is on, or a capture has failed (which turns
 // graphs off for this learner)
-static hipGraphExec_t graph_of(H* h, hipGraphExec_t* g, const CaptureSpec& s) {
+static hipGraphExec_t graph_of(H* h, hipGraphExec_t* g, const CaptureSpec& s, int* kernel_nodes = nullptr) {
   if (!h->cfg.use_graph || h->timing || h->graph_failed) return nullptr;
-  if (!*g && capture_exec(h, s, g)) h->graph_failed = true;
+  if (!*g && capture_exec(h, s, g, kernel_nodes)) h->graph_failed = true;
   return *g;
 }
 static hipGraphExec_t graph_of(H* h, GraphSlot slot, const int* idx_dev = nullptr) {
@@ -145,6 +149,80 @@ static int count_launches(H* h, bool multi, int updates, int* out) {
   const int rc = count_kernel_nodes(graph, out);
   hipGraphDestroy(graph);
   return rc;
+}
+
+// ---- dqnhip_update_indexed_n: banks ---------------------------------------------------------------------------------------------
+// A captured graph has its index and stats addresses baked into its kernel arguments, and two graph launches may be in flight
+// without the host having waited, so one set of slots is not enough.  Chosen here: kIxBanks banks, each with its OWN captured
+// graphs (ix_graph[bank][size]) - the alternative, one set of graphs whose kernel nodes are re-pointed before every launch
+// (hipGraphExecKernelNodeSetParams on 16 gathers + 16 ticks), costs a host round per node per launch, where a second set of
+// graphs costs one more capture, once.  A bank is guarded by the event recorded behind its graph; the host waits on it only when
+// the round robin comes back to a bank that is still busy, i.e. with two banks it waits for the graph BEFORE the one that is
+// running, and the device always has the next graph queued.
+static int ix_ensure_banks(H* h) {
+  if (h->ix_idx[0]) return 0;
+  for (int b = 0; b < kIxBanks; ++b) {
+    // (system-scope release: the ticks' stores into the stats bank are visible to the host once the event has completed)
+    HIPCHK(hipEventCreateWithFlags(&h->ix_ev[b], hipEventDisableTiming | hipEventReleaseToSystem));
+    HIPCHK(hipHostMalloc((void**)&h->ix_stats[b], kMultiU * 4 * sizeof(float), hipHostMallocMapped));
+    memset(h->ix_stats[b], 0, kMultiU * 4 * sizeof(float));
+    { void* d = nullptr; HIPCHK(hipHostGetDevicePointer(&d, h->ix_stats[b], 0)); h->ix_stats_dev[b] = (float*)d; }
+    HIPCHK(hipHostMalloc((void**)&h->ix_idx[b], (size_t)kMultiU * h->B * sizeof(int), hipHostMallocMapped));
+    memset(h->ix_idx[b], 0, (size_t)kMultiU * h->B * sizeof(int));
+    { void* d = nullptr; HIPCHK(hipHostGetDevicePointer(&d, h->ix_idx[b], 0)); h->ix_idx_dev[b] = (const int*)d; }
+  }
+  return 0;
+}
+// waits for bank b's graph and files its updates' scalars, in update order
+static int ix_harvest(H* h, int b) {
+  if (!h->ix_busy[b]) return 0;
+  HIPCHK(hipEventSynchronize(h->ix_ev[b]));
+  for (int u = 0; u < h->ix_busy[b]; ++u) {
+    const float* s = h->ix_stats[b] + 4 * u;
+    int fl = 0; memcpy(&fl, &s[2], sizeof fl);
+    h->ix_pairs.push_back(s[0]); h->ix_pairs.push_back(s[1]);
+    // the device flags are sticky: what THIS update raised is what the one before it had not left behind
+    if (fl & ~h->ix_prev_flags) h->ix_flagged.emplace_back(h->ix_harvested, fl & ~h->ix_prev_flags);
+    h->ix_prev_flags = fl;
+    h->ix_harvested += 1;
+  }
+  h->ix_busy[b] = 0;
+  return 0;
+}
+int ix_harvest_all(H* h) {
+  // oldest first: the busy banks are the last ones the round robin handed out
+  for (int k = 0; k < kIxBanks; ++k) RC(ix_harvest(h, (h->ix_next + k) % kIxBanks));
+  return 0;
+}
+// `sz` updates (a graph size: 16 / 8 / 4 / 2 / 1, kind = its index in that list) on idx[0 .. sz * B), through the next bank
+static int ix_run(H* h, const int32_t* idx, int sz, int kind) {
+  const int b = h->ix_next;
+  RC(ix_harvest(h, b));                       // the only host wait: a bank that is still busy when its turn comes round again
+  h->ix_next = (b + 1) % kIxBanks;
+  memcpy(h->ix_idx[b], idx, (size_t)sz * h->B * sizeof(int));
+  CaptureSpec s;
+  // (one update: the stand-alone form, as dqnhip_update_async(idx) captures it)
+  s.updates = sz; s.of = sz; s.multi = sz > 1;
+  s.idx_dev = h->ix_idx_dev[b]; s.idx_bank = h->ix_idx_dev[b]; s.stats_bank = h->ix_stats_dev[b];
+  int rc = 0;
+  if (hipGraphExec_t g = graph_of(h, &h->ix_graph[b][kind], s, &h->ix_nodes[kind])) rc = replay(h, g, sz);
+  else
+    for (int u = 0; u < sz && !rc; ++u) {     // eagerly: the same slots
+      h->cap_stats = s.stats_bank + 4 * u;
+      rc = run_update(h, s.idx_bank + (size_t)u * h->B);
+      h->cap_stats = nullptr;
+    }
+  const hipError_t e = hipEventRecord(h->ix_ev[b], h->stream);
+  if (rc || e != hipSuccess) {
+    // whatever was enqueued before the failure still reads and writes the bank: nothing may reuse it before that has drained, and
+    // what it wrote belongs to no update the caller was told about (the bank stays free, its slots are not harvested)
+    const std::string msg = g_err;
+    hipStreamSynchronize(h->stream);
+    if (rc) { g_err = msg; return rc; }
+    return fail("hipEventRecord: %s", hipGetErrorString(e));
+  }
+  h->ix_busy[b] = sz;
+  return 0;
 }
 
 }  // namespace dqnhip_host
@@ -218,6 +296,78 @@ int dqnhip_update_async_n(dqnhip_handle h, int32_t n) {
   return 0;
 }
 
+// n updates on caller-supplied indices as multi-update graphs (see dqnhip.h): what the reference's driver asks for with
+// `for (i < n_updates) dqn->Update()` (src/dqn_main.cpp:359-361, :340-343) once the adaptor stops reading every update's scalars back
+// (Update() is void, src/dqn.cpp:799-826 only logs and snapshots).  Same cut as dqnhip_update_async_n, same capture machinery.
+int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host, int32_t n) {
+  if (!h) return fail("null handle");
+  h->epoch += 1;
+  if (n < 0) return fail("dqnhip_update_indexed_n: n must be >= 0");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
+  if (h->next_phase != 0) return fail("dqnhip_update_indexed_n: a phased update is in progress (next phase %d)", h->next_phase);
+  if (n == 0) return 0;
+  if (!idx_host) return fail("dqnhip_update_indexed_n: explicit indices required (on-device sampling: dqnhip_update_async_n)");
+  RingUse ring_use(h);
+  RC(refresh_ring(h));
+  if (RO(h)->h_size < 1) return fail("replay memory is empty");
+  // all of them before anything is enqueued
+  const long long size = RO(h)->h_size;
+  for (int u = 0; u < n; ++u)
+    for (int i = 0; i < h->B; ++i) {
+      const int32_t v = idx_host[(size_t)u * h->B + i];
+      if (v < 0 || v >= size) return fail("update %d: sampled index %d = %d out of range [0,%lld)", u, i, v, size);
+    }
+  RC(sync_dirty16(h));
+  RC(ix_ensure_banks(h));
+  const int32_t* idx = idx_host;
+  for (int kind = 0; kind < kIxSizes; ++kind) {
+    const int sz = kMultiU >> kind;
+    while (n >= sz) {
+      RC(ix_run(h, idx, sz, kind));
+      idx += (size_t)sz * h->B; n -= sz;
+      if (sz < kMultiU) break;              // (16s repeat; of each smaller size at most one)
+    }
+  }
+  // dqnhip_read_stats reads the learner's one pinned triple: the last update's, copied behind the last graph of the call (a tick
+  // has one host pointer, and that is its slot of the bank)
+  HIPCHK(hipMemcpyAsync(h->pinned_stats, &h->st->critic_loss, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  return 0;
+}
+
+int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss, float* avg_q, int32_t cap, int32_t* n_out) {
+  if (!h || !n_out) return fail("null argument");
+  *n_out = 0;
+  if (cap < 0 || (cap > 0 && (!critic_loss || !avg_q))) return fail("dqnhip_collect_stats: cap must be >= 0 and both arrays given");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RC(ix_harvest_all(h));
+  const int n = (int)std::min<size_t>((size_t)cap, h->ix_pairs.size() / 2);
+  int bad = -1;                               // first update of this collection that raised a flag or left a non-finite loss
+  for (int i = 0; i < n; ++i) {
+    critic_loss[i] = h->ix_pairs[2 * i]; avg_q[i] = h->ix_pairs[2 * i + 1];
+    if (bad < 0 && !std::isfinite(critic_loss[i])) bad = i;
+  }
+  h->ix_pairs.erase(h->ix_pairs.begin(), h->ix_pairs.begin() + 2 * n);
+  const unsigned long long end = h->ix_collected + (unsigned long long)n;
+  int flags = 0; bool any = false;
+  for (; !h->ix_flagged.empty() && h->ix_flagged.front().first < end; h->ix_flagged.pop_front()) {
+    const int pos = (int)(h->ix_flagged.front().first - h->ix_collected);
+    if (!any && (bad < 0 || pos <= bad)) { bad = pos; flags = h->ix_flagged.front().second; }
+    any = true;
+  }
+  h->ix_collected = end;
+  *n_out = n;
+  if (any) {      // sticky on the device until reported: cleared as dqnhip_read_stats clears them
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemsetAsync(&h->st->flags, 0, sizeof(int), h->stream));
+    h->pinned_stats[2] = 0.0f; h->ix_prev_flags = 0;
+  }
+  if (bad < 0) return 0;
+  if (flags & kFlagTarget) return fail("collected update %d: Target not finite!", bad);
+  if (flags & kFlagGradNorm) return fail("collected update %d: Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale)", bad);
+  return fail("collected update %d: Critic loss not finite!", bad);
+}
+
 int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host) {
   if (!h) return fail("null handle");
   h->epoch += 1;
@@ -259,10 +409,11 @@ int dqnhip_read_stats(dqnhip_handle h, float* critic_loss, float* avg_q) {
   // {critic_loss, avg_q, flags}: the last block of every update writes them into this pinned, host-mapped buffer itself
   // (tick_body): no device-to-host copy, the stream sync is the only wait
   HIPCHK(hipStreamSynchronize(h->stream));
+  RC(ix_harvest_all(h));     // (indexed updates: files their scalars - nothing to wait for any more - so that ix_prev_flags is the device's)
   if (critic_loss) *critic_loss = h->pinned_stats[0];
   if (avg_q) *avg_q = h->pinned_stats[1];
   int flags = 0; memcpy(&flags, &h->pinned_stats[2], sizeof flags);
-  if (flags) { HIPCHK(hipMemsetAsync(&h->st->flags, 0, sizeof(int), h->stream)); h->pinned_stats[2] = 0.0f; }   // sticky until reported
+  if (flags) { HIPCHK(hipMemsetAsync(&h->st->flags, 0, sizeof(int), h->stream)); h->pinned_stats[2] = 0.0f; h->ix_prev_flags = 0; }   // sticky until reported
   // CHECK(std::isfinite(target)) (src/dqn.cpp:898) and CHECK(std::isfinite(critic_loss)) (:906) — the
   // reference aborts; here: an error code from the first read after the offending update, whichever
   // entry point (blocking, async, phased, hipGraph) ran it
@@ -433,7 +584,29 @@ int dqnhip_benchmark_blocking(dqnhip_handle h, int32_t warmup, int32_t iteration
   float loss = 0, avgq = 0;
   std::vector<int32_t> nxt(h->B);
   bool have_next = false;
+  // pipelined == 3, the drop-in's -deferred_updates form: the draws of the other modes, a submit every sixteen updates, one collection
+  // every 1000 updates and at the end
+  std::vector<int32_t> pend; int n_pend = 0, since_collect = 0;
+  std::vector<float> cl(1024), cq(1024);
+  auto submit = [&]() -> int {
+    const int rc = n_pend ? dqnhip_update_indexed_n(h, pend.data(), n_pend) : 0;
+    n_pend = 0;
+    return rc;
+  };
+  auto collect = [&]() -> int {
+    RC(submit());
+    for (int32_t got = 1; got > 0;) RC(dqnhip_collect_stats(h, cl.data(), cq.data(), (int32_t)cl.size(), &got));
+    since_collect = 0;
+    return 0;
+  };
+  if (pipelined == 3) pend.resize((size_t)kMultiU * h->B);
   auto one = [&]() -> int {
+    if (pipelined == 3) {
+      for (int i = 0; i < h->B; ++i) pend[(size_t)n_pend * h->B + i] = std::uniform_int_distribution<int>(0, size - 1)(rng);
+      if (++n_pend == kMultiU) RC(submit());
+      if (++since_collect == 1000) RC(collect());
+      return 0;
+    }
     if (pipelined == 2) {
       // the drop-in's chained form (dqn_dropin.cpp UpdateActorCritic): the next update's indices are drawn one call ahead
       // (drawing the prediction after next while the update runs — an enqueue-only call, then dqnhip_read_stats — was measured
@@ -447,9 +620,11 @@ int dqnhip_benchmark_blocking(dqnhip_handle h, int32_t warmup, int32_t iteration
     return pipelined ? dqnhip_update_pipelined(h, idx.data(), &loss, &avgq) : dqnhip_update(h, idx.data(), &loss, &avgq);
   };
   for (int i = 0; i < warmup; ++i) RC(one());
+  if (pipelined == 3) RC(collect());
   HIPCHK(hipStreamSynchronize(h->stream));
   const auto t0 = std::chrono::steady_clock::now();
   for (int i = 0; i < iterations; ++i) RC(one());
+  if (pipelined == 3) RC(collect());
   HIPCHK(hipStreamSynchronize(h->stream));
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (pipelined == 1) RC(dqnhip_read_stats(h, &loss, &avgq));      // drains the one outstanding read-back

@@ -395,6 +395,32 @@ class DQN:
         """n updates with on-device sampling in one call (dqnhip_update_async_n)."""
         self._ck(self.lib.dqnhip_update_async_n(self.h, int(n)))
 
+    def update_indexed_n(self, idx):
+        """dqnhip_update_indexed_n: one update per row of idx ([n, B] int32), enqueued as multi-update graphs without waiting;
+        the state n UpdateActorCritic(idx[t]) calls leave.  collect_stats() returns the pairs."""
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        if i.size and (i.ndim != 2 or i.shape[1] != self.kMinibatchSize):
+            raise DQNFatal("need [n, %d] indices, got %r" % (self.kMinibatchSize, i.shape))
+        n = i.shape[0] if i.ndim == 2 else 0
+        self._ck(self.lib.dqnhip_update_indexed_n(self.h, i.ctypes.data_as(capi.ip) if n else None, n))
+
+    def collect_stats(self, cap=None, out=None):
+        """dqnhip_collect_stats: waits for the indexed updates enqueued so far; the (critic_loss, avg_q) pairs not yet collected, in
+        update order (at most cap of them; None: all).  A flagged update raises DQNFatal AFTER the pairs were appended to `out`
+        (pass a list to keep them)."""
+        pairs = [] if out is None else out
+        while cap is None or cap > 0:
+            k = 256 if cap is None else min(cap, 256)
+            loss, avgq, n = np.empty(k, np.float32), np.empty(k, np.float32), C.c_int32()
+            rc = self.lib.dqnhip_collect_stats(self.h, _p(loss), _p(avgq), k, C.byref(n))
+            pairs.extend((float(np.float32(a)), float(np.float32(b))) for a, b in zip(loss[:n.value], avgq[:n.value]))
+            self._ck(rc)
+            if cap is not None:
+                cap -= n.value
+            if n.value < k:
+                break
+        return pairs
+
     def update_phase(self, phase, idx=None):
         keep, ip = self._idx(idx)
         self._ck(self.lib.dqnhip_update_phase(self.h, phase, ip))
@@ -507,7 +533,8 @@ class DQN:
 
     def BenchmarkBlocking(self, iterations=1000, warmup=50, seed=1, pipelined=False):
         """DQN::Benchmark as the drop-in's caller sees it: host-drawn indices + a (loss, avg_q) read-back per
-        update (blocking, or one-deep pipelined); average wall-clock ms per update."""
+        update (blocking, or one-deep pipelined; 2: the chained form; 3: deferred — a dqnhip_update_indexed_n every sixteen
+        updates, a dqnhip_collect_stats every 1000); average wall-clock ms per update."""
         ms = C.c_float()
         self._ck(self.lib.dqnhip_benchmark_blocking(self.h, warmup, iterations, seed, int(pipelined), C.byref(ms)))
         return ms.value

@@ -152,6 +152,16 @@ class DQN {
   bool dp_synced_once_ = false;                        // the group's first update has passed: Restore* / Load* are refused from here on (one-sided collective)
   void SyncReplicasIfPending();
   void RearmReplicaSync(const char* what);
+  // -deferred_updates: Update() only draws its indices; sixteen at a time go to dqnhip_update_indexed_n without a wait, and the
+  // host bookkeeping of Update() (src/dqn.cpp:806-825) is replayed in update order when the pairs are collected (dqn_dropin.cpp)
+  bool deferred_ = false;                              // the flag is set and nothing has switched deferral off (-dp_rendezvous, sharing)
+  std::vector<int> pend_idx_; int pend_n_ = 0;         // drawn, not yet submitted ([pend_n_][minibatch_])
+  int uncollected_ = 0;                                // submitted, not yet collected
+  int book_actor_iter_ = 0, book_critic_iter_ = 0;     // the iteration counters as the last BOOKKEPT update left them (valid while any is outstanding)
+  void Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_it);   // Update()'s log lines, smoothed sums and snapshot check
+  void SubmitPending();                                // pending indices -> dqnhip_update_indexed_n (no host wait)
+  void CollectDeferred(bool bookkeep = true);          // submit, wait, replay Bookkeep for every outstanding update in order
+  void StopDeferring();                                // collect, then every Update() takes the blocking path again
   dqnhip_handle h_;
 };
 

@@ -213,6 +213,33 @@ int dqnhip_update_async(dqnhip_handle h, const int32_t* idx_host);
  * next chain (~12 us; DQNHIP_TUNE_LATE_GATHER: the gather alone, in update u's last launch). */
 int dqnhip_update_async_n(dqnhip_handle h, int32_t n);
 
+/* The same bursts on the CALLER's indices: n updates, update u on idx_host[u*B .. u*B+B), enqueued on the learner's stream without
+ * waiting for them.  The reference's driver calls DQN::Update() in bursts and discards what it returns (`for (i < n_updates)
+ * dqn->Update()`, src/dqn_main.cpp:359-361; `while (dqn->max_iter() < FLAGS_max_iter) dqn->Update()`, :340-343; Update() is void and
+ * only logs two smoothed values and snapshots, src/dqn.cpp:799-826), so nothing at that boundary needs one host wake-up and one graph
+ * launch per update.  Exactly the state n calls of dqnhip_update(h, idx_host + u*B, ..) leave, bit for bit (weights, m, v, iteration
+ * counters, replay bookkeeping, sampling counter); with use_graph the updates are replayed as graphs of 16 / 8 / 4 / 2 / 1 updates,
+ * cut as dqnhip_update_async_n cuts n, each position reading its indices from a pinned index bank and writing its scalars into a
+ * pinned stats bank (two banks: the host waits only for the graph BEFORE the one that is running).  All n*B indices are checked
+ * against the current memory size before anything is enqueued ("update 1: sampled index 3 = 5000 out of range [0,3000)"; the learner
+ * is then untouched); idx_host may be reused as soon as the call returns.  n == 0: no-op.  Data-parallel learners are refused. */
+int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host /* [n][B] */, int32_t n);
+
+/* Waits for the dqnhip_update_indexed_n updates enqueued so far and writes the (critic_loss, avg_q) pairs of those not yet
+ * collected, in update order, up to cap; the rest stay collectable (8 bytes each, until collected or dqnhip_destroy).  *n_out: the
+ * count.  The pairs are what the blocking calls return, bit for bit.  If a collected update raised a flag or left a non-finite loss
+ * the pairs are still written and the call fails with dqnhip_read_stats' texts behind "collected update <i>: ", i the zero-based
+ * position within this collection of the first such update (a flag is attributed to the update that raised it; the sticky device
+ * flags are cleared as dqnhip_read_stats clears them).  dqnhip_read_stats after indexed updates still returns the last update's
+ * pair and reports flags; it consumes no pair.
+ * Attribution works on the sticky device flags: an update "raised" the bits the update before it had not left behind.  Two
+ * consequences: (i) a flag raised by another entry point (dqnhip_update_async, ..) between two indexed bursts and never read is
+ * attributed to the first update of the next burst - read the stats of non-indexed updates before mixing them with bursts if
+ * the position matters; (ii) a flag that dqnhip_read_stats has already reported (and cleared on the device) is reported once
+ * more by the dqnhip_collect_stats that hands out the update which raised it: it is a property of that update's pair. */
+int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss /* [cap] */, float* avg_q /* [cap] */,
+                         int32_t cap, int32_t* n_out);
+
 /* Data-parallel form of the same update, cut at its two exchange points:
  *   phase 0: gather .. critic backward      -> critic gradients ready
  *   phase 1: critic clip+Adam(+soft update), actor fwd, critic fwd, critic
@@ -362,7 +389,9 @@ int dqnhip_benchmark(dqnhip_handle h, int32_t warmup, int32_t iterations,
  * UpdateActorCritic(): indices drawn on the host with std::mt19937 + uniform_int_distribution, :501-509, and a
  * blocking (critic_loss, avg_q) per update): wall-clock average over `iterations` calls of dqnhip_update
  * (pipelined = 0), dqnhip_update_pipelined (pipelined = 1) or dqnhip_update_chained with the next call's indices drawn one
- * call ahead (pipelined = 2: what the drop-in's UpdateActorCritic() does) after `warmup` untimed ones. */
+ * call ahead (pipelined = 2: what the drop-in's UpdateActorCritic() does) after `warmup` untimed ones.  pipelined = 3: the
+ * drop-in's -deferred_updates form of the same loop — the same draws, dqnhip_update_indexed_n every sixteen updates, one
+ * dqnhip_collect_stats every 1000 updates and at the end. */
 int dqnhip_benchmark_blocking(dqnhip_handle h, int32_t warmup, int32_t iterations, uint64_t seed,
                               int32_t pipelined, float* avg_ms);
 
@@ -519,7 +548,9 @@ int dqnhip_remove_snapshots(const char* regexp, int32_t min_iter);
 /* Copy a named [B, *] intermediate of the last update to the host:
  * "q_target" [B] (Q'(s',mu'(s'))), "y" [B] (TD target), "q_train" [B],
  * "q_policy" [B], "actor_out" [B,10] (mu(s)), "dq_da" [B,10] (post
- * inverting-gradients), "idx" [B] (as float), "terminal" [B].
+ * inverting-gradients), "idx" [B] (as float), "terminal" [B];
+ * "indexed_graph_launches" [1]: the kernel nodes of the sixteen-update graph dqnhip_update_indexed_n has captured (0: none
+ * captured, or dropped since - sharing, set-up of data parallelism).
  * count = floats the caller's buffer holds; fails if too small. */
 int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
 
