@@ -83,7 +83,7 @@ struct HGemmBatch { HGemm g[kHGemmMax]; int n; int tile_end[kHGemmMax]; };
 struct Db16 { const h16* dyt; int ld; int n_out; int rows; float* db; int row_base; };
 struct Db16Batch { Db16 d[8]; int n; float scale; float* sumsq_partial; /* one slot per 64-column block of k_db16_cols (may be null) */ };
 
-__device__ __forceinline__ int hg_tile_of_block(int bid, int total) {
+__host__ __device__ __forceinline__ int hg_tile_of_block(int bid, int total) {
   // XCD x (= bid % 8) gets a contiguous run of row-major tiles: they share A row panels and
   // sweep all of B, so each XCD's L2 holds its A panels + B once (bijective for any total)
   const int xcd = bid & 7, j = bid >> 3;
@@ -95,7 +95,7 @@ __device__ __forceinline__ int hg_tile_of_block(int bid, int total) {
 // 4096 rows): an XCD's 8 concurrent tiles form a 2 x 4 block of the tile grid, so its L2 pulls 2 A panels + 4 B panels
 // instead of 1 + 8 (PMC, round 3: the grouped wgrad launch fetched 263 MB for ~50 MB of unique operands — 5.8 TB/s of
 // fabric traffic over its 45 us, i.e. it ran AT the fabric rate).  Needs (tiles_m / 2) * (tiles_n / 4) % 8 == 0.
-__device__ __forceinline__ bool hg_tile_2d(int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
+__host__ __device__ __forceinline__ bool hg_tile_2d(int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
   if ((tiles_m & 1) || (tiles_n & 3) || (((tiles_m >> 1) * (tiles_n >> 2)) & 7)) return false;
   const int xcd = bid & 7, j = bid >> 3;
   const int q = ((j >> 3) << 3) + xcd, jj = j & 7, bn = tiles_n >> 2;

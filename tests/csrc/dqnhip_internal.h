@@ -1,6 +1,8 @@
 /*
  * dqnhip_internal.h — test / tuning hooks exported by libdqnhip_test.so (csrc/gemm_bench.hip: the timing harness and the
- * probes; csrc/gemm_forms.hip: dqnhip_test_gemm_form, one launch of a product GEMM form on caller-made buffers).  Not part of
+ * probes; csrc/gemm_forms.hip: dqnhip_test_gemm_form, one launch of a product fp32 GEMM form on caller-made buffers) and by
+ * libdqnhip_test_h.so (csrc/hgemm_forms.hip: dqnhip_test_hgemm_form, one launch of an fp16 launch form — hgemm_nt on each tile,
+ * hgemm_group_db with its riders, k_db16_cols, k_cvt16 — with hgemm.hip.h compiled as the product compiles it).  Not part of
  * the drop-in boundary (include/dqnhip.h); used by tests/ and scripts/gemm_tune.py only.
  */
 #ifndef DQNHIP_INTERNAL_H_
@@ -72,6 +74,53 @@ int dqnhip_test_gemm_form(int32_t form, int32_t n_problems, const dqnhip_test_pr
  * max_abs_err excludes one fp16 rounding of each fp16 result. */
 int dqnhip_test_hgemm(int32_t mode, int32_t tile, int32_t M, int32_t N, int32_t K, int32_t iters,
                       float* avg_us, float* max_abs_err, float* max_ref);
+
+/* ---- dqnhip_test_hgemm_form (csrc/hgemm_forms.hip, libdqnhip_test_h.so): the fp16 launches of the learner, one launch ----
+ * The fp16 analogue of dqnhip_test_gemm_form, in a library of its own: hgemm_forms.hip compiles hgemm.hip.h exactly as
+ * libdqnhip.so does (neither HG_WITH_CT16 nor HG_CLOCKPROBE), gemm_bench.hip compiles it with both, and the two bodies behind
+ * the same hgemm_nt<...> symbols must not meet in one shared object.  The caller (tests/test_gpu_hgemm_forms.py with
+ * tests/hgemm_ref.py) makes every buffer, guards and pads included; the entry validates, uploads every buffer whole, calls
+ * hgemm_prepare_all(), launches ONCE through the product's launcher, synchronises and downloads every output buffer whole. */
+typedef struct dqnhip_test_buf16 {
+  uint16_t* host;    /* fp16 bit patterns; null: operand absent */
+  int64_t count;     /* halves in it */
+  int64_t offset;    /* half index of the operand's element [0][0] */
+} dqnhip_test_buf16;
+/* One HGemm (hgemm.hip.h): C[m][n] = sum_k Aop(m,k) Bop(n,k); ta / tb = 1: the operand is stored [K][M] resp. [K][N]. */
+typedef struct dqnhip_test_hproblem {
+  int32_t M, N, K, lda, ldb, ta, tb, ldc16, ldc32, n_valid32, relu, ldm, ldcs16, reserved;
+  float scale32, seed_scale;
+  dqnhip_test_buf16 A, B, mask;                 /* inputs */
+  dqnhip_test_buf bias, seed_w;                 /* inputs */
+  dqnhip_test_buf16 C16, CS16;                  /* in/out: arrive prefilled with the caller's sentinel */
+  dqnhip_test_buf C32, sumsq_partial;           /* in/out (sumsq_partial: one slot per tile of the problem) */
+} dqnhip_test_hproblem;
+typedef struct dqnhip_test_hdb {                /* one Db16: db[n] = scale * sum_b dy[b][n] */
+  dqnhip_test_buf16 dy; int32_t ld, n_out, rows, reserved; dqnhip_test_buf db;
+} dqnhip_test_hdb;
+typedef struct dqnhip_test_hcvt {               /* one Cvt16 without a transposed output, as the learner calls cvt16_add */
+  dqnhip_test_buf src; int32_t ld_src, rows, cols, ld16; float scale; int32_t reserved; dqnhip_test_buf16 dst;
+} dqnhip_test_hcvt;
+typedef struct dqnhip_test_hriders {
+  int32_t n_db; float db_scale; dqnhip_test_hdb db[8]; dqnhip_test_buf db_sumsq;     /* Db16Batch (db_sumsq: one slot per 64-column block) */
+  int32_t nh, lddy, H, rows, blocks, reserved;                                       /* HeadWsum; nh 0: none */
+  dqnhip_test_buf dy; dqnhip_test_buf16 X16; dqnhip_test_buf dW, hdb, partial;
+  int32_t n_cvt, reserved2; dqnhip_test_hcvt cvt[8];                                 /* Cvt16Batch */
+} dqnhip_test_hriders;
+enum dqnhip_test_hform {
+  DQNHIP_HFORM_NT_BIG_FWD = 0, DQNHIP_HFORM_NT_BIG_DGRAD = 1, DQNHIP_HFORM_NT_BIG_WGRAD = 2,        /* hgemm_launch_batch(.., 1) */
+  DQNHIP_HFORM_NT_SMALL_FWD = 3, DQNHIP_HFORM_NT_SMALL_DGRAD = 4, DQNHIP_HFORM_NT_SMALL_WGRAD = 5,  /* hgemm_launch_batch(.., 2) */
+  DQNHIP_HFORM_NT_SMALL_BWD = 6,                                     /* probs[0] dgrad, probs[1] wgrad, force 2 */
+  DQNHIP_HFORM_NT_HUGE_FWD = 7,                                      /* hgemm_launch_batch(.., 3) */
+  DQNHIP_HFORM_GROUP_DB_BIG = 8, DQNHIP_HFORM_GROUP_DB_SMALL = 9,    /* hgemm_group_db_launch: 1..4 wgrads + Db16Batch + HeadWsum */
+  DQNHIP_HFORM_DB16_COLS = 10,                                       /* k_db16_cols<0>: riders->db only, no problems */
+  DQNHIP_HFORM_CVT16 = 11,                                           /* cvt16_add + cvt16_launch: riders->cvt only, no problems */
+  DQNHIP_HFORM_COUNT = 12
+};
+/* Returns 0 on success; 1, before anything is uploaded or launched, on an invalid call (form, counts, tile multiples, K, an
+ * alignment, a leading dimension, an orientation that does not belong to the form, an operand outside its buffer, riders the form
+ * does not take); 2 on a HIP error.  riders may be null (none). */
+int dqnhip_test_hgemm_form(int32_t form, int32_t n_problems, const dqnhip_test_hproblem* problems, const dqnhip_test_hriders* riders);
 
 /* One tower layer's backward without transposed panels (see gemm_bench.hip): dgrad with the weight operand read
  * reduction-major, wgrad with both operands reduction-major, each alone and both in one launch; us[3] = the three

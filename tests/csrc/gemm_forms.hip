@@ -3,7 +3,9 @@
 // this entry is a thin host-visible door to the product's own launchers: every operand may sit at an offset inside a wider,
 // guard-banded buffer with a leading dimension larger than its width, and every in/out buffer comes back whole, so that the
 // Python side (tests/gemm_ref.py) can judge each element against a float64 reference and check that nothing outside the
-// tiles was touched.  Test infrastructure, not on the hot path.
+// tiles was touched.  Test infrastructure, not on the hot path.  The kernel-test entries: dqnhip_test_gemm / dqnhip_test_hgemm /
+// dqnhip_test_hgemm_backward (gemm_bench.hip: device-side reference, one figure), dqnhip_test_gemm_form (here: the fp32 tower's
+// forms) and dqnhip_test_hgemm_form (hgemm_forms.hip, in libdqnhip_test_h.so: the fp16 learner's launches).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
