@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "small_kernels.hip.h"
+#include "update_bodies.hip.h"     // philox_u32; Ring, DevState (learner_args.hip.h)
 
 namespace dqnhip {
 
@@ -278,6 +278,8 @@ __device__ __forceinline__ void env_flush_block(const EnvDev& e, const Ring& rin
   if (s_last) env_commit_body(e, ring, const_cast<DevState*>(st));
 }
 static __global__ __launch_bounds__(256) void k_env_flush(EnvDev e, Ring ring, const DevState* st, double gamma) {
+  // (every `extern __shared__` of one name in a translation unit is ONE symbol, and the first declaration sets its alignment:
+  // k_head_bwd / k_head_bwd_big, head_kernels.hip.h, also call theirs `sm` and ask for 16 bytes — keep the two headers in separate units)
   extern __shared__ float sm[];          // [T] mc labels
   env_flush_block(e, ring, st, gamma, blockIdx.x, gridDim.x, sm);
 }

@@ -1,5 +1,7 @@
-// gemm_common.hip.h — types shared by the fp32 MFMA GEMM kernels of the learner
-// (gemm_direct.hip.h) and the head / optimiser kernels (small_kernels.hip.h).
+// gemm_common.hip.h — the bottom of the argument layer (learner_args.hip.h has the map of the kernel headers): the GEMM problem
+// descriptions, where a launch goes (LaunchOn / launch), and the few device helpers every kernel group uses (leaky ReLU, the wave
+// sum, the tails block).  Shared by the fp32 MFMA GEMM family (gemm_bodies.hip.h, gemm_direct.hip.h), the fp16 family (hgemm.hip.h)
+// and the head / optimiser / replay kernels.
 //
 // Every tower GEMM computes C[q][p] = sum_k Pop(p,k) * Qop(q,k) with `p` the contiguous
 // output dimension; the three modes replace the Caffe InnerProduct forward/backward GEMMs
@@ -132,7 +134,7 @@ __device__ __forceinline__ float wave_sum64(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-// sticky device flags (DevState::flags, small_kernels.hip.h)
+// sticky device flags (DevState::flags, learner_args.hip.h)
 constexpr int kFlagTarget = 1;     // a TD target of the last update(s) was not finite
 constexpr int kFlagGradNorm = 2;   // a gradient L2 norm was not finite: that clip+Adam step was skipped
 

@@ -1,0 +1,617 @@
+// head_kernels.hip.h — the head layers' training kernels, launched by learner.hip: TD target + Euclidean loss (k_head_q_train, or
+// inside the critic's top-layer dgrad launch: k_dgrad_qtrain), the heads' backward with the inverting gradients (k_head_bwd,
+// k_head_bwd_big + k_head_wred, k_dqda_head_bwd).  The heads' forward: head_fwd_kernels.hip.h.
+#pragma once
+#include "gemm_direct.hip.h"
+#include "update_bodies.hip.h"
+
+namespace dqnhip {
+
+// Both critic heads of the training step in one launch: q' = q_values(critic_target tower
+// top), q = q_values(critic tower top), then the TD target (src/dqn.cpp:892-900, doubles where
+// the reference has them) and the EuclideanLoss diff.  One wave per row.
+static __global__ __launch_bounds__(256) void k_head_q_train(HeadTrainArgs a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  __shared__ float s_part[4];
+  float at = 0.0f, ao = 0.0f;
+  // the row's scalars and the two biases: requested before the dot products, used after the reduction
+  float bt0 = 0.0f, b0 = 0.0f, r = 0.0f, mcv = 0.0f, tm = 0.0f;
+  if (row < a.rows && lane == 0) { bt0 = a.bt[0]; b0 = a.b[0]; r = a.reward[row]; mcv = a.mc[row]; tm = a.term[row]; }
+  if (row < a.rows) {
+    const size_t x0 = (size_t)row * a.H;
+    auto dots = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 v0 = head_ld4t<decltype(tag)::value>(a.Xt, a.Xt16, x0 + k), w0 = *reinterpret_cast<const f32x4*>(a.Wt + k);
+        const f32x4 v1 = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), w1 = *reinterpret_cast<const f32x4*>(a.W + k);
+        at = fmaf(v0.x, w0.x, at); at = fmaf(v0.y, w0.y, at); at = fmaf(v0.z, w0.z, at); at = fmaf(v0.w, w0.w, at);
+        ao = fmaf(v1.x, w1.x, ao); ao = fmaf(v1.y, w1.y, ao); ao = fmaf(v1.z, w1.z, ao); ao = fmaf(v1.w, w1.w, ao);
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, dots);
+  }
+  at = wave_sum64(at); ao = wave_sum64(ao);
+  float d2 = 0.0f, dq_row = 0.0f;
+  if (row < a.rows && lane == 0) {
+    const float qt = at + bt0, q = ao + b0;
+    a.q_target[row] = qt; a.q[row] = q;
+    const float off_policy = tm != 0.0f ? r : (float)((double)r + a.gamma * (double)qt);
+    const float target = (float)(a.beta * (double)mcv + (1 - a.beta) * (double)off_policy);
+    a.y[row] = target;
+    if (!isfinite(target)) atomicOr(&a.st->flags, kFlagTarget);   // CHECK(std::isfinite(target)), src/dqn.cpp:898
+    const float d = q - target;
+    dq_row = a.inv_batch * d;
+    a.dq[row] = dq_row;
+    d2 = d * d;
+  }
+  if ((a.dZ != nullptr || a.dZ16 != nullptr) && row < a.rows) {     // (wave-uniform condition)
+    const float dqv = __shfl(dq_row, 0, 64);
+    const size_t x0 = (size_t)row * a.H;
+    auto seed = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 xv = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), wv = *reinterpret_cast<const f32x4*>(a.W + k);
+        // k_head_bwd<1>'s arithmetic: s0 = fma(d, w, 0) = d * w, then * lrelu'(x)
+        f32x4 dz;
+        dz.x = (dqv * wv.x) * lrelu_mask(xv.x); dz.y = (dqv * wv.y) * lrelu_mask(xv.y);
+        dz.z = (dqv * wv.z) * lrelu_mask(xv.z); dz.w = (dqv * wv.w) * lrelu_mask(xv.w);
+        if constexpr (decltype(tag)::value)
+          *reinterpret_cast<head_h4*>(a.dZ16 + x0 + k) = head_h4{(_Float16)(dz.x * a.scale16), (_Float16)(dz.y * a.scale16), (_Float16)(dz.z * a.scale16), (_Float16)(dz.w * a.scale16)};
+        else
+          *reinterpret_cast<f32x4*>(a.dZ + x0 + k) = dz;
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, seed);
+  }
+  if (lane == 0) s_part[wave] = d2;
+  __syncthreads();
+  if (threadIdx.x == 0) a.loss_partial[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
+// ---- Step(1)'s head arithmetic inside the critic's first backward launch (round 5) -------------------------------------------
+// k_head_q_train sits between the critics' last forward launch and the critic's top-layer dgrad: a 4.9-us launch-floor link
+// whose output the dgrad needs only as a PER-ROW SCALAR.  dZ_L[r][n] = (dq_r w_n) lrelu'(x_rn) = (-dq_r) U[r][n] with
+// U = (-w) lrelu'(x), which does not depend on q: the online critic's top forward layer leaves U in its epilogue
+// (GemmProblem::seed_w, as the dq = -1 pass already does), the dgrad runs on U, and
+//     dZ_{L-1}[r][j] = ((sum_n U[r][n] W[n][j]) * (-dq_r)) * lrelu'(x_{L-1}[r][j])
+// takes the scalar in its epilogue.  The two head dot products arrive in 16-column pieces from the critics' top forward layers
+// (GemmProblem::dot_w: the finished activations are in that epilogue's registers anyway).  Each of the workgroup's four waves
+// requests the pieces of four of the tile's 16 rows once its operand pipeline is primed (2 KB per workgroup), and after its last
+// MFMA sums them, forms q', q, the TD target and dq (k_head_q_train's arithmetic from there on), publishes -dq_r in LDS before
+// the body's barrier; afterwards the workgroup writes its 64-column slices of dZ_L (the next launch's wgrad reads them).  The
+// workgroups of tile column 0 write the per-row outputs.  q', q and dZ_{L-1} differ from the two-launch form by fp32 round-off
+// only (the dot product is summed in another fixed order; the scalar is applied after the reduction instead of before):
+// DQNHIP_TUNE_SEPARATE_Q_TRAIN restores the two launches.
+// Measured on the way (profiles/r05_dgrad_qtrain.txt): a FIFTH wave per workgroup reading the tower tops itself — 17.4 us against
+// 8.3 + 4.8 for the two launches (it shares a SIMD and the CU's load path with an MFMA wave); the four MFMA waves reading their
+// rows of the tower tops — 12.1 us (the 16 workgroups of a tile row each re-read the same 128 KB: +50% on an L2-bound kernel).
+struct QTrainHook {
+  const HeadTrainArgs& a; float* s_scale; float* s_dq; int q0; bool owner;
+  float v0[4], v1[4];        // rows 4 wave + j: piece `lane` of the target / online head dot product (H / 16 <= 64 pieces)
+  float rw[4], mcv[4], tm[4], bt0, b0;
+  f32x4 xv, wv;              // this thread's piece of the workgroup's first dZ_L slice (row threadIdx.x / 16, 4 columns)
+  int c_first;
+  __device__ __forceinline__ QTrainHook(const HeadTrainArgs& a_, float* sc, float* sd, int q0_, int tile_p) : a(a_), s_scale(sc), s_dq(sd), q0(q0_), owner(tile_p == 0), c_first(tile_p * 64) {}
+  __device__ __forceinline__ void after_prologue() {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int np = a.H >> 4;
+    const int pc = lane < np ? lane : 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t x0 = (size_t)(q0 + wave * 4 + j) * np + pc;
+      v0[j] = a.pdt[x0]; v1[j] = a.pd[x0];
+      const int row = q0 + wave * 4 + j;
+      rw[j] = a.reward[row]; mcv[j] = a.mc[row]; tm[j] = a.term[row];
+    }
+    bt0 = a.bt[0]; b0 = a.b[0];
+    if (c_first < a.H) {
+      const int rr = threadIdx.x >> 4, c = c_first + ((threadIdx.x & 15) << 2);
+      xv = *reinterpret_cast<const f32x4*>(a.X + (size_t)(q0 + rr) * a.H + c); wv = *reinterpret_cast<const f32x4*>(a.W + c);
+    }
+  }
+  __device__ __forceinline__ void before_park() {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool in = lane < (a.H >> 4);
+    float d2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int rr = wave * 4 + j, row = q0 + rr;
+      const float at = wave_sum64(in ? v0[j] : 0.0f), ao = wave_sum64(in ? v1[j] : 0.0f);
+      const float r = rw[j];
+      const float qt = at + bt0, q = ao + b0;
+      const float off_policy = tm[j] != 0.0f ? r : (float)((double)r + a.gamma * (double)qt);      // src/dqn.cpp:893-900
+      const float target = (float)(a.beta * (double)mcv[j] + (1 - a.beta) * (double)off_policy);
+      const float d = q - target;
+      const float dq_row = a.inv_batch * d;
+      d2[j] = d * d;
+      if (lane == 0) {
+        s_scale[rr] = -dq_row; s_dq[rr] = dq_row;
+        if (owner) {
+          a.q_target[row] = qt; a.q[row] = q; a.y[row] = target; a.dq[row] = dq_row;
+          if (!isfinite(target)) atomicOr(&a.st->flags, kFlagTarget);   // CHECK(std::isfinite(target)), src/dqn.cpp:898
+        }
+      }
+    }
+    // k_head_q_train's partial of its block of four rows (one row per wave there: ((w0 + w1) + w2) + w3)
+    if (owner && lane == 0) a.loss_partial[(q0 >> 2) + wave] = ((d2[0] + d2[1]) + d2[2]) + d2[3];
+  }
+};
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dgrad_qtrain(const GemmArgs<1> args, const HeadTrainArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float s_scale[16], s_dq[16];
+  int tile_p, tile_q;
+  HotArgs<1> r;
+  const int b = request_args(args, r, (int)blockIdx.x);
+  const GemmProblem pr = problem_at<0>(args, r);
+  tile_of_problem(pr, b, tile_p, tile_q);
+  const int q0 = tile_q * 16;
+  QTrainHook hook(a, s_scale, s_dq, q0, tile_p);
+  dgrad_lds_body<1, 1, true, QTrainHook>(pr, tile_p, tile_q, smem, s_scale, hook);
+  // this workgroup's slices of dZ_L: columns [64 tile_p, +64) and every tiles_p-th slice after it, 16 rows (one float4 per thread);
+  // s_dq was published before the body's barrier
+  for (int c0 = tile_p * 64; c0 < a.H; c0 += pr.tiles_p * 64) {
+    const int rr = threadIdx.x >> 4, c = c0 + ((threadIdx.x & 15) << 2);
+    const size_t x0 = (size_t)(q0 + rr) * a.H + c;
+    f32x4 xv = hook.xv, wv = hook.wv;       // (the first slice's operands were requested under the main loop)
+    if (c0 != tile_p * 64) { xv = *reinterpret_cast<const f32x4*>(a.X + x0); wv = *reinterpret_cast<const f32x4*>(a.W + c); }
+    const float dqv = s_dq[rr];
+    f32x4 dz;
+    dz.x = (dqv * wv.x) * lrelu_mask(xv.x); dz.y = (dqv * wv.y) * lrelu_mask(xv.y);
+    dz.z = (dqv * wv.z) * lrelu_mask(xv.z); dz.w = (dqv * wv.w) * lrelu_mask(xv.w);
+    *reinterpret_cast<f32x4*>(a.dZ + x0) = dz;
+  }
+}
+inline hipError_t dgrad_qtrain_launch(GemmBatch& batch, const HeadTrainArgs& a, const LaunchOn& on) {
+  batch.n = 1;
+  tile_batch(batch, 64, 16);
+  GemmArgs<1> args;
+  if (!pack_args(batch, args)) return hipErrorInvalidValue;
+  return launch(on, k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), dgrad_lds_bytes<1, 1>(), args, a);
+}
+
+// Fused head backward: in one pass over the tower top X4[rows][H]
+//   (actor only) inverting gradients (src/dqn.cpp:924-957) on the critic's input-gradient
+//                columns -> dYh[m][0..9]
+//   dZ4[m][k]  = (sum_j dYh[m][j] Wh[j][k]) * lrelu'(X4[m][k])       (head dgrad + ReLU bwd)
+//   dWh[j][k]  = sum_m dYh[m][j] X4[m][k] ;  dbh[j] = sum_m dYh[m][j]  (head wgrad)
+//   + one sum-of-squares partial per block.
+// Block = 64 columns x 16 row groups (1024 threads); row groups are added in fixed order.
+// Replaces three launches (invert, head dgrad, head wgrad) and 16x the parallelism of the
+// old column-strip wgrad.
+// Grid = (H/64 column blocks) x (RC row chunks); block = 64 columns x 16 row groups.  Each block
+// writes its dZ rows directly and a partial dW slab; the LAST block to arrive for a column block
+// (agent-scope release -> ticket -> acquire, guide G16) adds the RC slabs in fixed order, so the
+// result does not depend on which block that is.
+// cross-block hand-off words: coherent at agent scope without a fence on either side
+__device__ __forceinline__ void slab_st(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float slab_ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <int NH>
+__global__ __launch_bounds__(1024) void k_head_bwd(HeadBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int RC = a.rc_blocks > 0 ? a.rc_blocks : gridDim.y, rc = blockIdx.y, nkb = gridDim.x;
+  if (a.q_out != nullptr && rc >= RC) {                // rider blocks: one wave per row, k-strips of float4
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = (((int)blockIdx.y - RC) * (int)gridDim.x + (int)blockIdx.x) * 16 + wave;
+    if (row >= a.rows) return;
+    const float* rW = a.qr_W ? a.qr_W : a.W; const float* rX = a.qr_W ? a.qr_X4 : a.X4;
+    const _Float16* rX16 = a.qr_W ? a.qr_X416 : a.X416; const int rH = a.qr_W ? a.qr_H : a.H;
+    const size_t x0 = (size_t)row * rH;
+    float acc = 0.0f;
+    auto dots = [&](auto tag) {
+      for (int k = lane * 4; k < rH; k += 256) {
+        const f32x4 xv = head_ld4t<decltype(tag)::value>(rX, rX16, x0 + k), wv = *reinterpret_cast<const f32x4*>(rW + k);
+        acc = fmaf(xv.x, wv.x, acc); acc = fmaf(xv.y, wv.y, acc); acc = fmaf(xv.z, wv.z, acc); acc = fmaf(xv.w, wv.w, acc);
+      }
+    };
+    HEAD_DISPATCH(rX16 != nullptr, dots);
+    acc = wave_sum64(acc);
+    if (lane == 0) { const float v = acc + a.q_bias[0]; a.q_out[row] = v; a.qsum_partial[row] = (double)v; }
+    return;
+  }
+  const int rows_c = (a.rows + RC - 1) / RC;           // rows of this chunk
+  const int r0 = rc * rows_c, r1 = min(a.rows, r0 + rows_c);
+  float* s_dy = sm;                                    // [rows_c][NH]
+  float* s_acc = sm + rows_c * NH;                     // [16][NH][64]
+  __shared__ int s_last;
+  const int tid = threadIdx.x;
+  const bool want_w = a.dW != nullptr;
+  const int kc = tid & 63, rg = tid >> 6;              // 16 row groups
+  const int k = blockIdx.x * 64 + kc;
+  const int per = (r1 - r0 + 15) / 16;
+  const int m0 = r0 + rg * per, m1 = min(r1, m0 + per);
+  // this thread's head weights and its first four tower-top values go out BEFORE the head diffs are staged: neither
+  // depends on them, and the staging (two dependent loads + the inverting-gradients arithmetic + a barrier) is a chain
+  // of its own.  Rows are then taken four at a time, four independent loads in flight, instead of one load per iteration.
+  constexpr int RB = 4;
+  float w[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) w[j] = a.W[(size_t)j * a.H + k];
+  float xpre[RB];
+  auto ldx = [&](int m) -> float { return a.X416 != nullptr ? (float)a.X416[(size_t)m * a.H + k] : a.X4[(size_t)m * a.H + k]; };
+#pragma unroll
+  for (int u = 0; u < RB; ++u) xpre[u] = (m0 + u < m1) ? ldx(m0 + u) : 0.0f;
+  // ---- head diffs of this chunk's rows into LDS
+  for (int i = tid; i < (r1 - r0) * NH; i += 1024) {
+    const int m = r0 + i / NH, j = i % NH;
+    float d;
+    if constexpr (NH == kNO) {
+      d = a.dXc[(size_t)m * a.ldx + a.S + j];
+      const float out = a.aout16[(size_t)m * kAP + j];
+      float mn, mx;
+      if (j < kNA) { mn = -1.0f; mx = 1.0f; }
+      else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+      if (d < 0) d *= (mx - out) / (mx - mn);
+      else if (d > 0) d *= (out - mn) / (mx - mn);
+      if (blockIdx.x == 0) a.dA16[(size_t)m * kAP + j] = d;
+    } else {
+      d = a.dyh ? a.dyh[(size_t)m * a.lddy + j] : -1.0f;
+    }
+    s_dy[i] = d;
+  }
+  __syncthreads();
+  float acc[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) acc[j] = 0.0f;
+  auto rows_loop = [&](auto tag) {
+  for (int mb = m0; mb < m1; mb += RB) {
+    float xb[RB];
+#pragma unroll
+    for (int u = 0; u < RB; ++u)
+      xb[u] = (mb == m0) ? xpre[u] : ((mb + u < m1) ? head_ld1t<decltype(tag)::value>(a.X4, a.X416, (size_t)(mb + u) * a.H + k) : 0.0f);
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+      const int m = mb + u;
+      if (m >= m1) break;
+      const float xv = xb[u];
+      float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+      for (int j = 0; j < NH; ++j) {
+        const float d = s_dy[(m - r0) * NH + j];
+        // Split layer: action_layer's and actionpara_layer's bottom diffs are
+        // formed separately and added
+        if (NH == kNO && j >= kNA) s1 = fmaf(d, w[j], s1); else s0 = fmaf(d, w[j], s0);
+        acc[j] = fmaf(d, xv, acc[j]);
+      }
+      if (NH == kNO) s0 += s1;
+      const float dz = s0 * lrelu_mask(xv);
+      if (a.dZ != nullptr) a.dZ[(size_t)m * a.H + k] = dz;
+      if (a.dZ16 != nullptr) a.dZ16[(size_t)m * a.H + k] = (_Float16)(dz * a.scale16);
+    }
+  }
+  };
+  HEAD_DISPATCH(a.X416 != nullptr, rows_loop);
+  if (!want_w) return;
+#pragma unroll
+  for (int j = 0; j < NH; ++j) s_acc[(rg * NH + j) * 64 + kc] = acc[j];
+  __syncthreads();
+  // this chunk's partial: row groups added in fixed order
+  float* my_slab = a.slab + ((size_t)rc * nkb + blockIdx.x) * NH * 64;
+  if (rg < NH) {                                      // wave j folds head j (NH <= 16 waves)
+    const int j = rg;
+    float v = 0.0f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) v += s_acc[(g * NH + j) * 64 + kc];
+    slab_st(&my_slab[j * 64 + kc], v);
+  }
+  if (rg == NH && blockIdx.x == 0 && kc < NH) {       // partial bias gradient of this chunk (a spare wave)
+    float v = 0.0f;
+    for (int m = 0; m < r1 - r0; ++m) v += s_dy[m * NH + kc];
+    slab_st(&a.slab[(size_t)RC * nkb * NH * 64 + rc * 16 + kc], v);
+  }
+  // publish the slab, take a ticket; the last arriver reduces (placement independent).  The slab travels as
+  // agent-scope (sc1: write-through / L2-bypassing) stores and loads, drained before the ticket — not plain stores +
+  // a release fence (the fence writes back the whole L2, this launch's dZ rows included, once per block, and the
+  // last arriver's acquire invalidates it again).  Measured alternatives at 256 rows, same-box A/B: one row chunk on
+  // 32-column blocks (no counter): no gain; the gradients from an extra grid row of blocks that walk all rows: -0.8 %.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    // The hand-off is MI355X_MICROARCH.md's "handoff-flag" form for gfx950: write-through (sc1) payload stores, the storing
+    // waves' `s_waitcnt vmcnt(0)` above, a barrier, then a relaxed agent-scope counter; the last arriver reads the slabs with
+    // sc1 (L1-bypassing) loads.  No release / acquire fence: an agent-scope release writes the whole L2 back — this launch's
+    // dZ rows included — once per block (measured round 4 with ACQ_REL here: k_head_bwd<10> 9.6 -> 10.7 us, <1> 6.2 -> 6.8
+    // at 512 fp16 rows).  That is an ISA-level guarantee, not one of the HIP memory model, so it is pinned by
+    // a stress test that checks every word of the reduced gradient under uneven load from a second stream
+    // (tests/test_gpu_head_handoff.py); shapes whose head gradients ride in a carrier launch never come here.
+    const int t = __hip_atomic_fetch_add(a.ticket + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (t == RC - 1);
+  }
+  __syncthreads();
+  if (!s_last) return;
+  float ssq = 0.0f;
+  if (rg < NH) {
+    const int j = rg;
+    float v = 0.0f;
+    for (int c = 0; c < RC; ++c) v += slab_ld(&a.slab[((size_t)c * nkb + blockIdx.x) * NH * 64 + j * 64 + kc]);
+    a.dW[(size_t)j * a.H + k] = v;
+    ssq = v * v;
+  } else if (rg == NH && blockIdx.x == 0 && kc < NH) {
+    float v = 0.0f;
+    for (int c = 0; c < RC; ++c) v += slab_ld(&a.slab[(size_t)RC * nkb * NH * 64 + c * 16 + kc]);
+    a.db[kc] = v;
+    ssq = v * v;
+  }
+  ssq = wave_sum64(ssq);
+  if (kc == 0) s_acc[rg] = ssq;                        // s_acc is free again
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.0f;
+#pragma unroll
+    for (int g = 0; g <= NH; ++g) t += s_acc[g];        // heads in order, then the bias wave
+    if (a.partial != nullptr) a.partial[blockIdx.x] = t;
+    a.ticket[blockIdx.x] = 0;                          // re-arm for the next launch
+  }
+}
+
+// ---- critic dQ/da + inverting gradients + actor heads' backward in ONE launch (round 5) ----------------------------------------
+// The critic's BackwardFrom(q_values) chain (src/dqn.cpp:918-923) ends in the first layer's input gradient, of which only the ten
+// action columns are consumed; the inverting-gradients pass (:924-957) and the actor heads' backward (BackwardFrom(actionpara_layer),
+// :960-963: head dgrad + the tower top's ReLU') follow.  They used to be two launch-floor launches (gemm_dgrad_narrow_qrider:
+// 32 tiles of 16 x 16 + the q riders, 6.2 us; k_head_bwd<10>: 4.8 us).  Here workgroup (row tile t, column chunk c) recomputes
+// the 16 x 16 tile of dQ/da for its 16 rows — a 1024-deep reduction on four waves, 0.1 us of MFMA: recomputing it in each of the
+// H / 256 column chunks costs less than handing it across a kernel boundary — inverts it, and writes its 16 x 256 piece of the
+// actor's tower-top gradient.  Same arithmetic in the same order as the two kernels it replaces (bit-identical: the narrow
+// tile's values do not depend on which columns a workgroup owns, the head part is k_head_bwd's loop).  The q(s, mu(s)) riders
+// come last in the grid, as before.  The head's own dW / db are the wgrad-tail launch's riders (HeadWgradRider).
+template <bool F16 = false>
+__global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, const QHeadRider rider) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // the narrow dgrad's parking area (4 waves x 64 lanes x 16 B)
+  __shared__ float s_d[16][17];
+  __shared__ float s_dy[16 * kNO];
+  // what routes the workgroup, what the head part's first loads need and the narrow tile's operands: ONE round of scalar loads
+  // (request_args, gemm_bodies.hip.h, has the reasoning; left alone: the tile count, then the head's pointers, then the tile's)
+  int blk = (int)blockIdx.x;
+  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred));
+  else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
+  const int tiles = a.row_tiles * ((a.H + 255) >> 8);
+  if (blk >= tiles) { q_head_rider(rider, blk - tiles); return; }
+  const int rt = blk % a.row_tiles, cc = blk / a.row_tiles;
+  const int tid = threadIdx.x, q0 = rt * 16;
+  // (round 6: any tower-top width — the reference's own tower ends in 128 units; threads beyond it keep column H - 1's loads, take
+  // part in the tile and the barriers, and store nothing)
+  const bool live = (cc << 8) + tid < a.H;
+  const int k = live ? (cc << 8) + tid : a.H - 1;
+  // everything the head part needs that does not depend on dQ/da goes out first: this thread's ten head weights, its column of
+  // the 16 tower-top rows, and (160 threads) one output of mu(s)
+  float wh[kNO], xv[16];
+#pragma unroll
+  for (int j = 0; j < kNO; ++j) wh[j] = a.W[(size_t)j * a.H + k];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) xv[r] = F16 ? (float)a.X416[(size_t)(q0 + r) * a.H + k] : a.X4[(size_t)(q0 + r) * a.H + k];
+  float out = 0.0f;
+  if (tid < 16 * kNO) out = a.aout16[(size_t)(q0 + tid / kNO) * kAP + tid % kNO];
+  f32x4 v;
+  if constexpr (F16) { v = dgrad_narrow_tile16<8>(a.t16, rt, smem); v.x *= a.inv_ls; v.y *= a.inv_ls; v.z *= a.inv_ls; v.w *= a.inv_ls; }
+  else v = dgrad_narrow_tile<8>(a.pr, 0, rt, smem);
+  if (tid < 64) {                          // wave 0 holds the tile: lane (li, lg), register r = dX[row q0 + li][column 4 lg + r]
+    const int li = tid & 15, lg = tid >> 4;
+    s_d[li][(lg << 2) + 0] = v.x; s_d[li][(lg << 2) + 1] = v.y; s_d[li][(lg << 2) + 2] = v.z; s_d[li][(lg << 2) + 3] = v.w;
+  }
+  __syncthreads();
+  if (tid < 16 * kNO) {                    // inverting gradients (k_head_bwd<10>'s staging loop)
+    const int r = tid / kNO, j = tid % kNO;
+    float d = s_d[r][j];
+    float mn, mx;
+    if (j < kNA) { mn = -1.0f; mx = 1.0f; }
+    else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+    if (d < 0) d *= (mx - out) / (mx - mn);
+    else if (d > 0) d *= (out - mn) / (mx - mn);
+    if (cc == 0) a.dA16[(size_t)(q0 + r) * kAP + j] = d;
+    s_dy[tid] = d;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kNO; ++j) {
+      const float d = s_dy[r * kNO + j];
+      // Split layer: action_layer's and actionpara_layer's bottom diffs are formed separately and added
+      if (j >= kNA) s1 = fmaf(d, wh[j], s1); else s0 = fmaf(d, wh[j], s0);
+    }
+    s0 += s1;
+    const float dz = s0 * lrelu_mask(xv[r]);
+    if (!live) continue;
+    if constexpr (F16) a.dZ16[(size_t)(q0 + r) * a.H + k] = (_Float16)(dz * a.scale16);
+    else a.dZ[(size_t)(q0 + r) * a.H + k] = dz;
+  }
+}
+inline hipError_t dqda_head_bwd_launch(DqdaHeadArgs& a, const QHeadRider& rider, const LaunchOn& on) {
+  a.row_tiles = a.rows / 16;
+  a.pr.tiles_p = 1; a.pr.tiles_q = a.row_tiles; a.pr.tile_base = 0;
+  const dim3 grid(a.row_tiles * ((a.H + 255) / 256) + rider.blocks);
+  if (a.dZ16 != nullptr) return launch(on, k_dqda_head_bwd<true>, grid, dim3(256), kNarrowDgradLds, a, rider);
+  return launch(on, k_dqda_head_bwd<false>, grid, dim3(256), kNarrowDgradLds, a, rider);
+}
+
+// ---- head backward for large minibatches (rows >= 1024) -------------------------------------
+// Same arithmetic as k_head_bwd, re-tiled for bandwidth: block = 64 rows x 256 columns, wave = 16
+// rows, lane = 4 consecutive columns (16-B loads / stores of X4 and dZ).  Per-chunk partial head
+// gradients go to a slab [rows/64][NH][H]; k_head_wred adds the chunks in index order.  In fp16
+// mode the tower-top gradient is written directly as the scaled fp16 panel, replacing the fp32 panel +
+// conversion pass.
+template <int NH>
+__global__ __launch_bounds__(256) void k_head_bwd_big(HeadBwdBigArgs b) {
+  typedef __attribute__((ext_vector_type(4))) _Float16 h4;
+  const HeadBwdArgs& a = b.a;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* s_dy = sm;                                    // [64][NH]
+  float* s_red = sm + 64 * NH;                         // [4][NH][256]
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  if (b.chunks > 0 && (int)blockIdx.x >= b.chunks) {
+    // (rider: the q head of HeadBwdArgs::qr_* when given — the fp16 learner's critic(s, mu(s)) head in the ACTOR heads' launch —
+    // else this launch's own head, the dq = -1 launch)
+    const float* rW = a.qr_W ? a.qr_W : a.W; const float* rX4 = a.qr_W ? a.qr_X4 : a.X4;
+    const _Float16* rX416 = a.qr_W ? a.qr_X416 : a.X416; const int rH = a.qr_W ? a.qr_H : a.H;
+    // one wave per row, four rows of the wave in flight at once (16 x 16-B loads per lane before the first use:
+    // with one row at a time the rider was a chain of exposed memory latencies, 9 us at 4096 rows)
+    const int nwave = ((int)gridDim.x - b.chunks) * (int)gridDim.y * 4;
+    const int wv = (((int)blockIdx.x - b.chunks) * (int)gridDim.y + (int)blockIdx.y) * 4 + w;
+    const bool hoist = rH <= 1024;
+    f32x4 wreg[4];
+    if (hoist) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { const int k = lane * 4 + 256 * t; wreg[t] = k < rH ? *reinterpret_cast<const f32x4*>(rW + k) : f32x4{0.f, 0.f, 0.f, 0.f}; }
+    }
+    for (int r0 = wv * 4; r0 < a.rows; r0 += nwave * 4) {
+      if (hoist) {
+        f32x4 xr[4][4];
+        if (rX416 != nullptr) {
+          head_h4 hr[4][4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const int k = lane * 4 + 256 * t;
+              hr[j][t] = (r0 + j < a.rows && k < rH) ? *reinterpret_cast<const head_h4*>(rX416 + (size_t)(r0 + j) * rH + k) : head_h4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+            }
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) xr[j][t] = f32x4{(float)hr[j][t].x, (float)hr[j][t].y, (float)hr[j][t].z, (float)hr[j][t].w};
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const int k = lane * 4 + 256 * t;
+              xr[j][t] = (r0 + j < a.rows && k < rH) ? *reinterpret_cast<const f32x4*>(rX4 + (size_t)(r0 + j) * rH + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float acc = 0.0f;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            acc = fmaf(xr[j][t].x, wreg[t].x, acc); acc = fmaf(xr[j][t].y, wreg[t].y, acc);
+            acc = fmaf(xr[j][t].z, wreg[t].z, acc); acc = fmaf(xr[j][t].w, wreg[t].w, acc);
+          }
+          acc = wave_sum64(acc);
+          if (lane == 0 && r0 + j < a.rows) { const float v = acc + a.q_bias[0]; a.q_out[r0 + j] = v; a.qsum_partial[r0 + j] = (double)v; }
+        }
+      } else {
+        for (int j = 0; j < 4 && r0 + j < a.rows; ++j) {
+          const size_t x0 = (size_t)(r0 + j) * rH;
+          float acc = 0.0f;
+          for (int k = lane * 4; k < rH; k += 256) {
+            const f32x4 xv = head_ld4(rX4, rX416, x0 + k), wv4 = *reinterpret_cast<const f32x4*>(rW + k);
+            acc = fmaf(xv.x, wv4.x, acc); acc = fmaf(xv.y, wv4.y, acc); acc = fmaf(xv.z, wv4.z, acc); acc = fmaf(xv.w, wv4.w, acc);
+          }
+          acc = wave_sum64(acc);
+          if (lane == 0) { const float v = acc + a.q_bias[0]; a.q_out[r0 + j] = v; a.qsum_partial[r0 + j] = (double)v; }
+        }
+      }
+    }
+    return;
+  }
+  const int m0 = blockIdx.x * 64, kb = blockIdx.y * 256, k0 = kb + lane * 4;
+  const bool want_w = a.dW != nullptr;
+  // the head weights and all 16 rows of this wave's strip of the tower top go out BEFORE the head diffs are staged: neither
+  // depends on them, and the staging (two dependent loads, the inverting-gradients arithmetic, a barrier) is a memory round
+  // trip of its own that used to sit in front of these loads (round 4: one exposed latency less per launch)
+  f32x4 wv[NH], acc[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) { wv[j] = *reinterpret_cast<const f32x4*>(a.W + (size_t)j * a.H + k0); acc[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  f32x4 xr[16];
+  head_h4 hr[16];
+  if (a.X416 != nullptr) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) hr[r] = *reinterpret_cast<const head_h4*>(a.X416 + (size_t)(m0 + w * 16 + r) * a.H + k0);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) xr[r] = *reinterpret_cast<const f32x4*>(a.X4 + (size_t)(m0 + w * 16 + r) * a.H + k0);
+  }
+  for (int i = tid; i < 64 * NH; i += 256) {
+    const int m = m0 + i / NH, j = i % NH;
+    float d;
+    if constexpr (NH == kNO) {
+      d = a.dXc[(size_t)m * a.ldx + a.S + j];
+      const float out = a.aout16[(size_t)m * kAP + j];
+      float mn, mx;
+      if (j < kNA) { mn = -1.0f; mx = 1.0f; }
+      else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+      if (d < 0) d *= (mx - out) / (mx - mn);
+      else if (d > 0) d *= (out - mn) / (mx - mn);
+      if (blockIdx.y == 0) a.dA16[(size_t)m * kAP + j] = d;
+    } else {
+      d = a.dyh ? a.dyh[(size_t)m * a.lddy + j] : -1.0f;
+    }
+    s_dy[i] = d;
+  }
+  __syncthreads();
+  if (a.X416 != nullptr) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) xr[r] = f32x4{(float)hr[r].x, (float)hr[r].y, (float)hr[r].z, (float)hr[r].w};
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int ml = w * 16 + r, m = m0 + ml;
+    const f32x4 x = xr[r];
+    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+      const float d = s_dy[ml * NH + j];
+      if (NH == kNO && j >= kNA) { s1.x = fmaf(d, wv[j].x, s1.x); s1.y = fmaf(d, wv[j].y, s1.y); s1.z = fmaf(d, wv[j].z, s1.z); s1.w = fmaf(d, wv[j].w, s1.w); }
+      else { s0.x = fmaf(d, wv[j].x, s0.x); s0.y = fmaf(d, wv[j].y, s0.y); s0.z = fmaf(d, wv[j].z, s0.z); s0.w = fmaf(d, wv[j].w, s0.w); }
+      acc[j].x = fmaf(d, x.x, acc[j].x); acc[j].y = fmaf(d, x.y, acc[j].y); acc[j].z = fmaf(d, x.z, acc[j].z); acc[j].w = fmaf(d, x.w, acc[j].w);
+    }
+    if (NH == kNO) { s0.x += s1.x; s0.y += s1.y; s0.z += s1.z; s0.w += s1.w; }
+    const f32x4 dz = f32x4{s0.x * lrelu_mask(x.x), s0.y * lrelu_mask(x.y), s0.z * lrelu_mask(x.z), s0.w * lrelu_mask(x.w)};
+    if (a.dZ != nullptr) *reinterpret_cast<f32x4*>(a.dZ + (size_t)m * a.H + k0) = dz;
+    if (b.dZ16 != nullptr) {
+      const h4 hz = h4{(_Float16)(dz.x * b.scale16), (_Float16)(dz.y * b.scale16), (_Float16)(dz.z * b.scale16), (_Float16)(dz.w * b.scale16)};
+      *reinterpret_cast<h4*>(b.dZ16 + (size_t)m * a.H + k0) = hz;
+    }
+  }
+  if (want_w) {
+#pragma unroll
+    for (int j = 0; j < NH; ++j) *reinterpret_cast<f32x4*>(s_red + ((w * NH + j) * 256 + lane * 4)) = acc[j];
+  }
+  if (!want_w) return;
+  __syncthreads();
+  float* slab = b.slab2 + (size_t)blockIdx.x * NH * a.H;
+  for (int i = tid; i < NH * 256; i += 256) {
+    const int j = i >> 8, c = i & 255;
+    slab[(size_t)j * a.H + kb + c] = (s_red[(0 * NH + j) * 256 + c] + s_red[(1 * NH + j) * 256 + c]) +
+                                     (s_red[(2 * NH + j) * 256 + c] + s_red[(3 * NH + j) * 256 + c]);
+  }
+  if (blockIdx.y == 0 && tid < NH) {
+    float v = 0.0f;
+    for (int m = 0; m < 64; ++m) v += s_dy[m * NH + tid];
+    const size_t n_chunks = b.chunks > 0 ? (size_t)b.chunks : (size_t)gridDim.x;      // (rider blocks extend the grid beyond the row chunks)
+    b.slab2[n_chunks * NH * a.H + blockIdx.x * 16 + tid] = v;
+  }
+}
+// adds the row-chunk slabs of k_head_bwd_big: block = (64 columns, head j); the 4 waves take every
+// 4th chunk and are combined in fixed order.  Writes dW, db and one sum-of-squares partial per
+// (head, 64 columns) into partial[j * H/64 + column block].
+template <int NH>
+__global__ __launch_bounds__(256) void k_head_wred(HeadBwdBigArgs b, int chunks) {
+  const HeadBwdArgs& a = b.a;
+  __shared__ float s[4][64];
+  __shared__ float s_bias;
+  const int j = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 64 + lane;
+  float v = 0.0f;
+#pragma unroll 4
+  for (int c = w; c < chunks; c += 4) v += b.slab2[((size_t)c * NH + j) * a.H + k];
+  s[w][lane] = v;
+  if (w == 1) {
+    float t = 0.0f;
+    if (blockIdx.x == 0) {
+      for (int c = lane; c < chunks; c += 64) t += b.slab2[(size_t)chunks * NH * a.H + c * 16 + j];
+      t = wave_sum64(t);
+      if (lane == 0) a.db[j] = t;
+    }
+    if (lane == 0) s_bias = t * t;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  v = (s[0][lane] + s[1][lane]) + (s[2][lane] + s[3][lane]);
+  a.dW[(size_t)j * a.H + k] = v;
+  float ssq = v * v;
+  ssq = wave_sum64(ssq);
+  if (lane == 0 && a.partial != nullptr) a.partial[j * gridDim.x + blockIdx.x] = ssq + s_bias;
+}
+
+}  // namespace dqnhip

@@ -1,0 +1,118 @@
+// io_kernels.hip.h — the kernels learner_io.hip launches: replay-ring I/O, the acting-time pack / unpack helpers, the local
+// gradient reduction.  (Kernels are static: a unit that includes this embeds all of them.)
+#pragma once
+#include "update_bodies.hip.h"
+
+namespace dqnhip {
+
+// ---- replay ring (Ring: learner_args.hip.h) -------------------------------------
+// DQN::AddTransitions / AddTransition (src/dqn.cpp:768-781): the eviction
+// arithmetic runs on one thread and publishes (head,size); rows are scattered
+// by the rest of the grid from the values BEFORE the update (old_head/old_size
+// are recomputed identically by every block).
+static __global__ void k_add_transitions(Ring ring, DevState* st, const float* __restrict__ s,
+                                  const float* __restrict__ a, const float* __restrict__ r,
+                                  const float* __restrict__ mc, const float* __restrict__ nx,
+                                  const uint8_t* __restrict__ term, int n, int single_mode,
+                                  int* done_counter) {
+  // every block derives the same post-eviction (head,size)
+  int head = st->ring_head, size = st->ring_size;
+  if (single_mode == 2) {      // LoadReplayMemory: plain append, no eviction (caller checked the capacity)
+  } else if (single_mode) {    // AddTransition: pop iff size == capacity
+    if (size == ring.cap) { head = (head + 1) % ring.cap; size -= 1; }
+  } else {                     // AddTransitions: while (size + n >= capacity) pop_front
+    int pops = size + n - ring.cap + 1;
+    if (pops < 0) pops = 0;
+    if (pops > size) pops = size;
+    head = (int)(((long long)head + pops) % ring.cap); size -= pops;
+  }
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row < n) {
+    const long long slot = ((long long)head + size + row) % ring.cap;
+    const uint8_t t = term[row];
+    for (int c = lane; c < ring.SP; c += 64) {
+      ring.state[slot * ring.SP + c] = c < ring.S ? s[(size_t)row * ring.S + c] : 0.0f;
+      ring.next[slot * ring.SP + c] = (c < ring.S && !t && nx != nullptr) ? nx[(size_t)row * ring.S + c] : 0.0f;
+    }
+    if (lane < kAP) ring.act[slot * kAP + lane] = lane < kNO ? a[(size_t)row * kNO + lane] : 0.0f;
+    if (lane == 0) { ring.reward[slot] = r[row]; ring.mc[slot] = mc[row]; ring.term[slot] = t ? 1 : 0; }
+  }
+  // last block to finish publishes the new (head,size)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const int prev = atomicAdd(done_counter, 1);
+    if (prev == (int)gridDim.x - 1) {
+      st->ring_head = head; st->ring_size = size + n; *done_counter = 0;
+      __threadfence();
+    }
+  }
+}
+
+static __global__ void k_read_memory(Ring ring, const DevState* st, int first, int n, float* s, float* a,
+                              float* r, float* mc, float* nx, uint8_t* term) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const long long slot = ((long long)st->ring_head + first + row) % ring.cap;
+  for (int c = lane; c < ring.S; c += 64) {
+    if (s) s[(size_t)row * ring.S + c] = ring.state[slot * ring.SP + c];
+    if (nx) nx[(size_t)row * ring.S + c] = ring.next[slot * ring.SP + c];
+  }
+  if (a && lane < kNO) a[(size_t)row * kNO + lane] = ring.act[slot * kAP + lane];
+  if (lane == 0) {
+    if (r) r[row] = ring.reward[slot];
+    if (mc) mc[row] = ring.mc[slot];
+    if (term) term[row] = ring.term[slot];
+  }
+}
+
+// DQN::SampleStatesFromMemory (src/dqn.cpp:511-523): one wave per sampled transition, dense [n][S] out
+static __global__ void k_sample_states(Ring ring, const DevState* rs, const int* __restrict__ idx_in, uint64_t key,
+                                unsigned long long counter, int n, float* __restrict__ out) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const int size = rs->ring_size;
+  int li = idx_in ? idx_in[row] : (int)(((uint64_t)philox_u32(key, counter, (uint32_t)row) * (uint64_t)size) >> 32);
+  li = li < 0 ? 0 : (li >= size ? size - 1 : li);
+  const long long slot = ((long long)rs->ring_head + li) % ring.cap;
+  for (int c = lane; c < ring.S; c += 64) out[(size_t)row * ring.S + c] = ring.state[slot * ring.SP + c];
+}
+
+// ---- acting-time helpers ---------------------------------------------------------
+// dense [n][S] -> padded panel [npad][SP] (pad rows/cols zero)
+static __global__ void k_pack_rows(const float* __restrict__ src, int n, int S, float* __restrict__ dst,
+                            int npad, int SP) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npad * SP) return;
+  const int r = i / SP, c = i % SP;
+  dst[i] = (r < n && c < S) ? src[(size_t)r * S + c] : 0.0f;
+}
+// critic input panel from dense states + dense actor outputs
+static __global__ void k_pack_critic(const float* __restrict__ s, const float* __restrict__ a, int n, int S,
+                              float* __restrict__ dst, int npad, int KP) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npad * KP) return;
+  const int r = i / KP, c = i % KP;
+  float v = 0.0f;
+  if (r < n) { if (c < S) v = s[(size_t)r * S + c]; else if (c < S + kNO) v = a[(size_t)r * kNO + (c - S)]; }
+  dst[i] = v;
+}
+static __global__ void k_unpack_out(const float* __restrict__ out16, int n, float* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * kNO) return;
+  dst[i] = out16[(size_t)(i / kNO) * kAP + (i % kNO)];
+}
+
+// Sum of up to 8 co-located gradient arenas in rank order, written back to all (dqnhip_reduce_gradients_local)
+static __global__ __launch_bounds__(256) void k_local_reduce(LocalReduce a) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * 256) {
+    f32x4 s = reinterpret_cast<const f32x4*>(a.g[0])[i];
+    for (int r = 1; r < a.n; ++r) { const f32x4 v = reinterpret_cast<const f32x4*>(a.g[r])[i]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+    for (int r = 0; r < a.n; ++r) reinterpret_cast<f32x4*>(a.g[r])[i] = s;
+  }
+}
+
+}  // namespace dqnhip

@@ -8,6 +8,11 @@
 // (run_phase16), and dqnhip_apply_update*.  Which merged forms they take is decided in learner_plan.hip (plan_of); who calls them —
 // capture, replay, the update entry points — is learner_update.hip.  The other units: learner_internal.hip.h.
 #include "learner_internal.hip.h"
+#include "gemm_direct.hip.h"
+#include "hgemm.hip.h"
+#include "head_fwd_kernels.hip.h"
+#include "head_kernels.hip.h"
+#include "small_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;

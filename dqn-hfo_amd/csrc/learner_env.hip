@@ -1,5 +1,8 @@
 // learner_env.hip — host side of the batched env front-end (include/dqnhip_env.h; device side: env.hip.h).
 #include "learner_internal.hip.h"
+#include "env.hip.h"
+#include "gemm_bodies.hip.h"        // k_env_l0_flush carries a forward GEMM tile
+#include "head_fwd_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;

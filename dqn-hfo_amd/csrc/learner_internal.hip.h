@@ -11,9 +11,10 @@
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), parameters, multi-agent sharing, introspection
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   snapshot.cpp        Caffe snapshot layout (no device code)
-// A unit that launches a kernel embeds its own copy of the device code the headers' inline launchers name (~0.4 MB), and a launch
-// attribute (hipFuncSetAttribute) of a kernel with internal linkage holds for the calling unit's copy only: host-only units cost
-// nothing, and an attribute is set in the unit that launches the kernel.
+// This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
+// of the kernels it launches and embeds exactly those (tests/test_kernel_inventory.py), the host-only units embed no device code.
+// A launch attribute (hipFuncSetAttribute) of a kernel with internal linkage holds for the calling unit's copy only: it is set in
+// the unit that launches the kernel.
 // Not installed, not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,11 +38,9 @@
 
 #include "../../include/dqnhip.h"
 #include "../../include/dqnhip_env.h"
-#include "env.hip.h"
-#include "gemm_direct.hip.h"
-#include "hgemm.hip.h"
-#include "small_kernels.hip.h"
-
+#include "gemm_common.hip.h"      // LaunchOn, launch, TailsArgs, the flags
+#include "learner_args.hip.h"
+#include "hgemm_plan.hip.h"
 
 namespace dqnhip_host {
 using namespace dqnhip;
@@ -303,17 +302,7 @@ struct FwdPass { int net; const NetLayout* l; float** act; const float* seed_w =
 
 int layer_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, int i);
 int tower_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, int first_layer = 0);   // first_layer 1: layer 0 came out of a FirstLayerRider
-template <int NH, int MODE>
-int head_forward(H* h, hipStream_t st, const HeadArgs& a, const HeadArgs* b = nullptr) {
-  HeadArgs2 a2{}; a2.p[0] = a; if (b) a2.p[1] = *b;
-  if (NH > 1 && a.rows >= 1024 && a.H <= 1024 && a.H % 4 == 0)   // (single-head: the block-per-row form measured faster, 6.6 vs 8.8 us)
-    HIPCHK(launch(st, k_head_fwd_rows<NH, MODE>, dim3(256, b ? 2 : 1), dim3(256), 0, a2));
-  else if (a.l1_y != nullptr || (b && b->l1_y != nullptr))      // Step(1): the target actor's head also finishes critic_target's first layer
-    HIPCHK(launch(st, k_head_fwd<NH, MODE, true>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
-  else
-    HIPCHK(launch(st, k_head_fwd<NH, MODE, false>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
-  return 0;
-}
+// head_forward<NH, MODE>: head_fwd_kernels.hip.h (a template that names kernels: its users include it)
 constexpr int kMultiU = 16;    // updates per replay of the multi-update graph (dqnhip_update_async_n; see learner_update.hip)
 // Philox key of SampleTransitionsFromMemory: cfg.seed on rank 0 (what oracle/c_oracle.philox_indices
 // reproduces); data-parallel ranks get distinct streams from the SAME cfg.seed, so that the weight

@@ -1,6 +1,8 @@
 // learner_io.hip — everything of the C-ABI around the update: acting (SelectActions / CriticForward), the replay memory and
 // its .replaymemory files, parameter access, multi-agent sharing, introspection (include/dqnhip.h).
 #include "learner_internal.hip.h"
+#include "head_fwd_kernels.hip.h"
+#include "io_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;

@@ -13,7 +13,7 @@
 
 #include "dqnhip_internal.h"
 #include "gemm_direct.hip.h"
-#include "small_kernels.hip.h"   // kNO
+#include "learner_args.hip.h"   // kNO
 
 using namespace dqnhip;
 

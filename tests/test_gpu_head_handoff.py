@@ -1,4 +1,4 @@
-"""k_head_bwd's cross-block slab hand-off (small_kernels.hip.h) under UNEVEN load, every word checked.
+"""k_head_bwd's cross-block slab hand-off (head_kernels.hip.h) under UNEVEN load, every word checked.
 
 For shapes whose head gradients have no carrier launch (the fp16 learner below 1024 rows; the fp32 learner's actor heads from 1 383 rows when the
 bandwidth-tiled kernel does not apply, e.g. 1 440 rows), the head layer's dW / db are reduced over row chunks by the LAST block to arrive for a column block:
