@@ -19,6 +19,7 @@ TUNE_LATE_GATHER = 128
 # dqnhip_update_plan.forms bits (DQNHIP_PLAN_*), in bit order
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
               "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride")
+LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
 KIND_W, KIND_M, KIND_V, KIND_G = 0, 1, 2, 3
 
@@ -36,7 +37,16 @@ class Config(C.Structure):
         ("seed", C.c_uint64), ("stream", C.c_void_p), ("grad_arena", C.c_void_p),
         ("grad_arena_bytes", C.c_size_t), ("precision", C.c_int32), ("loss_scale", C.c_float),
         ("tuning_flags", C.c_int32),
+        ("loss_scale_mode", C.c_int32), ("loss_scale_growth_interval", C.c_int32),
+        ("loss_scale_min_mult", C.c_float), ("loss_scale_max_mult", C.c_float),
     ]
+
+
+class LossScaleState(C.Structure):
+    """struct dqnhip_loss_scale_state (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("mult_critic", C.c_float), ("mult_actor", C.c_float),
+                ("good_critic", C.c_int32), ("good_actor", C.c_int32), ("backoffs_critic", C.c_int32), ("backoffs_actor", C.c_int32),
+                ("growths_critic", C.c_int32), ("growths_actor", C.c_int32), ("skipped_steps", C.c_int32), ("reserved", C.c_int32)]
 
 
 class UpdatePlan(C.Structure):
@@ -85,6 +95,8 @@ SIGNATURES = {
     "dqnhip_dp_destroy": (C.c_int, [H]),
     "dqnhip_dp_info": (C.c_int, [ip, C.c_char_p, C.c_size_t]),
     "dqnhip_skipped_steps": (C.c_int, [H, C.POINTER(C.c_int64)]),
+    "dqnhip_get_loss_scale": (C.c_int, [H, C.POINTER(LossScaleState)]),
+    "dqnhip_set_loss_scale": (C.c_int, [H, C.c_float, C.c_float]),
     "dqnhip_reduce_gradients_local": (C.c_int, [C.POINTER(H), C.c_int32, C.c_int32]),
     "dqnhip_sample_states": (C.c_int, [H, ip, C.c_int32, fp]),
     "dqnhip_get_actor_output": (C.c_int, [H, C.c_int32, C.c_int32, fp]),

@@ -41,6 +41,10 @@ DEFINE_int32(select_actions_cap, 0, "Largest batch SelectActions accepts. 0: the
 DEFINE_int32(hip_device, 0, "HIP device ordinal of this process's learners.");
 DEFINE_bool(hip_graph, true, "Replay each update as one captured hipGraph.");
 DEFINE_string(precision, "fp32", "fp32 (exact-fp32 MFMA, the parity path) or fp16 (fp16 MFMA operands, fp32 accumulate).");
+DEFINE_bool(dynamic_loss_scale, false, "-precision fp16 only: the learner halves a per-net multiplier of its loss scales when a gradient norm is not "
+                                       "finite (the step is skipped, nothing is reported) and doubles it after -loss_scale_growth_interval finite "
+                                       "steps, on the device (dqnhip_config.loss_scale_mode). Off: the static scales; an overflow is fatal.");
+DEFINE_int32(loss_scale_growth_interval, 2000, "-dynamic_loss_scale: finite steps in a row before a multiplier doubles (0: never grow).");
 DEFINE_bool(device_sampling, false, "Sample minibatch indices on the device (counter-based) instead of the host std::mt19937.");
 DEFINE_bool(chained_updates, true, "UpdateActorCritic() tells the library which indices the NEXT call will draw (a copy of the engine runs ahead; "
             "dqnhip_update_chained): bursts of Update() get the launch schedule of a multi-update graph.  Same results, same RNG order.");
@@ -253,6 +257,13 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   c.seed = seed;
   CHECK(FLAGS_precision == "fp32" || FLAGS_precision == "fp16") << "-precision must be fp32 or fp16";
   c.precision = FLAGS_precision == "fp16" ? DQNHIP_FP16 : DQNHIP_FP32;
+  if (FLAGS_dynamic_loss_scale) {
+    CHECK(FLAGS_precision == "fp16") << "-dynamic_loss_scale needs -precision fp16 (the fp32 learner scales nothing)";
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-dynamic_loss_scale is a single-learner option (-dp_world 1, no -dp_rendezvous)";
+    CHECK_GE(FLAGS_loss_scale_growth_interval, 0) << "-loss_scale_growth_interval must be >= 0 (0: never grow)";
+    c.loss_scale_mode = DQNHIP_LOSS_SCALE_DYNAMIC;
+    c.loss_scale_growth_interval = FLAGS_loss_scale_growth_interval;
+  }
   dp_ = !FLAGS_dp_rendezvous.empty();
   deferred_ = FLAGS_deferred_updates && !dp_;          // (data parallel: every update is a collective the ranks enter together)
   CHECK(dp_ || FLAGS_dp_world == 1) << "-dp_world > 1 needs -dp_rendezvous <path shared by the ranks>";
@@ -529,6 +540,12 @@ void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_
     smoothed_actor_loss_ = 0;
   }
   smoothed_actor_loss_ += res.second / float(FLAGS_loss_display_iter);
+  // -dynamic_loss_scale: where the multipliers stand, at the same cadence (deferred updates: as of the collection that replays this update)
+  if (FLAGS_dynamic_loss_scale && critic_it % FLAGS_loss_display_iter == 0) {
+    dqnhip_loss_scale_state ls;
+    DQNHIP_CK(dqnhip_get_loss_scale(h_, &ls));
+    LOG(INFO) << "[Agent" << tid_ << "] Loss scale: critic x" << ls.mult_critic << ", actor x" << ls.mult_actor << ", skipped steps = " << ls.skipped_steps;
+  }
   if (critic_it >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_it >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
     Snapshot();
     last_snapshot_iter_ = max_iter();

@@ -138,6 +138,10 @@ __device__ __forceinline__ float wave_sum64(float v) {
 constexpr int kFlagTarget = 1;     // a TD target of the last update(s) was not finite
 constexpr int kFlagGradNorm = 2;   // a gradient L2 norm was not finite: that clip+Adam step was skipped
 
+// Dynamic loss scaling (DevState::ls_mult, learner_args.hip.h): a static loss scale times the live multiplier, or the reciprocal of
+// one times the reciprocal of the other.  Null: static mode, the immediate as it is and no load.
+__device__ __forceinline__ float ls_live(float base, const float* mult) { return mult != nullptr ? base * *mult : base; }
+
 // Data-parallel learners: the per-block loss / q partials reduced into the 4-float tails that ride in the gradient exchange
 // ([loss_sum, q_sum, target flag, 0]; tail[2] carries this rank's non-finite-target flag: it is raised from the rank's OWN replay
 // shard, so without it one rank would stop with "Target not finite!" while the others walk into the next collective).

@@ -47,6 +47,7 @@ static __global__ __launch_bounds__(256) void k_head_q_train(HeadTrainArgs a) {
   if ((a.dZ != nullptr || a.dZ16 != nullptr) && row < a.rows) {     // (wave-uniform condition)
     const float dqv = __shfl(dq_row, 0, 64);
     const size_t x0 = (size_t)row * a.H;
+    const float sc16 = a.dZ16 != nullptr ? ls_live(a.scale16, a.ls_mult) : 0.0f;      // (dynamic loss scaling: times the critic's live multiplier)
     auto seed = [&](auto tag) {
       for (int k = lane * 4; k < a.H; k += 256) {
         const f32x4 xv = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), wv = *reinterpret_cast<const f32x4*>(a.W + k);
@@ -55,7 +56,7 @@ static __global__ __launch_bounds__(256) void k_head_q_train(HeadTrainArgs a) {
         dz.x = (dqv * wv.x) * lrelu_mask(xv.x); dz.y = (dqv * wv.y) * lrelu_mask(xv.y);
         dz.z = (dqv * wv.z) * lrelu_mask(xv.z); dz.w = (dqv * wv.w) * lrelu_mask(xv.w);
         if constexpr (decltype(tag)::value)
-          *reinterpret_cast<head_h4*>(a.dZ16 + x0 + k) = head_h4{(_Float16)(dz.x * a.scale16), (_Float16)(dz.y * a.scale16), (_Float16)(dz.z * a.scale16), (_Float16)(dz.w * a.scale16)};
+          *reinterpret_cast<head_h4*>(a.dZ16 + x0 + k) = head_h4{(_Float16)(dz.x * sc16), (_Float16)(dz.y * sc16), (_Float16)(dz.z * sc16), (_Float16)(dz.w * sc16)};
         else
           *reinterpret_cast<f32x4*>(a.dZ + x0 + k) = dz;
       }
@@ -252,6 +253,7 @@ __global__ __launch_bounds__(1024) void k_head_bwd(HeadBwdArgs a) {
   float acc[NH];
 #pragma unroll
   for (int j = 0; j < NH; ++j) acc[j] = 0.0f;
+  const float sc16 = a.dZ16 != nullptr ? ls_live(a.scale16, a.ls_mult) : 0.0f;      // (dynamic loss scaling: times the net's live multiplier)
   auto rows_loop = [&](auto tag) {
   for (int mb = m0; mb < m1; mb += RB) {
     float xb[RB];
@@ -275,7 +277,7 @@ __global__ __launch_bounds__(1024) void k_head_bwd(HeadBwdArgs a) {
       if (NH == kNO) s0 += s1;
       const float dz = s0 * lrelu_mask(xv);
       if (a.dZ != nullptr) a.dZ[(size_t)m * a.H + k] = dz;
-      if (a.dZ16 != nullptr) a.dZ16[(size_t)m * a.H + k] = (_Float16)(dz * a.scale16);
+      if (a.dZ16 != nullptr) a.dZ16[(size_t)m * a.H + k] = (_Float16)(dz * sc16);
     }
   }
   };
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
   // what routes the workgroup, what the head part's first loads need and the narrow tile's operands: ONE round of scalar loads
   // (request_args, gemm_bodies.hip.h, has the reasoning; left alone: the tile count, then the head's pointers, then the tile's)
   int blk = (int)blockIdx.x;
-  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred));
+  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred), "s"(a.ls_mult));
   else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
   const int tiles = a.row_tiles * ((a.H + 255) >> 8);
   if (blk >= tiles) { q_head_rider(rider, blk - tiles); return; }
@@ -381,7 +383,16 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
   float out = 0.0f;
   if (tid < 16 * kNO) out = a.aout16[(size_t)(q0 + tid / kNO) * kAP + tid % kNO];
   f32x4 v;
-  if constexpr (F16) { v = dgrad_narrow_tile16<8>(a.t16, rt, smem); v.x *= a.inv_ls; v.y *= a.inv_ls; v.z *= a.inv_ls; v.w *= a.inv_ls; }
+  float sc16 = 0.0f;
+  if constexpr (F16) {
+    v = dgrad_narrow_tile16<8>(a.t16, rt, smem);
+    // (dynamic loss scaling: the incoming panel carries ls_q x mult, the outgoing one ls_a x mult — DqdaHeadArgs::ls_mult, whose
+    // pointer came with the launch's one round of scalar loads above; the pair itself is read behind the tile)
+    float inv_ls = a.inv_ls;
+    sc16 = a.scale16;
+    if (a.ls_mult != nullptr) { inv_ls *= a.ls_mult[1]; sc16 *= a.ls_mult[0]; }
+    v.x *= inv_ls; v.y *= inv_ls; v.z *= inv_ls; v.w *= inv_ls;
+  }
   else v = dgrad_narrow_tile<8>(a.pr, 0, rt, smem);
   if (tid < 64) {                          // wave 0 holds the tile: lane (li, lg), register r = dX[row q0 + li][column 4 lg + r]
     const int li = tid & 15, lg = tid >> 4;
@@ -412,7 +423,7 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
     s0 += s1;
     const float dz = s0 * lrelu_mask(xv[r]);
     if (!live) continue;
-    if constexpr (F16) a.dZ16[(size_t)(q0 + r) * a.H + k] = (_Float16)(dz * a.scale16);
+    if constexpr (F16) a.dZ16[(size_t)(q0 + r) * a.H + k] = (_Float16)(dz * sc16);
     else a.dZ[(size_t)(q0 + r) * a.H + k] = dz;
   }
 }
@@ -538,6 +549,7 @@ __global__ __launch_bounds__(256) void k_head_bwd_big(HeadBwdBigArgs b) {
     }
     s_dy[i] = d;
   }
+  const float sc16 = b.dZ16 != nullptr ? ls_live(b.scale16, a.ls_mult) : 0.0f;      // (dynamic loss scaling: times the net's live multiplier)
   __syncthreads();
   if (a.X416 != nullptr) {
 #pragma unroll
@@ -559,7 +571,7 @@ __global__ __launch_bounds__(256) void k_head_bwd_big(HeadBwdBigArgs b) {
     const f32x4 dz = f32x4{s0.x * lrelu_mask(x.x), s0.y * lrelu_mask(x.y), s0.z * lrelu_mask(x.z), s0.w * lrelu_mask(x.w)};
     if (a.dZ != nullptr) *reinterpret_cast<f32x4*>(a.dZ + (size_t)m * a.H + k0) = dz;
     if (b.dZ16 != nullptr) {
-      const h4 hz = h4{(_Float16)(dz.x * b.scale16), (_Float16)(dz.y * b.scale16), (_Float16)(dz.z * b.scale16), (_Float16)(dz.w * b.scale16)};
+      const h4 hz = h4{(_Float16)(dz.x * sc16), (_Float16)(dz.y * sc16), (_Float16)(dz.z * sc16), (_Float16)(dz.w * sc16)};
       *reinterpret_cast<h4*>(b.dZ16 + (size_t)m * a.H + k0) = hz;
     }
   }

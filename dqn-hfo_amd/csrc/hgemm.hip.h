@@ -51,6 +51,14 @@ typedef __attribute__((ext_vector_type(4))) float hg_f32x4;
 struct Db16 { const h16* dyt; int ld; int n_out; int rows; float* db; int row_base; };
 struct Db16Batch { Db16 d[8]; int n; float scale; float* sumsq_partial; /* one slot per 64-column block of k_db16_cols (may be null) */ };
 
+// Dynamic loss scaling (DevState::ls_mult, learner_args.hip.h): the device scalars of ONE launch — every problem of a launch belongs to
+// one net.  HGemm::seed_scale is multiplied by *seed_mult (the live multiplier), HGemm::scale32 and Db16Batch::scale by *scale32_mult
+// (its reciprocal); null: not applied.  They are an argument of kernels of their own (hgemm_nt_ls, hgemm_group_db_ls, k_db16_cols_ls:
+// the same bodies with LS = true), so that a static learner launches exactly the kernels, with exactly the arguments, it launched
+// before the mode existed: with the pointers inside HGemm and a null test in the one epilogue, static mode measured +0.5 % per update
+// at 512 rows, all of it in the GEMM launches (profiles/fp16_loss_scale_ab.md).
+struct HGemmLs { const float* seed_mult; const float* scale32_mult; };
+
 __host__ __device__ __forceinline__ int hg_tile_of_block(int bid, int total) {
   // XCD x (= bid % 8) gets a contiguous run of row-major tiles: they share A row panels and
   // sweep all of B, so each XCD's L2 holds its A panels + B once (bijective for any total)
@@ -109,8 +117,8 @@ typedef __attribute__((__vector_size__(4 * sizeof(short)))) short hg_s16x4;
 typedef __attribute__((address_space(3))) hg_s16x4* hg_lds_s16x4_ptr;
 
 // MODE = ta | tb << 1 of the problem (compile time: the fragment loads of the main loop differ)
-template <int WM, int WN, int MODE, int TM = 1>
-__device__ __forceinline__ void hgemm_body(const HGemm& g, const int bid) {
+template <int WM, int WN, int MODE, int TM = 1, bool LS = false>
+__device__ __forceinline__ void hgemm_body(const HGemm& g, const int bid, const HGemmLs ls = HGemmLs{nullptr, nullptr}) {
   using Cfg = HGCfg<WM, WN, TM>;
   constexpr int NW = Cfg::NW, NT = Cfg::NT;
   constexpr int MI = 2 * TM;                 // 32-row MFMA blocks per wave in M
@@ -381,6 +389,11 @@ __device__ __forceinline__ void hgemm_body(const HGemm& g, const int bid) {
     seed0 = *reinterpret_cast<const hg_f32x4*>(g.seed_w + gn); seed1 = *reinterpret_cast<const hg_f32x4*>(g.seed_w + gn + 4);
   }
   float sq = 0.f;                           // sum of squares of the fp32 values this thread writes (clip norm)
+  // LS: the live multipliers, read here in the epilogue (source order: behind the main loop; they are uniform loads through kernel
+  // arguments, which the compiler may hoist — nothing in front of the first LDS-DMA piece depends on them)
+  // (LS = false reads the two immediates where it always did: the same code as before the mode existed)
+  float m_seed = 1.0f, m_scale32 = 1.0f;
+  if constexpr (LS) { m_seed = ls_live(1.0f, ls.seed_mult); m_scale32 = ls_live(1.0f, ls.scale32_mult); }
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
     const int q = tid + it * NT;
@@ -422,12 +435,12 @@ __device__ __forceinline__ void hgemm_body(const HGemm& g, const int bid) {
         const float sw[8] = {seed0.x, seed0.y, seed0.z, seed0.w, seed1.x, seed1.y, seed1.z, seed1.w};
         h16x8 z;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) z[e] = (h16)(((-sw[e]) * ((float)o[e] > 0.f ? 1.0f : 0.01f)) * g.seed_scale);
+        for (int e = 0; e < 8; ++e) z[e] = (h16)(((-sw[e]) * ((float)o[e] > 0.f ? 1.0f : 0.01f)) * (LS ? g.seed_scale * m_seed : g.seed_scale));
         *reinterpret_cast<h16x8*>(g.CS16 + (size_t)gm * g.ldcs16 + gn) = z;
       }
     }
     if (g.C32 && gn < g.n_valid32) {
-      const float s = g.scale32;
+      const float s = LS ? g.scale32 * m_scale32 : g.scale32;
       float* d = g.C32 + (size_t)gm * g.ldc32 + gn;
       *reinterpret_cast<hg_f32x4*>(d) = hg_f32x4{v[0] * s, v[1] * s, v[2] * s, v[3] * s};
       *reinterpret_cast<hg_f32x4*>(d + 4) = hg_f32x4{v[4] * s, v[5] * s, v[6] * s, v[7] * s};
@@ -488,6 +501,15 @@ __global__ __launch_bounds__((HGCfg<WM, WN>::NT), 1) void hgemm_nt(HGemmBatch ba
   else hgemm_body<WM, WN, MODE1>(batch.g[sel], bid);
 }
 
+template <int WM, int WN, int MODE0, int MODE1>
+__global__ __launch_bounds__((HGCfg<WM, WN>::NT), 1) void hgemm_nt_ls(HGemmBatch batch, HGemmLs ls) {      // dynamic loss scaling (HGemmLs)
+  int bid;
+  const int sel = hg_select(batch, (int)blockIdx.x, bid);
+  if constexpr (MODE0 == MODE1) hgemm_body<WM, WN, MODE0, 1, true>(batch.g[sel], bid, ls);
+  else if (sel == 0) hgemm_body<WM, WN, MODE0, 1, true>(batch.g[0], bid, ls);
+  else hgemm_body<WM, WN, MODE1, 1, true>(batch.g[sel], bid, ls);
+}
+
 #ifdef HG_WITH_CT16
 // Probe (test build only): k-major problems on 256 x 128 tiles of FOUR waves, 128 x 64 per wave — 25 %
 // fewer LDS fragment bytes and DMA bytes per FLOP than the 64 x 64 wave tile.  Measured (profiles/r03_fp16_gemm_tiles.txt):
@@ -517,10 +539,17 @@ inline hipError_t hgemm_prepare_all() {
                             HGCfg<WM, WN>::LDS_BYTES);
   HG_FOR_EACH_KERNEL(HG_PREP)
 #undef HG_PREP
+#define HG_PREP_LS(WM, WN, M0, M1)                                                                                  \
+  if (e == hipSuccess)                                                                                               \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgemm_nt_ls<WM, WN, M0, M1>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                            HGCfg<WM, WN>::LDS_BYTES);
+  HG_FOR_EACH_KERNEL(HG_PREP_LS)
+#undef HG_PREP_LS
   return e;
 }
 
-inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, const LaunchOn& on, int force = 0) {
+// ls (may be null; both members null: as null): dynamic loss scaling — the launch takes the *_ls kernel and applies the multipliers
+inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, const LaunchOn& on, int force = 0, const HGemmLs* ls = nullptr) {
   HGemmBatch b; int wm, wn; long blocks;
   hipError_t e = hgemm_plan(gs, n, force, b, wm, wn, blocks);
   if (e != hipSuccess) return e;
@@ -534,13 +563,21 @@ inline hipError_t hgemm_launch_batch(const HGemm* gs, int n, const LaunchOn& on,
     return hipErrorInvalidValue;
 #endif
   }
+  if (ls != nullptr && (ls->seed_mult != nullptr || ls->scale32_mult != nullptr)) {
+    if (force == 4) return hipErrorInvalidValue;
+#define HG_TRY_LS(WM, WN, M0, M1) \
+  if (wm == WM && wn == WN && m0 == M0 && m1 == M1) return launch(on, hgemm_nt_ls<WM, WN, M0, M1>, dim3((unsigned)blocks), dim3(HGCfg<WM, WN>::NT), HGCfg<WM, WN>::LDS_BYTES, b, *ls);
+    HG_FOR_EACH_KERNEL(HG_TRY_LS)
+#undef HG_TRY_LS
+    return hipErrorInvalidValue;
+  }
 #define HG_TRY(WM, WN, M0, M1) \
   if (wm == WM && wn == WN && m0 == M0 && m1 == M1) return launch(on, hgemm_nt<WM, WN, M0, M1>, dim3((unsigned)blocks), dim3(HGCfg<WM, WN>::NT), HGCfg<WM, WN>::LDS_BYTES, b);
   HG_FOR_EACH_KERNEL(HG_TRY)
 #undef HG_TRY
   return hipErrorInvalidValue;          // an orientation pair no kernel was built for
 }
-inline hipError_t hgemm_launch(const HGemm& g, const LaunchOn& on, int force = 0) { return hgemm_launch_batch(&g, 1, on, force); }
+inline hipError_t hgemm_launch(const HGemm& g, const LaunchOn& on, int force = 0, const HGemmLs* ls = nullptr) { return hgemm_launch_batch(&g, 1, on, force, ls); }
 
 // ---------------------------------------------------------------------------------------------
 // fp32 [rows][ld_src] -> fp16 [rows][ld16] (+ transposed fp16 [ld16][ldT]) glue: minibatch panels,
@@ -595,6 +632,7 @@ inline hipError_t cvt16_launch(const Cvt16Batch& b, const LaunchOn& on) {
 
 #ifdef HG_WITH_CT16
 // bias gradients from TRANSPOSED panels (round-1 form, test build only): db_l[n] = scale * sum_b dYT_l[n][b]
+// (static loss scale only: it has no HGemmLs form)
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void k_db16(Db16Batch b) {
   int j = 0;
@@ -618,7 +656,7 @@ __global__ __launch_bounds__(256) void k_db16(Db16Batch b) {
 // the same from the batch-major panels dY [rows][ld] (no transposed copy exists): a block owns 64 columns of one layer,
 // 8 lanes x 16 B cover them, 32 row groups stride the rows; fixed-order LDS reduction over the row groups.
 // (Db16::dyt = the panel, ld = its row stride, row_base counts 64-column blocks.)
-__device__ __forceinline__ void db16_cols_block(const Db16Batch& b, int blk, float* scratch /* 32 x 65 floats of LDS */) {
+__device__ __forceinline__ void db16_cols_block(const Db16Batch& b, int blk, float* scratch /* 32 x 65 floats of LDS */, const float* scale_mult = nullptr /* HGemmLs::scale32_mult */) {
   float (*sred)[65] = reinterpret_cast<float (*)[65]>(scratch);
   int j = 0;
   while (j + 1 < b.n && blk >= b.d[j + 1].row_base) ++j;
@@ -648,7 +686,7 @@ __device__ __forceinline__ void db16_cols_block(const Db16Batch& b, int blk, flo
     float s = 0.f;
 #pragma unroll
     for (int g = 0; g < 32; ++g) s += sred[g][threadIdx.x];
-    s *= b.scale;
+    s *= ls_live(b.scale, scale_mult);
     d.db[col0 + threadIdx.x] = s;
     if (b.sumsq_partial) {                   // one wave: butterfly, lane 0 stores
       float q = s * s;
@@ -661,6 +699,11 @@ template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void k_db16_cols(Db16Batch b) {
   __shared__ float sred[32 * 65];
   db16_cols_block(b, (int)blockIdx.x, sred);
+}
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_db16_cols_ls(Db16Batch b, const float* scale_mult) {      // dynamic loss scaling
+  __shared__ float sred[32 * 65];
+  db16_cols_block(b, (int)blockIdx.x, sred, scale_mult);
 }
 
 // ALL wgrads of a net in one launch, with the bias-gradient column sums of every layer as extra workgroups.
@@ -818,15 +861,39 @@ __global__ __launch_bounds__((HGCfg<WM, WN>::NT), 1) void hgemm_group_db(HGemmBa
   if (b < db_blocks) { db16_cols_block(db, b, reinterpret_cast<float*>(hg_smem)); return; }
   if (tails.on) tails_block(tails, reinterpret_cast<float*>(hg_smem), reinterpret_cast<double*>(hg_smem + 64));
 }
+template <int WM, int WN>
+__global__ __launch_bounds__((HGCfg<WM, WN>::NT), 1) void hgemm_group_db_ls(HGemmBatch batch, Db16Batch db, int db_blocks, HeadWsum head, TailsArgs tails, HGemmLs ls) {      // dynamic loss scaling (the head blocks form unscaled fp32 gradients: untouched)
+  extern __shared__ __attribute__((aligned(1024))) unsigned char hg_smem[];
+  const int nt = batch.tile_end[batch.n - 1];
+  int b = (int)blockIdx.x;
+  if (b < nt) {
+    int bid;
+    const int sel = hg_select(batch, b, bid);
+    hgemm_body<WM, WN, 3, 1, true>(batch.g[sel], bid, ls);
+    return;
+  }
+  b -= nt;
+  const int nhb = head.nh != 0 ? head.blocks : 0;     // (the head blocks before the shorter column-sum blocks: with one workgroup per CU what does not fit beside the tiles queues)
+  if (b < nhb) {
+    float* sc = reinterpret_cast<float*>(hg_smem);
+    if (head.nh == 1) head_wsum_block<1>(head, b, sc); else head_wsum_block<10>(head, b, sc);
+    return;
+  }
+  b -= nhb;
+  if (b < db_blocks) { db16_cols_block(db, b, reinterpret_cast<float*>(hg_smem), ls.scale32_mult); return; }
+  if (tails.on) tails_block(tails, reinterpret_cast<float*>(hg_smem), reinterpret_cast<double*>(hg_smem + 64));
+}
 inline hipError_t hgemm_group_db_prepare() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgemm_group_db<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, HGCfg<1, 1>::LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgemm_group_db<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, HGCfg<2, 2>::LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgemm_group_db_ls<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, HGCfg<1, 1>::LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgemm_group_db_ls<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, HGCfg<2, 2>::LDS_BYTES);
   return e;
 }
 // gs: n reduction-major wgrads (mode 3); db_blocks = 64-column blocks of db (0: none).  big: 128 x 128 tiles
 // (every M, N a multiple of 128), else 64 x 64 split-K tiles.
 inline hipError_t hgemm_group_db_launch(const HGemm* gs, int n, bool big, const Db16Batch& db, int db_blocks, const LaunchOn& on,
-                                        const HeadWsum* head_in = nullptr, const TailsArgs* tails_in = nullptr) {
+                                        const HeadWsum* head_in = nullptr, const TailsArgs* tails_in = nullptr, const HGemmLs* ls = nullptr) {
   for (int i = 0; i < n; ++i) if (hgemm_mode(gs[i]) != 3) return hipErrorInvalidValue;
   HGemmBatch b; int wm, wn; long blocks;
   hipError_t e = hgemm_plan(gs, n, big ? 1 : 2, b, wm, wn, blocks);
@@ -836,6 +903,10 @@ inline hipError_t hgemm_group_db_launch(const HGemm* gs, int n, bool big, const 
   if (head.nh != 0 && ((head.nh != 1 && head.nh != 10) || head.blocks * 64 != head.H)) return hipErrorInvalidValue;
   if (tails_in != nullptr) { tails = *tails_in; tails.on = 1; }
   const dim3 grid((unsigned)(blocks + db_blocks + (head.nh ? head.blocks : 0) + (tails.on ? 1 : 0)));
+  if (ls != nullptr && ls->scale32_mult != nullptr) {
+    if (big) return launch(on, hgemm_group_db_ls<2, 2>, grid, dim3(256), HGCfg<2, 2>::LDS_BYTES, b, db, db_blocks, head, tails, *ls);
+    return launch(on, hgemm_group_db_ls<1, 1>, grid, dim3(256), HGCfg<1, 1>::LDS_BYTES, b, db, db_blocks, head, tails, *ls);
+  }
   if (big) return launch(on, hgemm_group_db<2, 2>, grid, dim3(256), HGCfg<2, 2>::LDS_BYTES, b, db, db_blocks, head, tails);
   return launch(on, hgemm_group_db<1, 1>, grid, dim3(256), HGCfg<1, 1>::LDS_BYTES, b, db, db_blocks, head, tails);
 }

@@ -269,6 +269,11 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
   a.beta1 = h->cfg.momentum; a.beta2 = h->cfg.momentum2; a.eps = h->cfg.delta;
   a.clip = h->cfg.clip_gradients; a.tau = (float)h->cfg.tau;
   a.soft_update_freq = h->cfg.soft_update_freq; a.which = net; a.st = h->st;
+  // dynamic loss scaling moves inside an update only (corr_pre): dqnhip_apply_update* keep the static behaviour — skip and report
+  if (h->ls_dynamic && corr_pre) {
+    a.ls_dynamic = 1;
+    a.ls = LossScaleCfg{h->cfg.loss_scale_growth_interval, h->cfg.loss_scale_min_mult, h->cfg.loss_scale_max_mult};
+  }
   if (tick) {
     if (!corr_pre) return fail("adam_launch: the update's bookkeeping needs the scalars k_gather leaves in DevState");
     a.tick_on = 1; a.tick = *tick;
@@ -350,11 +355,11 @@ static int optimiser_step(H* h, hipStream_t st, int net, bool dp, const TickArgs
 
 // ---- mixed-precision building blocks (hgemm.hip.h) --------------------------------------------
 
-int hgemm_timed(H* h, hipStream_t st, const HGemm* gs, int n, Family fam, int force = 0) {
-  HIPCHK(hgemm_launch_batch(gs, n, timed(h, fam, st), force));
+int hgemm_timed(H* h, hipStream_t st, const HGemm* gs, int n, Family fam, int force = 0, const HGemmLs* ls = nullptr) {
+  HIPCHK(hgemm_launch_batch(gs, n, timed(h, fam, st), force, ls));
   return 0;
 }
-int hgemm_timed(H* h, hipStream_t st, const HGemm& g, Family fam) { return hgemm_timed(h, st, &g, 1, fam); }
+int hgemm_timed(H* h, hipStream_t st, const HGemm& g, Family fam, const HGemmLs* ls = nullptr) { return hgemm_timed(h, st, &g, 1, fam, 0, ls); }
 
 // fp32 master weights of `net` -> fp16 mirror [N][kp].  The Adam pass keeps the mirrors current by itself; this
 // runs after host-side weight changes (w16_dirty).
@@ -399,7 +404,8 @@ int tower_forward16_pair(H* h, hipStream_t st, int p0, int net0, int p1, int net
   return 0;
 }
 
-// Tower backward in fp16 from dZ16[kind][L] (already scaled by `ls`).  want_w: dW (fp32, unscaled)
+// Tower backward in fp16 from dZ16[kind][L] (already scaled by `ls`; dynamic loss scaling: by ls x the live multiplier, and ls_mult
+// points at the net's {mult, 1 / mult} pair in DevState — null: static).  want_w: dW (fp32, unscaled)
 // into garena + bias gradients; input_grad: fp32 dZ32_0[rows][kp0] (unscaled).
 // No transposed copy of any panel exists: the dgrad reads the weight mirror W[n][k_in] reduction-major (its rows ARE
 // the reduction index), the wgrad reads dY[b][n_out] and X[b][k_in] reduction-major (hgemm.hip.h, HGemm::ta / tb).
@@ -410,10 +416,13 @@ int tower_forward16_pair(H* h, hipStream_t st, int p0, int net0, int p1, int net
 // partial: the clip norm's per-launch partial sums (single learner); rider (the head's dW / db) and tails ride in the last launch
 struct Bwd16Riders { float* partial = nullptr; const HeadWsum* rider = nullptr; const TailsArgs* tails = nullptr; };
 int tower_backward16(H* h, hipStream_t st, int net, int p, float* garena, float* dZ32_0, int rows,
-                     bool want_w, bool input_grad, float ls, const Bwd16Riders& r = Bwd16Riders{}) {
+                     bool want_w, bool input_grad, float ls, const float* ls_mult, const Bwd16Riders& r = Bwd16Riders{}) {
   const NetLayout& l = layout_of(h, net);
   const int kind = net & 1;
   h16** dZ = h->dZ16[kind];
+  // dynamic loss scaling: every 1 / ls below times 1 / mult, in the kernel — the launches then take the *_ls kernels (HGemmLs)
+  const HGemmLs lsv{nullptr, ls_mult != nullptr ? ls_mult + 1 : nullptr};
+  const HGemmLs* lsp = ls_mult != nullptr ? &lsv : nullptr;
   const bool grouped = want_w && l.L <= kHGemmMax && rows >= kGroupMinRows && !(h->cfg.tuning_flags & DQNHIP_TUNE_FP16_WGRAD_PER_LAYER);
   HGemm gws[kMaxL];
   for (int i = l.L - 1; i >= 0; --i) {
@@ -443,15 +452,15 @@ int tower_backward16(H* h, hipStream_t st, int net, int p, float* garena, float*
       g.C32 = garena + l.w_off[i]; g.ldc32 = l.kp[i]; g.n_valid32 = l.kp[i]; g.scale32 = 1.0f / ls;
       if (r.partial) g.sumsq_partial = r.partial + l.part_off[i];      // clip-norm share of this layer's dW (unscaled)
     }
-    if (grouped) { if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad)); continue; }
+    if (grouped) { if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad, lsp)); continue; }
     // per-layer form: both read dZ[i+1] and neither reads the other's output — at small minibatches (both on the
     // 64x64 split-K tile) they share one launch
     if (need_dx && want_w && hgemm_uses_small_tile(gd) && hgemm_uses_small_tile(gw) && gd.K % 128 == 0 && gw.K % 128 == 0) {
       const HGemm gs[2] = {gd, gw};
-      RC(hgemm_timed(h, st, gs, 2, kFamHgemmDgrad, 2));      // both on the 64x64 tile, as each would be alone
+      RC(hgemm_timed(h, st, gs, 2, kFamHgemmDgrad, 2, lsp));      // both on the 64x64 tile, as each would be alone
     } else {
-      if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad));
-      if (want_w && (i > 0 || need_dx)) RC(hgemm_timed(h, st, gw, kFamHgemmWgrad));
+      if (need_dx) RC(hgemm_timed(h, st, gd, kFamHgemmDgrad, lsp));
+      if (want_w && (i > 0 || need_dx)) RC(hgemm_timed(h, st, gw, kFamHgemmWgrad, lsp));
     }
   }
   if (!want_w) return 0;
@@ -463,14 +472,15 @@ int tower_backward16(H* h, hipStream_t st, int net, int p, float* garena, float*
   if (grouped) {
     // 128x128 tiles: a quarter of the operand bytes per FLOP of the 64x64 split-K tile (fp16 mode guarantees
     // hidden % 128 == 0, minibatch % 128 == 0 and a 128-wide first panel, so every wgrad tiles)
-    HIPCHK(hgemm_group_db_launch(gws, l.L, true, db, db_blocks, on, r.rider, r.tails));
+    HIPCHK(hgemm_group_db_launch(gws, l.L, true, db, db_blocks, on, r.rider, r.tails, lsp));
   } else if (!input_grad && hgemm_uses_small_tile(gws[0]) && gws[0].K % 128 == 0) {
     // per-layer form: the first layer's wgrad (few tiles, long reduction) carries the column sums
-    HIPCHK(hgemm_group_db_launch(gws, 1, false, db, db_blocks, on, r.rider, r.tails));
+    HIPCHK(hgemm_group_db_launch(gws, 1, false, db, db_blocks, on, r.rider, r.tails, lsp));
   } else {
     if (r.rider != nullptr || r.tails != nullptr) return fail("internal: the fp16 backward found no carrier launch for its riders");
-    if (!input_grad) HIPCHK(hgemm_launch(gws[0], on));
-    HIPCHK(launch(st, k_db16_cols<0>, dim3(db_blocks), dim3(256), 0, db));
+    if (!input_grad) HIPCHK(hgemm_launch(gws[0], on, 0, lsp));
+    if (lsp != nullptr) HIPCHK(launch(st, k_db16_cols_ls<0>, dim3(db_blocks), dim3(256), 0, db, lsv.scale32_mult));
+    else HIPCHK(launch(st, k_db16_cols<0>, dim3(db_blocks), dim3(256), 0, db));
   }
   return 0;
 }
@@ -533,6 +543,9 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
   const int Hh = la.dims[L], Hc = lc.dims[L];
   hipStream_t st = h->stream;
   const bool split = phase == 10;
+  // dynamic loss scaling: the {mult, 1 / mult} pairs the kernels read (null: static mode, the immediates alone)
+  const float* lsm_c = h->ls_dynamic ? h->st->ls_mult[DQNHIP_CRITIC] : nullptr;
+  const float* lsm_a = h->ls_dynamic ? h->st->ls_mult[DQNHIP_ACTOR] : nullptr;
   const bool part16 = !dp;      // the backward leaves the clip norm's partial sums (single learner: optimiser_step)
   // (the heads read the fp16 tower tops and write mu / mu' straight into the critics' fp16 input panels; the fp32 panels are unused)
   HeadArgs hA = actor_head_args(h, DQNHIP_ACTOR); hA.X16 = h->act16[1][L]; hA.xc16 = h->act16[4][0]; hA.ldxc16 = h->k16[1][0];
@@ -554,14 +567,14 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       t.Xt16 = h->act16[2][L]; t.X16 = h->act16[3][L];
       // with the head's dW / db riding in the net's last backward launch, the scaled fp16 tower-top gradient comes out of
       // this launch too (HeadTrainArgs::dZ16) — Step(1) has no head-backward launch (as on the fp32 path)
-      if (P.fuse_q) { t.dZ16 = h->dZ16[1][L]; t.scale16 = h->ls_c; }
+      if (P.fuse_q) { t.dZ16 = h->dZ16[1][L]; t.scale16 = h->ls_c; t.ls_mult = lsm_c; }
       HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
     }
     const TailsArgs tails_c = critic_tails(h);
     {
       HeadBwdArgs a{}; a.dyh = h->dq; a.lddy = 1; a.W = wat(h, DQNHIP_CRITIC, lc.hw_off); a.X416 = h->act16[3][L];
       a.H = Hc; a.rows = B; a.dZ = nullptr; a.dW = h->g[1] + lc.hw_off; a.db = h->g[1] + lc.hb_off;
-      a.partial = h->part[1] + lc.part_off[L];
+      a.partial = h->part[1] + lc.part_off[L]; a.ls_mult = lsm_c;
       const HeadWsum r{h->dq, 1, h->act16[3][L], Hc, B, a.dW, a.db, a.partial, 1, Hc / 64};
       if (P.head_rides_c) {}                                       // (dZ16 came out of k_head_q_train, dW / db come from the riders)
       else if (head_big_ok(h, B, Hc)) { a.dZ = nullptr; RC(head_backward_big<1>(h, st, a, h->dZ16[1][L], h->ls_c)); }
@@ -569,7 +582,7 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       Bwd16Riders br; br.partial = part16 ? h->part[1] : nullptr;
       if (P.head_rides_c) br.rider = &r;
       if (P.tails_ride) br.tails = &tails_c;
-      RC(tower_backward16(h, st, DQNHIP_CRITIC, 3, h->g[1], nullptr, B, true, false, h->ls_c, br));
+      RC(tower_backward16(h, st, DQNHIP_CRITIC, 3, h->g[1], nullptr, B, true, false, h->ls_c, lsm_c, br));
     }
     if (dp && !P.tails_ride) RC(tails_launch(st, tails_c));
     return 0;
@@ -584,29 +597,30 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
     for (int i = 0; i < L; ++i) {
       HGemm g = fwd16_problem(h, 4, DQNHIP_CRITIC, B, i);
       if (fused_seed && i == L - 1) { g.seed_w = wat(h, DQNHIP_CRITIC, lc.hw_off); g.CS16 = h->dZ16[1][L]; g.ldcs16 = Hc; g.seed_scale = h->ls_q; }
-      RC(hgemm_timed(h, st, g, kFamHgemmFwd));
+      const HGemmLs seed_ls{lsm_a, nullptr};      // (dynamic loss scaling: the seed panel carries ls_q x the actor's live multiplier)
+      RC(hgemm_timed(h, st, g, kFamHgemmFwd, fused_seed && i == L - 1 && lsm_a != nullptr ? &seed_ls : nullptr));
     }
     if (!fused_seed) {
       // q(s, mu(s)) rides in the dq = -1 head launch (rider blocks)
       HeadBwdArgs a{}; a.dyh = nullptr; a.lddy = 1; a.W = wat(h, DQNHIP_CRITIC, lc.hw_off); a.X416 = h->act16[4][L];
-      a.H = Hc; a.rows = B; a.dZ = nullptr;
+      a.H = Hc; a.rows = B; a.dZ = nullptr; a.ls_mult = lsm_a;
       a.q_bias = wat(h, DQNHIP_CRITIC, lc.hb_off); a.q_out = h->q2; a.qsum_partial = h->q_partial;
       if (head_big_ok(h, B, Hc)) { a.dZ = nullptr; RC(head_backward_big<1>(h, st, a, h->dZ16[1][L], h->ls_q)); }
       else { a.dZ16 = h->dZ16[1][L]; a.scale16 = h->ls_q; RC(head_backward<1>(h, st, a)); }
     }
-    RC(tower_backward16(h, st, DQNHIP_CRITIC, 4, nullptr, h->dZc[0], B, false, !P.fuse_head, h->ls_q));       // (fuse_head: layers L-1 .. 1 only)
+    RC(tower_backward16(h, st, DQNHIP_CRITIC, 4, nullptr, h->dZc[0], B, false, !P.fuse_head, h->ls_q, lsm_a));       // (fuse_head: layers L-1 .. 1 only)
     if (P.fuse_head) {
       DqdaHeadArgs fz{};
       fz.aout16 = h->aout16; fz.dA16 = h->dA16; fz.W = wat(h, DQNHIP_ACTOR, la.hw_off); fz.H = Hh; fz.rows = B;
       fz.t16 = NarrowTile16{h->w16[DQNHIP_CRITIC][0] + h->S, h->k16[1][0], h->dZ16[1][1], lc.dims[1], lc.dims[1]}; fz.inv_ls = 1.0f / h->ls_q;
-      fz.X416 = h->act16[1][L]; fz.dZ16 = h->dZ16[0][L]; fz.scale16 = h->ls_a;
+      fz.X416 = h->act16[1][L]; fz.dZ16 = h->dZ16[0][L]; fz.scale16 = h->ls_a; fz.ls_mult = lsm_a;
       // (DQNHIP_TUNE_SEPARATE_HEAD_SEED: q(s, mu(s)) came out of the dq = -1 head launch — no rider blocks)
       const QHeadRider qr{nullptr, wat(h, DQNHIP_CRITIC, lc.hw_off), wat(h, DQNHIP_CRITIC, lc.hb_off), h->q2, h->q_partial, Hc, B, fused_seed ? (B + 3) / 4 : 0, h->act16[4][L]};
       HIPCHK(dqda_head_bwd_launch(fz, qr, st));
     }
     {
       HeadBwdArgs a{}; a.dXc = h->dZc[0]; a.ldx = lc.kp[0]; a.S = h->S; a.aout16 = h->aout16; a.dA16 = h->dA16;
-      a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.X416 = h->act16[1][L]; a.H = Hh; a.rows = B; a.dZ = nullptr;
+      a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.X416 = h->act16[1][L]; a.H = Hh; a.rows = B; a.dZ = nullptr; a.ls_mult = lsm_a;
       if (fused_seed) {
         a.q_bias = wat(h, DQNHIP_CRITIC, lc.hb_off); a.q_out = h->q2; a.qsum_partial = h->q_partial;
         a.qr_W = wat(h, DQNHIP_CRITIC, lc.hw_off); a.qr_X416 = h->act16[4][L]; a.qr_H = Hc;
@@ -621,7 +635,7 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       Bwd16Riders br; br.partial = part16 ? h->part[0] : nullptr;
       if (P.head_rides_a) br.rider = &r;
       if (P.tails_ride) br.tails = &tails_a;
-      RC(tower_backward16(h, st, DQNHIP_ACTOR, 1, h->g[0], nullptr, B, true, false, h->ls_a, br));
+      RC(tower_backward16(h, st, DQNHIP_ACTOR, 1, h->g[0], nullptr, B, true, false, h->ls_a, lsm_a, br));
       if (dp && !P.tails_ride) RC(tails_launch(st, tails_a));
     }
     return 0;

@@ -50,8 +50,47 @@ struct DevState {
   // takes its own from here: base + its position in the graph (a capture-time constant).
   unsigned long long gbase_counter;
   int gbase_it[2];
+  // Dynamic loss scaling (cfg.loss_scale_mode = DQNHIP_LOSS_SCALE_DYNAMIC, fp16 learner), indexed [actor, critic] like adam_corr: the
+  // live power-of-two multiplier of the net's static scales and its reciprocal, side by side (ls_mult[1] multiplies ls_c, ls_mult[0]
+  // both ls_q and ls_a), the finite steps in a row since the multiplier last moved, and how often it was halved / doubled.
+  // WRITER: lane 0 of block 0 of the strided pass of that net's optimiser launch inside an update (adam_scalars), and nobody else on
+  // the device.  READERS: the backward kernels of the update — ls_mult[1] between the update's gather and the critic's optimiser
+  // launch, ls_mult[0] between the critic's optimiser launch and the actor's — always a kernel boundary away from the writer on the
+  // one stream.  No block of an optimiser launch reads a multiplier: the other optimiser blocks only need "finite or not", the
+  // riders that share those launches are the next update's gather (counters and indices) and, on fp32 learners only, first tower
+  // layers.  So one slot is enough (adam_corr needs two because a rider WRITES the next update's value beside its reader).
+  float ls_mult[2][2];     // [net][mult, 1 / mult]; {1, 1} in static mode (never read there)
+  int ls_good[2];
+  int ls_backoffs[2], ls_growths[2];
 };
 // (kFlagTarget / kFlagGradNorm: gemm_common.hip.h)
+
+// ---- dynamic loss scaling: the decision, once per net per update (adam_scalars; tests/cpp/loss_scale_host.cpp runs it on the host) ----
+struct LossScaleCfg { int growth_interval; float min_mult, max_mult; };      // growth_interval 0: never grow
+struct LossScaleState { float mult; int good; };
+struct LossScaleStep { LossScaleState st; int raise_flag, backed_off, grew; };
+// finite: the net's gradient norm of this update.  Not finite: the step is skipped (the caller's business); the multiplier is halved
+// and the update stays silent — unless the multiplier is at its floor already, where no backoff is left: raise kFlagGradNorm as the
+// static mode does (a NaN weight, a hopeless scale).  Finite: after growth_interval such steps in a row the multiplier doubles, up to
+// max_mult.  Multipliers are powers of two: halving and doubling are exact.
+__host__ __device__ inline LossScaleStep loss_scale_step(LossScaleState s, bool finite, const LossScaleCfg& c) {
+  LossScaleStep r{s, 0, 0, 0};
+  if (!finite) {
+    r.st.good = 0;
+    if (s.mult <= c.min_mult) r.raise_flag = 1;
+    else { r.st.mult = s.mult * 0.5f; r.backed_off = 1; }
+    return r;
+  }
+  r.st.good = s.good + 1;
+  if (c.growth_interval > 0 && r.st.good == c.growth_interval) {
+    const float up = s.mult * 2.0f < c.max_mult ? s.mult * 2.0f : c.max_mult;
+    r.grew = up > s.mult ? 1 : 0;
+    r.st.mult = up > s.mult ? up : s.mult;
+    r.st.good = 0;
+  }
+  return r;
+}
+// (the readers take the multiplier through ls_live, gemm_common.hip.h)
 
 // ---- replay ring -------------------------------------------------------------
 // SoA ring in HBM: state[cap][SP], next[cap][SP] (rows padded to SP = roundup(S,64)
@@ -142,6 +181,7 @@ struct HeadTrainArgs {
   _Float16* dZ16; float scale16;
   // k_dgrad_qtrain: the two head dot products in 16-column pieces, [rows][H / 16], left by the top forward layers (GemmProblem::dot_w)
   const float* pdt; const float* pd;
+  const float* ls_mult;                                 // dynamic loss scaling: scale16 is multiplied by *ls_mult (DevState::ls_mult[1]; null: static)
 };
 
 // k_head_bwd
@@ -166,6 +206,7 @@ struct HeadBwdArgs {
   // fp16 learner: also emit the tower-top gradient as the scaled fp16 panel the fp16 GEMMs read (dZ16 [rows][H])
   // instead of a separate conversion launch
   _Float16* dZ16; float scale16;
+  const float* ls_mult;                // dynamic loss scaling: scale16 is multiplied by *ls_mult (null: static)
 };
 
 // the fp16 operands of a narrow dgrad tile (dgrad_narrow_tile16, gemm_bodies.hip.h)
@@ -182,12 +223,15 @@ struct DqdaHeadArgs {
   // tower-top gradient written as the scaled fp16 panel dZ16 = (h16)(dZ * scale16)
   NarrowTile16 t16; float inv_ls;
   const _Float16* X416; _Float16* dZ16; float scale16;
+  // dynamic loss scaling: {mult, 1 / mult} of the actor (DevState::ls_mult[0]) — inv_ls is multiplied by ls_mult[1] (the incoming panel
+  // carries ls_q x mult), scale16 by ls_mult[0] (the outgoing one carries ls_a x mult); null: static
+  const float* ls_mult;
 };
 
 // k_head_bwd_big / k_head_wred
 struct HeadBwdBigArgs {
   HeadBwdArgs a;
-  _Float16* dZ16; float scale16;                             // fp16 output (null: fp32 a.dZ only)
+  _Float16* dZ16; float scale16;                             // fp16 output (null: fp32 a.dZ only); dynamic loss scaling: times *a.ls_mult
   float* slab2;                                              // [rows/64][NH][H] then [rows/64][16]
   // rider (NH == 1, dq = -1 pass; a.q_out != null): blocks with blockIdx.x >= chunks compute q = head(X4) + the avg-Q
   // partials (critic(s, mu(s)) head forward, src/dqn.cpp:913-916), one wave per row — as in k_head_bwd
@@ -235,6 +279,9 @@ struct AdamArgs {
   // by then every block has read the iteration counters it is about to advance) runs tick_body
   int tick_on;                    // 1: block 0 also runs tick_body (requires corr_pre / soft_pre)
   TickArgs tick;
+  // dynamic loss scaling (an optimiser pass INSIDE an update of a dynamic learner; else 0 and the static behaviour): block 0 of the
+  // strided pass runs loss_scale_step on DevState::ls_mult[which] / ls_good[which]
+  int ls_dynamic; LossScaleCfg ls;
 };
 
 // the first-layer riders of the optimiser launches (k_adam_soft_fwd1*, k_adam_soft_l0)

@@ -56,6 +56,10 @@ void dqnhip_default_config(dqnhip_config* c, int32_t state_size) {
   c->delta = 1e-8f;                        // Caffe SolverParameter.delta default
   c->clip_gradients = 10.f;                // src/dqn_main.cpp:35
   c->device = 0; c->dp_world = 1; c->dp_rank = 0; c->use_graph = 0; c->seed = 1;
+  c->loss_scale_mode = DQNHIP_LOSS_SCALE_STATIC;
+  c->loss_scale_growth_interval = 2000;                // the customary value of mixed-precision trainers; not measured here
+  c->loss_scale_min_mult = 1.0f / 4096.0f;             // ls_q x 2^-12 = 1: no scaling left
+  c->loss_scale_max_mult = 1.0f;                       // never above the built-in scales unless asked
 }
 
 int dqnhip_get_config(dqnhip_handle h, dqnhip_config* out) {
@@ -142,8 +146,9 @@ static int create_impl(H* h, const dqnhip_config* cfg) {
   RC(dalloc(&h->mb_reward, B)); RC(dalloc(&h->mb_mc, B)); RC(dalloc(&h->mb_term, B));
   HIPCHK(hipMalloc(&h->mb_idx, B * sizeof(int)));
   HIPCHK(hipHostMalloc((void**)&h->idx_pinned, B * sizeof(int), hipHostMallocMapped));
-  HIPCHK(hipHostMalloc((void**)&h->pinned_stats, 64, hipHostMallocMapped));
-  memset(h->pinned_stats, 0, 64);
+  // [0, 3) the tick's {loss, avg_q, flags}; [8] dqnhip_skipped_steps; [16, 32) dqnhip_get_loss_scale
+  HIPCHK(hipHostMalloc((void**)&h->pinned_stats, 128, hipHostMallocMapped));
+  memset(h->pinned_stats, 0, 128);
   { void* d = nullptr; HIPCHK(hipHostGetDevicePointer(&d, h->idx_pinned, 0)); h->idx_pinned_dev = (const int*)d;
     HIPCHK(hipHostGetDevicePointer(&d, h->pinned_stats, 0)); h->stats_dev = (float*)d; }
   RC(dalloc(&h->aout_t16, (size_t)B * kAP)); RC(dalloc(&h->aout16, (size_t)B * kAP)); RC(dalloc(&h->dA16, (size_t)B * kAP));
@@ -167,6 +172,12 @@ static int create_impl(H* h, const dqnhip_config* cfg) {
     h->ls_c = 16.0f * (float)(B * cfg->dp_world) * user;   // dq = (q-y)/B_global: back to O(q-y)
     h->ls_q = 4096.0f * user;
     h->ls_a = 16384.0f * user;
+    h->ls_dynamic = cfg->loss_scale_mode == DQNHIP_LOSS_SCALE_DYNAMIC;
+    if (h->ls_dynamic) {                                   // both multipliers start at 1 (DevState::ls_mult; the rest of it stays zero)
+      const float one[2][2] = {{1.0f, 1.0f}, {1.0f, 1.0f}};
+      HIPCHK(hipMemcpyAsync(h->st->ls_mult, one, sizeof one, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
     auto halloc = [&](h16** p, size_t n) -> int {
       HIPCHK(hipMalloc(p, n * sizeof(h16)));
       HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(h16), h->stream));

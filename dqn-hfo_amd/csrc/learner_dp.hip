@@ -239,6 +239,7 @@ int dqnhip_dp_init(dqnhip_handle h, const void* id, size_t bytes, int32_t flags)
   if (bytes != sizeof(ncclUniqueId)) return fail("dp_init: id must be DQNHIP_DP_ID_BYTES = %zu bytes", sizeof(ncclUniqueId));
   if (h->comm) return fail("dp_init: this learner already has a communicator");
   if (h->w_owner || h->sharers) return fail("dp_init: learners that share layers cannot join a data-parallel group");
+  if (h->ls_dynamic) return fail("dp_init: loss_scale_mode = dynamic is a single-learner mode (the data-parallel form has never run: DESIGN.md 9)");
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   // Exchange forms no multi-rank run has ever executed (every box so far had one GPU; one-rank groups, where each collective
@@ -303,6 +304,7 @@ int dqnhip_dp_init(dqnhip_handle h, const void* id, size_t bytes, int32_t flags)
 // (A launcher that has its own channel — MPI, torch.distributed's store — passes the id to dqnhip_dp_init directly.)
 int dqnhip_dp_init_file(dqnhip_handle h, const char* path, int32_t flags, int32_t timeout_s) {
   if (!h || !path) return fail("null argument");
+  if (h->ls_dynamic) return fail("dp_init: loss_scale_mode = dynamic is a single-learner mode (the data-parallel form has never run: DESIGN.md 9)");
   ncclUniqueId uid;
   if (h->cfg.dp_rank == 0) RC(dqnhip_dp_unique_id(&uid, sizeof uid));
   RC(dqnhip_dp_rendezvous_file(path, h->cfg.dp_rank, h->cfg.dp_world, timeout_s, &uid, sizeof uid));

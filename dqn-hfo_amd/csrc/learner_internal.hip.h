@@ -194,6 +194,9 @@ struct dqnhip_learner {
   // transposed copy of anything exists
   bool fp16 = false;
   float ls_c = 1.f, ls_q = 1.f, ls_a = 1.f;  // static loss scales: critic step, dQ/da pass, actor step
+  // cfg.loss_scale_mode == DQNHIP_LOSS_SCALE_DYNAMIC: the kernels multiply the static scales by the live multipliers in
+  // DevState::ls_mult (ls_c by the critic's, ls_q and ls_a by the actor's), which the optimiser launches of an update adjust
+  bool ls_dynamic = false;
   int k16[2][kMaxL + 1] = {{0}};             // fp16 panel widths per net kind (k16[.][0] = in_dim rounded to 128)
   h16* w16a[4] = {nullptr, nullptr, nullptr, nullptr};   // fp16 mirror of each weight arena (written by the Adam pass)
   h16* w16[4][kMaxL] = {{nullptr}};          // = w16a[net] + w_off[i]: [N_out][kp]
@@ -288,6 +291,7 @@ void dense_to_arena(const NetLayout& l, const float* dense, std::vector<float>& 
 void arena_to_dense(const NetLayout& l, const std::vector<float>& arena, float* dense);
 inline const NetLayout& layout_of(const H* h, int net) { return (net & 1) ? h->lc : h->la; }
 int validate(const dqnhip_config* c);
+bool is_pow2(float x);                                   // a positive, normal power of two (loss-scale multipliers)
 // shape predicates of the launch schedules (learner_plan.hip)
 bool bwd_layer_is_pair(const NetLayout& l, int i, int rows);
 bool bwd_is_shifted(const H* h, const NetLayout& l, int rows);

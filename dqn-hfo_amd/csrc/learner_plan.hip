@@ -76,6 +76,12 @@ void arena_to_dense(const NetLayout& l, const std::vector<float>& arena, float* 
 }
 
 
+// a positive, normal power of two (a loss-scale multiplier: halving and doubling it, and multiplying by it, are exact)
+bool is_pow2(float x) {
+  int e = 0;
+  return std::isfinite(x) && x >= 1.17549435e-38f && std::frexp(x, &e) == 0.5f;
+}
+
 int validate(const dqnhip_config* c) {
   if (!c) return fail("config is null");
   if (c->struct_size != (int32_t)sizeof(dqnhip_config)) return fail("dqnhip_config.struct_size %d != %zu (ABI mismatch)", c->struct_size, sizeof(dqnhip_config));
@@ -92,6 +98,19 @@ int validate(const dqnhip_config* c) {
     if (c->minibatch % 128) return fail("fp16 mode: minibatch must be a multiple of 128 (got %d)", c->minibatch);
     for (int i = 0; i < c->num_hidden; ++i)
       if (c->hidden[i] % 128) return fail("fp16 mode: hidden[%d]=%d must be a multiple of 128", i, c->hidden[i]);
+  }
+  if (c->loss_scale_mode != DQNHIP_LOSS_SCALE_STATIC && c->loss_scale_mode != DQNHIP_LOSS_SCALE_DYNAMIC)
+    return fail("loss_scale_mode must be DQNHIP_LOSS_SCALE_STATIC or DQNHIP_LOSS_SCALE_DYNAMIC (got %d)", c->loss_scale_mode);
+  if (c->loss_scale_mode == DQNHIP_LOSS_SCALE_DYNAMIC) {      // (static mode reads none of the other three fields)
+    if (c->precision != DQNHIP_FP16) return fail("loss_scale_mode = dynamic needs precision = DQNHIP_FP16 (an fp32 learner scales nothing)");
+    if (c->dp_world > 1) return fail("loss_scale_mode = dynamic needs dp_world = 1 (got %d): the data-parallel form has never run", c->dp_world);
+    if (c->loss_scale_growth_interval < 0) return fail("loss_scale_growth_interval must be >= 0 (0: never grow; got %d)", c->loss_scale_growth_interval);
+    if (!is_pow2(c->loss_scale_min_mult)) return fail("loss_scale_min_mult must be a power of two (got %g)", (double)c->loss_scale_min_mult);
+    if (!is_pow2(c->loss_scale_max_mult)) return fail("loss_scale_max_mult must be a power of two (got %g)", (double)c->loss_scale_max_mult);
+    if (c->loss_scale_min_mult > c->loss_scale_max_mult)
+      return fail("loss_scale_min_mult %g > loss_scale_max_mult %g", (double)c->loss_scale_min_mult, (double)c->loss_scale_max_mult);
+    if (c->loss_scale_min_mult > 1.0f) return fail("loss_scale_min_mult %g > 1: the multipliers start at 1", (double)c->loss_scale_min_mult);
+    if (c->loss_scale_max_mult < 1.0f) return fail("loss_scale_max_mult %g < 1: the multipliers start at 1", (double)c->loss_scale_max_mult);
   }
   return 0;
 }

@@ -364,7 +364,7 @@ int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss, float* avg_q, int3
   }
   if (bad < 0) return 0;
   if (flags & kFlagTarget) return fail("collected update %d: Target not finite!", bad);
-  if (flags & kFlagGradNorm) return fail("collected update %d: Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale)", bad);
+  if (flags & kFlagGradNorm) return fail("collected update %d: Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale or use loss_scale_mode = dynamic)", bad);
   return fail("collected update %d: Critic loss not finite!", bad);
 }
 
@@ -418,7 +418,7 @@ int dqnhip_read_stats(dqnhip_handle h, float* critic_loss, float* avg_q) {
   // reference aborts; here: an error code from the first read after the offending update, whichever
   // entry point (blocking, async, phased, hipGraph) ran it
   if (flags & kFlagTarget) return fail("Target not finite!");
-  if (flags & kFlagGradNorm) return fail("Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale)");
+  if (flags & kFlagGradNorm) return fail("Gradient norm not finite: the clip+Adam step was skipped (fp16: lower cfg.loss_scale or use loss_scale_mode = dynamic)");
   if (!std::isfinite(h->pinned_stats[0])) return fail("Critic loss not finite!");
   return 0;
 }
@@ -431,6 +431,54 @@ int dqnhip_skipped_steps(dqnhip_handle h, int64_t* count) {
   HIPCHK(hipStreamSynchronize(h->stream));
   memcpy(&v, h->pinned_stats + 8, sizeof v);
   *count = v;
+  return 0;
+}
+
+// Dynamic loss scaling: the state the optimiser launches keep in DevState.  Stream-ordered like dqnhip_skipped_steps: copied behind
+// everything enqueued so far, one sync.
+int dqnhip_get_loss_scale(dqnhip_handle h, dqnhip_loss_scale_state* out) {
+  if (!h || !out) return fail("null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  struct Tail { float mult[2][2]; int good[2], backoffs[2], growths[2]; } t;
+  static_assert(offsetof(DevState, ls_good) == offsetof(DevState, ls_mult) + offsetof(Tail, good) &&
+                offsetof(DevState, ls_backoffs) == offsetof(DevState, ls_mult) + offsetof(Tail, backoffs) &&
+                offsetof(DevState, ls_growths) == offsetof(DevState, ls_mult) + offsetof(Tail, growths) && sizeof(Tail) <= 15 * sizeof(float),
+                "the loss-scale fields of DevState are contiguous and fit pinned_stats[16 .. 31)");
+  int skipped = 0;
+  HIPCHK(hipMemcpyAsync(h->pinned_stats + 16, h->st->ls_mult, sizeof t, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->pinned_stats + 31, &h->st->skipped_steps, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memcpy(&t, h->pinned_stats + 16, sizeof t);
+  memcpy(&skipped, h->pinned_stats + 31, sizeof skipped);
+  memset(out, 0, sizeof *out);
+  out->struct_size = (int32_t)sizeof *out;
+  out->mode = h->ls_dynamic ? DQNHIP_LOSS_SCALE_DYNAMIC : DQNHIP_LOSS_SCALE_STATIC;
+  out->mult_actor = h->ls_dynamic ? t.mult[DQNHIP_ACTOR][0] : 1.0f; out->mult_critic = h->ls_dynamic ? t.mult[DQNHIP_CRITIC][0] : 1.0f;
+  out->good_actor = t.good[DQNHIP_ACTOR]; out->good_critic = t.good[DQNHIP_CRITIC];
+  out->backoffs_actor = t.backoffs[DQNHIP_ACTOR]; out->backoffs_critic = t.backoffs[DQNHIP_CRITIC];
+  out->growths_actor = t.growths[DQNHIP_ACTOR]; out->growths_critic = t.growths[DQNHIP_CRITIC];
+  out->skipped_steps = skipped;
+  return 0;
+}
+
+int dqnhip_set_loss_scale(dqnhip_handle h, float mult_critic, float mult_actor) {
+  if (!h) return fail("null handle");
+  if (!h->ls_dynamic) return fail("dqnhip_set_loss_scale: this learner's loss_scale_mode is static (cfg.loss_scale is fixed at create time)");
+  if (h->next_phase != 0) return fail("dqnhip_set_loss_scale: a phased update is in progress (next phase %d)", h->next_phase);
+  const float m[2] = {mult_actor, mult_critic};      // DevState order: [actor, critic]
+  for (int i = 0; i < 2; ++i) {
+    const char* who = i == DQNHIP_ACTOR ? "mult_actor" : "mult_critic";
+    if (!is_pow2(m[i])) return fail("dqnhip_set_loss_scale: %s = %g is not a power of two", who, (double)m[i]);
+    if (m[i] < h->cfg.loss_scale_min_mult || m[i] > h->cfg.loss_scale_max_mult)
+      return fail("dqnhip_set_loss_scale: %s = %g is outside [loss_scale_min_mult, loss_scale_max_mult] = [%g, %g]", who, (double)m[i],
+                  (double)h->cfg.loss_scale_min_mult, (double)h->cfg.loss_scale_max_mult);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  h->epoch += 1;                                     // (a chained update's riders are dropped: the next call starts a chain afresh)
+  struct { float mult[2][2]; int good[2]; } v = {{{m[0], 1.0f / m[0]}, {m[1], 1.0f / m[1]}}, {0, 0}};
+  static_assert(offsetof(DevState, ls_good) == offsetof(DevState, ls_mult) + sizeof v.mult, "ls_good follows ls_mult");
+  HIPCHK(hipStreamSynchronize(h->stream));           // behind every update enqueued so far; the copy below is synchronous (v is on this stack)
+  HIPCHK(hipMemcpy(h->st->ls_mult, &v, sizeof v, hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -82,7 +82,7 @@ static __global__ __launch_bounds__(256) void k_adam_soft(AdamArgs a) {
   // update's first launch, no block of this launch reads anything tick_body writes, so block 0 runs it as soon as its
   // own slice is done, beside the other 2047 blocks.
   if (a.tick_on && blockIdx.x == 0) {
-    const bool skipped = s[7] != 0.0f;
+    const bool skipped = s[7] == 1.0f;      // (2: dynamic loss scaling backed off — skipped, not reported)
     __syncthreads();
     tick_body(a.tick, s, sq, skipped);
   }
@@ -100,7 +100,7 @@ static __global__ __launch_bounds__(256) void k_adam_soft_gather(AdamArgs a, Gat
   const int blk = b0 - g.blocks;
   adam_soft_body<1, 0>(a, blk, (int)gridDim.x - g.blocks, s);
   if (a.tick_on && blk == 0) {
-    const bool skipped = s[7] != 0.0f;
+    const bool skipped = s[7] == 1.0f;      // (2: dynamic loss scaling backed off — skipped, not reported)
     __syncthreads();
     tick_body(a.tick, s, sq, skipped);
   }
@@ -182,7 +182,7 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
   b -= p1.blocks;
   adam_soft_body<1, 0, true>(a, b, (int)gridDim.x - ra.blocks - p0.blocks - p1.blocks, s);
   if (a.tick_on && b == 0) {
-    const bool skipped = s[7] != 0.0f;
+    const bool skipped = s[7] == 1.0f;      // (2: dynamic loss scaling backed off — skipped, not reported)
     __syncthreads();
     tick_body(a.tick, s, sq, skipped);
   }

@@ -153,6 +153,22 @@ template <bool IN16> __device__ __forceinline__ float head_ld1t(const float* x32
 // per-launch scalars of the optimiser pass into s[4..7]: clip scale, lr * Adam correction, soft-update
 // switch, skip flag.  Every block re-derives them from the same partials in the same order.
 // PRE: the caller guarantees corr_pre / soft_pre (inside an update) — the stand-alone path's two double pow() are not compiled in
+// Dynamic loss scaling, once per net per update: the one place on the device that writes this net's multiplier (DevState::ls_mult has
+// the readers — none of them in this launch; the update's later launches, and the next update's, read what is stored here across a
+// kernel boundary).  Returns adam_scalars' s[7].  Out of line, so that the one-lane prologue of the optimiser kernels — whose register
+// budget was tuned — stays the code it was: only a dynamic learner's block 0 makes the call.
+// The reciprocal follows the multiplier by exact halving / doubling (growth below the cap is always x2: both are powers of two).
+__device__ __noinline__ float loss_scale_update(DevState* st, int which, bool finite, LossScaleCfg cfg) {
+  const float mult = st->ls_mult[which][0];
+  const LossScaleStep r = loss_scale_step(LossScaleState{mult, st->ls_good[which]}, finite, cfg);
+  if (r.backed_off) { st->ls_mult[which][0] = r.st.mult; st->ls_mult[which][1] *= 2.0f; st->ls_backoffs[which] += 1; }
+  if (r.grew) { st->ls_mult[which][0] = r.st.mult; st->ls_mult[which][1] *= 0.5f; st->ls_growths[which] += 1; }
+  st->ls_good[which] = r.st.good;
+  if (finite) return 0.0f;
+  atomicAdd(&st->skipped_steps, 1);
+  if (r.raise_flag) atomicOr(&st->flags, kFlagGradNorm);
+  return r.raise_flag ? 1.0f : 2.0f;
+}
 template <bool PRE = false>
 __device__ __forceinline__ void adam_scalars(const AdamArgs& a, int blk, float* s /*>= 8 floats*/) {
   // every block re-derives the same global L2 norm from the partials, in the
@@ -182,8 +198,12 @@ __device__ __forceinline__ void adam_scalars(const AdamArgs& a, int blk, float* 
     // A non-finite norm (fp16 mode: an overflowed dZ panel) would give scale = clip/inf = 0 and
     // g*0 = NaN in m, v, w and the targets for good.  Every block derives the same norm, so every
     // block takes the same decision: skip the whole step and raise the sticky flag.
-    s[7] = isfinite(sumsq) ? 0.0f : 1.0f;
-    if (s[7] != 0.0f && blk == 0) { atomicOr(&a.st->flags, kFlagGradNorm); atomicAdd(&a.st->skipped_steps, 1); }   // one launch per net per update
+    // s[7]: 0 take the step, 1 skip it and report (kFlagGradNorm), 2 skip it in silence (dynamic loss scaling backed off).  The
+    // blocks other than the strided pass's first only tell zero from non-zero.
+    const bool finite = isfinite(sumsq);
+    s[7] = finite ? 0.0f : 1.0f;
+    if (a.ls_dynamic && blk == 0) s[7] = loss_scale_update(a.st, a.which, finite, a.ls);
+    else if (!finite && blk == 0) { atomicOr(&a.st->flags, kFlagGradNorm); atomicAdd(&a.st->skipped_steps, 1); }   // one launch per net per update
   }
   __syncthreads();
 }
@@ -285,6 +305,7 @@ __device__ __forceinline__ void adam_soft_body(const AdamArgs& a, int blk, int n
 // is taken from the per-block double partials when they are local (single GPU),
 // from the all-reduced float tail under data parallelism.
 // One block of 256 threads: strided partial sums, fixed butterfly + fixed cross-wave order.
+// skipped_now: block 0 of this launch has just raised kFlagGradNorm (adam_scalars' s[7] == 1: a skipped step that is reported)
 __device__ __forceinline__ void tick_body(const TickArgs& a, float* sdot /*[4]*/, double* sq /*[4]*/, bool skipped_now) {
   const int t = threadIdx.x;
   double qs = 0.0;

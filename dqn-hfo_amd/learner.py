@@ -84,7 +84,8 @@ class DQN:
                  gamma=0.99, beta=0.5, tau=0.001, soft_update_freq=1, actor_lr=1e-5, critic_lr=1e-3,
                  momentum=0.95, momentum2=0.999, clip_grad=10.0, memory_threshold=1000, seed=1,
                  device=0, dp_world=1, dp_rank=0, use_graph=False, stream=None, grad_arena=None,
-                 grad_arena_bytes=0, tid=0, save_path="state/dqn", precision="fp32", loss_scale=0.0, tuning=0):
+                 grad_arena_bytes=0, tid=0, save_path="state/dqn", precision="fp32", loss_scale=0.0, tuning=0,
+                 loss_scale_mode="static", loss_scale_growth_interval=None, loss_scale_min_mult=None, loss_scale_max_mult=None):
         self.lib = capi.load()
         cfg = capi.Config()
         self.lib.dqnhip_default_config(C.byref(cfg), state_size)
@@ -105,6 +106,14 @@ class DQN:
         cfg.precision = {"fp32": 0, "fp16": 1}[precision]
         cfg.loss_scale = loss_scale
         cfg.tuning_flags = int(tuning)                  # capi.TUNE_* bits: alternative schedules of the same arithmetic
+        # fp16 learner: "dynamic" lets the optimiser launches halve / double a per-net multiplier of the loss scales (None: the header's defaults)
+        cfg.loss_scale_mode = {"static": capi.LOSS_SCALE_STATIC, "dynamic": capi.LOSS_SCALE_DYNAMIC}[loss_scale_mode]
+        if loss_scale_growth_interval is not None:
+            cfg.loss_scale_growth_interval = int(loss_scale_growth_interval)
+        if loss_scale_min_mult is not None:
+            cfg.loss_scale_min_mult = loss_scale_min_mult
+        if loss_scale_max_mult is not None:
+            cfg.loss_scale_max_mult = loss_scale_max_mult
         self.cfg = cfg
         self.h = capi.H()
         self._ck(self.lib.dqnhip_create(C.byref(cfg), C.byref(self.h)))
@@ -497,6 +506,18 @@ class DQN:
         n = C.c_int64()
         self._ck(self.lib.dqnhip_skipped_steps(self.h, C.byref(n)))
         return n.value
+
+    def loss_scale_state(self):
+        """dqnhip_get_loss_scale as a dict: mode, mult_critic / mult_actor, good_*, backoffs_*, growths_*, skipped_steps."""
+        s = capi.LossScaleState()
+        self._ck(self.lib.dqnhip_get_loss_scale(self.h, C.byref(s)))
+        d = {name: getattr(s, name) for name, _ in capi.LossScaleState._fields_ if name not in ("struct_size", "reserved", "mode")}
+        d["mode"] = "dynamic" if s.mode == capi.LOSS_SCALE_DYNAMIC else "static"
+        return d
+
+    def set_loss_scale(self, mult_critic, mult_actor):
+        """Dynamic mode: sets both multipliers (powers of two inside the configured bounds) and zeroes the finite-step counters."""
+        self._ck(self.lib.dqnhip_set_loss_scale(self.h, float(mult_critic), float(mult_actor)))
 
     def read_stats(self):
         loss, avgq = C.c_float(), C.c_float()

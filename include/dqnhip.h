@@ -68,6 +68,9 @@ enum dqnhip_param_kind {
  * src/dqn.cpp:21-31 and the solver fields set in src/dqn_main.cpp:249-262. */
 #define DQNHIP_FP32 0
 #define DQNHIP_FP16 1
+/* dqnhip_config.loss_scale_mode (fp16 learner) */
+#define DQNHIP_LOSS_SCALE_STATIC 0   /* the built-in scales x loss_scale, fixed at create time (default)                 */
+#define DQNHIP_LOSS_SCALE_DYNAMIC 1  /* ... x a power-of-two multiplier per net that the optimiser launch adjusts itself */
 
 typedef struct dqnhip_config {
   int32_t struct_size;       /* = sizeof(dqnhip_config); ABI check            */
@@ -103,11 +106,36 @@ typedef struct dqnhip_config {
                                 Adam, heads, TD target and losses stay fp32.  Needs
                                 minibatch % 128 == 0 and hidden[i] % 128 == 0.       */
   float loss_scale;          /* FP16 only: multiplies the built-in static scales of the
-                                back-propagated gradients (0 or 1: defaults)           */
+                                back-propagated gradients (0 or 1: defaults).  An fp16
+                                gradient panel that overflows makes the net's gradient
+                                norm non-finite: the step is skipped and the next
+                                dqnhip_read_stats fails ("Gradient norm not finite") —
+                                unless loss_scale_mode is dynamic.                     */
   int32_t tuning_flags;      /* DQNHIP_TUNE_* bits: A/B switches that select an alternative
                                 SCHEDULE of the same arithmetic (0 = the measured winners).
                                 The library reads no environment variable; every bit has a
                                 parity test (tests/test_gpu_tuning_flags.py).          */
+  /* Dynamic loss scaling (FP16, dp_world = 1 only; off by default — static mode launches the same
+   * kernels and produces the same bits as before these fields existed).  Two multipliers live on the
+   * device, both powers of two starting at 1: the critic's multiplies the critic step's scale, the
+   * actor's those of the dQ/da pass and the actor step.  Once per net per update, inside that net's
+   * optimiser launch (captured graphs included; no extra launch, no host read):
+   *   norm not finite           -> the step is skipped as in static mode (dqnhip_skipped_steps counts it),
+   *                                the multiplier is halved, the update reports NO error;
+   *   ... at loss_scale_min_mult -> no backoff is left: "Gradient norm not finite" as in static mode;
+   *   norm finite                -> the step is taken; after loss_scale_growth_interval such steps in a row
+   *                                the multiplier doubles, up to loss_scale_max_mult.
+   * Gradients (dqnhip_get_params(.., DQNHIP_KIND_G)) are unscaled in either mode, and a dynamic learner
+   * whose multipliers are m computes, bit for bit, what a static one with loss_scale x m computes.
+   * dqnhip_apply_update* never move the multipliers.  Snapshots do not carry them. */
+  int32_t loss_scale_mode;            /* DQNHIP_LOSS_SCALE_STATIC (default) / DQNHIP_LOSS_SCALE_DYNAMIC            */
+  int32_t loss_scale_growth_interval; /* finite steps in a row before the multiplier doubles; 0: never grow.
+                                         Default 2000, the customary value of mixed-precision trainers —
+                                         NOT measured on this workload.                                       */
+  float loss_scale_min_mult;          /* floor, a power of two <= 1 (default 2^-12: the dQ/da scale x 2^-12 = 1,
+                                         no scaling left)                                                     */
+  float loss_scale_max_mult;          /* cap, a power of two >= 1 (default 1: nothing measured says scales above
+                                         the built-in ones help)                                              */
 } dqnhip_config;
 
 /* fp16 learner: one wgrad launch per layer (a layer's dgrad + wgrad sharing a launch at small
@@ -372,6 +400,24 @@ int dqnhip_read_stats(dqnhip_handle h, float* critic_loss, float* avg_q);
  * norm is that of the REDUCED gradient) and a rank-local "Target not finite!" is shared through the
  * all-reduced tail, so all ranks report the same error at the same update. */
 int dqnhip_skipped_steps(dqnhip_handle h, int64_t* count);
+
+/* Dynamic loss scaling (cfg.loss_scale_mode): the device's state, read behind everything enqueued so far
+ * (stream-ordered, like dqnhip_skipped_steps).  A static learner reports mode 0, multipliers 1, counters 0. */
+typedef struct dqnhip_loss_scale_state {
+  int32_t struct_size;                       /* filled in by the library */
+  int32_t mode;                              /* cfg.loss_scale_mode */
+  float mult_critic, mult_actor;             /* the live multipliers */
+  int32_t good_critic, good_actor;           /* finite steps in a row since the multiplier last moved */
+  int32_t backoffs_critic, backoffs_actor;   /* halvings so far */
+  int32_t growths_critic, growths_actor;     /* doublings so far */
+  int32_t skipped_steps;                     /* dqnhip_skipped_steps */
+  int32_t reserved;
+} dqnhip_loss_scale_state;
+int dqnhip_get_loss_scale(dqnhip_handle h, dqnhip_loss_scale_state* out);
+/* Sets both multipliers (powers of two inside [loss_scale_min_mult, loss_scale_max_mult]) and zeroes both
+ * finite-step counters; with loss_scale_growth_interval = 0 and no overflow they then stay put.  Waits for the
+ * stream.  Refused on a static learner. */
+int dqnhip_set_loss_scale(dqnhip_handle h, float mult_critic, float mult_actor);
 
 /* Sum-reduce the gradient arenas (tails included) of n learners of one data-parallel group that
  * live on ONE device, in rank order, leaving the sum in each: the exchange step between
