@@ -20,6 +20,7 @@ TUNE_LATE_GATHER = 128
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
               "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride")
 LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
+FP32, FP16 = 0, 1                                   # DQNHIP_FP32 / DQNHIP_FP16: dqnhip_config.precision, dqnhip_set_act_precision
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
 KIND_W, KIND_M, KIND_V, KIND_G = 0, 1, 2, 3
 
@@ -107,6 +108,8 @@ SIGNATURES = {
     "dqnhip_select_actions_device": (C.c_int, [H, C.c_void_p, C.c_int32, C.c_void_p]),
     "dqnhip_select_actions_net": (C.c_int, [H, C.c_int32, fp, C.c_int32, fp]),
     "dqnhip_critic_forward": (C.c_int, [H, C.c_int32, fp, fp, C.c_int32, fp]),
+    "dqnhip_set_act_precision": (C.c_int, [H, C.c_int32]),
+    "dqnhip_get_act_precision": (C.c_int, [H, ip]),
     "dqnhip_add_transitions": (C.c_int, [H, fp, fp, fp, fp, fp, up, C.c_int32]),
     "dqnhip_add_transition": (C.c_int, [H, fp, fp, C.c_float, C.c_float, fp, C.c_uint8]),
     "dqnhip_add_transitions_device": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -41,6 +41,8 @@ DEFINE_int32(select_actions_cap, 0, "Largest batch SelectActions accepts. 0: the
 DEFINE_int32(hip_device, 0, "HIP device ordinal of this process's learners.");
 DEFINE_bool(hip_graph, true, "Replay each update as one captured hipGraph.");
 DEFINE_string(precision, "fp32", "fp32 (exact-fp32 MFMA, the parity path) or fp16 (fp16 MFMA operands, fp32 accumulate).");
+DEFINE_string(act_precision, "fp32", "fp32: SelectActions / EvaluateAction run the exact-fp32 kernels on the master weights. fp16 (-precision fp16 only): "
+              "they compute what the update's own forward passes compute, on the learner's fp16 weight mirrors (dqnhip_set_act_precision).");
 DEFINE_bool(dynamic_loss_scale, false, "-precision fp16 only: the learner halves a per-net multiplier of its loss scales when a gradient norm is not "
                                        "finite (the step is skipped, nothing is reported) and doubles it after -loss_scale_growth_interval finite "
                                        "steps, on the device (dqnhip_config.loss_scale_mode). Off: the static scales; an overflow is fatal.");
@@ -257,6 +259,8 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   c.seed = seed;
   CHECK(FLAGS_precision == "fp32" || FLAGS_precision == "fp16") << "-precision must be fp32 or fp16";
   c.precision = FLAGS_precision == "fp16" ? DQNHIP_FP16 : DQNHIP_FP32;
+  CHECK(FLAGS_act_precision == "fp32" || FLAGS_act_precision == "fp16") << "-act_precision must be fp32 or fp16";
+  CHECK(FLAGS_act_precision == "fp32" || FLAGS_precision == "fp16") << "-act_precision fp16 needs -precision fp16 (the fp32 learner keeps no fp16 weight mirrors)";
   if (FLAGS_dynamic_loss_scale) {
     CHECK(FLAGS_precision == "fp16") << "-dynamic_loss_scale needs -precision fp16 (the fp32 learner scales nothing)";
     CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-dynamic_loss_scale is a single-learner option (-dp_world 1, no -dp_rendezvous)";
@@ -280,6 +284,7 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     c.dp_world = FLAGS_dp_world; c.dp_rank = FLAGS_dp_rank;
   }
   DQNHIP_CK(dqnhip_create(&c, &h_));
+  if (FLAGS_act_precision == "fp16") DQNHIP_CK(dqnhip_set_act_precision(h_, DQNHIP_FP16));
   if (dp_) {
     // one communicator per agent thread's learner: agents are independent DQNs (src/dqn_main.cpp:264), each its own group
     const std::string rv = FLAGS_dp_rendezvous + "_agent" + std::to_string(tid);

@@ -42,6 +42,17 @@ struct EnvDev {
   int* commit_ticket;              // arrival counter of k_env_flush (its last block publishes the ring bookkeeping); null: k_env_commit does
 };
 
+// fp16 acting (dqnhip_set_act_precision): what the fp16 instantiations of k_env_init / k_env_step take beside EnvDev.  The fp32
+// instantiations' argument is EnvDev alone — the bytes they always took — and their code is what it was.
+struct Env16 {
+  _Float16* x16; int ldx16;        // [Npad16][ldx16] the actor's fp16 input panel (ldx16 == SP: the fp16 learner pads both to 128)
+  const _Float16* head_x16;        // fused actor heads: the fp16 tower-top rows [.][head_h] (null: a separate head launch wrote out16)
+};
+template <bool F16> struct EnvArgs;
+template <> struct EnvArgs<false> { EnvDev e; };
+template <> struct EnvArgs<true> { EnvDev e; Env16 x; };
+static_assert(sizeof(EnvArgs<false>) == sizeof(EnvDev), "the fp32 step's kernel argument is EnvDev");
+
 __device__ __forceinline__ float env_u01(unsigned long long seed, unsigned long long g, int w, int k) {
   return (float)(philox_u32(seed, g, (uint32_t)(w * 256 + k)) >> 8) * (1.0f / 16777216.0f);
 }
@@ -111,12 +122,15 @@ __device__ __forceinline__ void game_reset(GameState& g) {
 }
 
 // new episode for worker w: first state, HFOGameState() and the initial update after the forced
-// DASH(0,0) (src/dqn_main.cpp:103-105).  One wave; s_state is a [SP] LDS row.
-__device__ __forceinline__ void env_reset_worker(const EnvDev& e, int w, int lane, float* s_state) {
+// DASH(0,0) (src/dqn_main.cpp:103-105).  One wave; s_state is a [SP] LDS row.  F16: the state also goes, rounded, into the fp16 panel.
+template <bool F16>
+__device__ __forceinline__ void env_reset_worker(const EnvArgs<F16>& a, int w, int lane, float* s_state) {
+  const EnvDev& e = a.e;
   const unsigned long long g = e.g[w];
   for (int f = lane; f < e.SP; f += 64) {
     const float v = f < e.S ? env_feature(e, g, w, f) : 0.0f;
     s_state[f] = v; e.cur[(size_t)w * e.SP + f] = v;
+    if constexpr (F16) { if (f < a.x.ldx16) a.x.x16[(size_t)w * a.x.ldx16 + f] = (_Float16)v; }
   }
   __syncthreads();
   if (lane == 0) {
@@ -126,9 +140,10 @@ __device__ __forceinline__ void env_reset_worker(const EnvDev& e, int w, int lan
   }
 }
 
-static __global__ void k_env_init(EnvDev e) {
+template <bool F16>
+__global__ void k_env_init(const EnvArgs<F16> a) {
   extern __shared__ float s_state[];
-  env_reset_worker(e, blockIdx.x, threadIdx.x, s_state);
+  env_reset_worker<F16>(a, blockIdx.x, threadIdx.x, s_state);
 }
 
 // one environment step of every worker: block = one worker, 4 waves.  What used to be one wave's serial chain
@@ -138,7 +153,13 @@ static __global__ void k_env_init(EnvDev e) {
 // (Also computing the first tower layer of the NEXT step here, from the state row the block has just produced — one
 // launch fewer per step — was built and measured: 77 instead of 29 us per step at 64 workers.  64 blocks on 64 CUs
 // each pull all of W0 (512 KB) through one CU's load path, where the separate launch spreads it over 256.)
-static __global__ __launch_bounds__(256) void k_env_step(EnvDev e) {
+// F16 (fp16 acting): the fused heads read the fp16 tower-top row, and the actor's next input row also goes, rounded to fp16, into
+// the fp16 panel beside the fp32 `cur` row (which the episode rows and the reward keep reading): a step has no pack launch.
+template <bool F16>
+__global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a) {
+  const EnvDev& e = a.e;
+  bool fused_heads = e.head_x != nullptr;
+  if constexpr (F16) fused_heads = a.x.head_x16 != nullptr;
   const float epsilon = e.eps[0];
   extern __shared__ float s_next[];                  // [2 SP]: next state | first state of the next episode
   __shared__ float s_ao[16];
@@ -148,18 +169,20 @@ static __global__ __launch_bounds__(256) void k_env_step(EnvDev e) {
   const unsigned long long g = e.g[w];
   GameState gs;                                      // fetched now, used at the end: its latency hides behind the heads
   if (tid == 0) gs = e.game[w];
-  const float head_bias = (e.head_x != nullptr && tid < kNO) ? e.head_b[tid] : 0.0f;   // likewise
+  const float head_bias = (fused_heads && tid < kNO) ? e.head_b[tid] : 0.0f;   // likewise
   // SelectAction(state, epsilon): ONE epsilon draw per call (src/dqn.cpp:700)
   const bool rnd = env_u01(e.seed, g, w, 0) < epsilon;
-  if (e.head_x != nullptr) {
+  if (fused_heads) {
     // SelectActionGreedily's last step for this worker: the 10 head outputs of its tower-top row — the separate head
     // launch of the batched step folded in.  Thread t owns the float4 k-strip t (+ 256 strips per round).
-    const float* x = e.head_x + (size_t)w * e.head_h;
+    const size_t x0 = (size_t)w * e.head_h;
+    const _Float16* x16 = nullptr;
+    if constexpr (F16) x16 = a.x.head_x16;
     float acc[kNO];
 #pragma unroll
     for (int j = 0; j < kNO; ++j) acc[j] = 0.0f;
     for (int k = tid * 4; k < e.head_h; k += 1024) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + k);
+      const f32x4 xv = head_ld4t<F16>(e.head_x, x16, x0 + k);
 #pragma unroll
       for (int j = 0; j < kNO; ++j) {
         const f32x4 wv = *reinterpret_cast<const f32x4*>(e.head_w + (size_t)j * e.head_h + k);
@@ -187,10 +210,10 @@ static __global__ __launch_bounds__(256) void k_env_step(EnvDev e) {
   if (tid < kAP) {
     float v = 0.0f;
     if (tid < kNO) {
-      if (e.head_x != nullptr) v = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) + head_bias;
+      if (fused_heads) v = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) + head_bias;
       else v = e.out16[(size_t)w * kAP + tid];       // written by the separate head launch
     }
-    if (e.head_x != nullptr) e.out16[(size_t)w * kAP + tid] = v;
+    if (fused_heads) e.out16[(size_t)w * kAP + tid] = v;
     if (tid < kNO && rnd) {                          // GetRandomActorOutput (src/dqn.cpp:664-682)
       const float u = env_u01(e.seed, g, w, 1 + tid);
       if (tid < kNA) v = fmaf(2.0f, u, -1.0f);
@@ -205,7 +228,10 @@ static __global__ __launch_bounds__(256) void k_env_step(EnvDev e) {
   // (src/dqn_main.cpp:97-105; the finished episode's transitions are labelled and added by k_env_flush, which
   // does not have to run before the next forward pass)
   const float* s_sel = status != 0 ? s_first : s_next;
-  for (int f = tid; f < e.SP; f += 256) cur[f] = s_sel[f];     // (thread f also made the ep_s copy of cur[f] above)
+  for (int f = tid; f < e.SP; f += 256) {                      // (thread f also made the ep_s copy of cur[f] above)
+    cur[f] = s_sel[f];
+    if constexpr (F16) { if (f < a.x.ldx16) a.x.x16[(size_t)w * a.x.ldx16 + f] = (_Float16)s_sel[f]; }
+  }
   if (wave == 0) {
     // the four angles of this step's (at most) two HFOGameState::update calls, one per lane: lanes 0 / 1 the ball and
     // goal angles of the next state, lanes 2 / 3 those of the new episode's first state

@@ -100,6 +100,39 @@ static __global__ void k_pack_critic(const float* __restrict__ s, const float* _
   if (r < n) { if (c < S) v = s[(size_t)r * S + c]; else if (c < S + kNO) v = a[(size_t)r * kNO + (c - S)]; }
   dst[i] = v;
 }
+// fp16 acting (dqnhip_set_act_precision): the same two panels in fp16, rounded to nearest even, [rows][k16] with k16 % 128 == 0.
+// One wave per row piece of 512 columns, a lane converts 8 consecutive columns and writes them with one 16-byte store.  Pad rows
+// (>= n) and pad columns are written as zero on EVERY call: the panel is reused between actor and critic passes of different
+// widths, and a stale Inf / NaN in a pad column times a zero weight is NaN.
+typedef __attribute__((ext_vector_type(8))) _Float16 pack_h8;
+// src: [n][ld_src] fp32, the first S columns of a row are the state; act (k_pack_critic16): dense actor outputs [n][10]
+struct Pack16Args { const float* src; const float* act; int n, S, ld_src; _Float16* dst; int rows, k16; };
+static __global__ __launch_bounds__(256) void k_pack_rows16(const Pack16Args p) {
+  const int ppr = (p.k16 + 511) / 512;                 // row pieces per row
+  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int r = gw / ppr, c = (gw % ppr) * 512 + lane * 8;
+  if (r >= p.rows || c >= p.k16) return;               // (k16 % 8 == 0: c < k16 means the whole piece is inside the row)
+  pack_h8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (_Float16)((r < p.n && c + e < p.S) ? p.src[(size_t)r * p.ld_src + c + e] : 0.0f);
+  *reinterpret_cast<pack_h8*>(p.dst + (size_t)r * p.k16 + c) = v;
+}
+// critic input panel [s | a | p] from dense states [n][S] (ld_src == S) + dense actor outputs
+static __global__ __launch_bounds__(256) void k_pack_critic16(const Pack16Args p) {
+  const int ppr = (p.k16 + 511) / 512;
+  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int r = gw / ppr, c = (gw % ppr) * 512 + lane * 8;
+  if (r >= p.rows || c >= p.k16) return;
+  pack_h8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int col = c + e;
+    float x = 0.0f;
+    if (r < p.n) { if (col < p.S) x = p.src[(size_t)r * p.ld_src + col]; else if (col < p.S + kNO) x = p.act[(size_t)r * kNO + (col - p.S)]; }
+    v[e] = (_Float16)x;
+  }
+  *reinterpret_cast<pack_h8*>(p.dst + (size_t)r * p.k16 + c) = v;
+}
 static __global__ void k_unpack_out(const float* __restrict__ out16, int n, float* __restrict__ dst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * kNO) return;

@@ -376,17 +376,27 @@ int sync_w16(H* h, hipStream_t st, int net) {
   return 0;
 }
 
-HGemm fwd16_problem(H* h, int p, int net, int rows, int i) {
+// layer i of `net` forward on the fp16 panels `panels` ([rows][k16[kind][.]]): the update's act16[p], or acting panels
+HGemm fwd16_problem(H* h, h16* const* panels, int net, int rows, int i) {
   const NetLayout& l = layout_of(h, net);
   const int kind = net & 1;
   HGemm g{};
-  g.A = h->act16[p][i]; g.lda = h->k16[kind][i];
+  g.A = panels[i]; g.lda = h->k16[kind][i];
   g.B = h->w16[net][i]; g.ldb = h->k16[kind][i];
   g.M = rows; g.N = l.dims[i + 1]; g.K = h->k16[kind][i];
-  g.C16 = h->act16[p][i + 1]; g.ldc16 = l.dims[i + 1];
+  g.C16 = panels[i + 1]; g.ldc16 = l.dims[i + 1];
   // (no fp32 copy of the tower top: the head kernels read the fp16 panel, as every tower layer reads its input)
   g.bias = h->w[net] + l.b_off[i]; g.relu = 1; g.scale32 = 1.0f;
   return g;
+}
+HGemm fwd16_problem(H* h, int p, int net, int rows, int i) { return fwd16_problem(h, h->act16[p], net, rows, i); }
+int tower_forward16_on(H* h, hipStream_t st, int net, h16* const* panels, int rows) {
+  if (!h->fp16) return fail("internal: fp16 tower forward on an fp32 learner");
+  if (rows < 64 || rows % 64) return fail("internal: fp16 tower forward needs whole 64-row tiles (got %d rows)", rows);
+  if (h->w16_dirty[net]) RC(sync_w16(h, st, net));
+  const NetLayout& l = layout_of(h, net);
+  for (int i = 0; i < l.L; ++i) RC(hgemm_timed(h, st, fwd16_problem(h, panels, net, rows, i), kFamHgemmFwd));
+  return 0;
 }
 int tower_forward16(H* h, hipStream_t st, int p, int net, int rows) {
   const NetLayout& l = layout_of(h, net);

@@ -27,6 +27,26 @@ int ensure_act(H* h, int rows) {
   return 0;
 }
 
+// fp16 acting panels for `rows` rows (a multiple of 64) of either net kind, zero-filled on allocation
+int ensure_act16(H* h, int rows) {
+  if (!h->fp16) return fail("internal: fp16 acting panels on an fp32 learner");
+  if (rows < 64 || rows % 64) return fail("internal: fp16 acting panels hold whole 64-row tiles (got %d rows)", rows);
+  if (rows <= h->actp16_rows) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i <= h->L; ++i) if (h->actp16[i]) { HIPCHK(hipFree(h->actp16[i])); h->actp16[i] = nullptr; }
+  if (h->actp16_out) { HIPCHK(hipFree(h->actp16_out)); h->actp16_out = nullptr; }
+  h->actp16_rows = 0;
+  for (int i = 0; i <= h->L; ++i) {
+    const size_t n = (size_t)rows * act16_width(h, i);
+    HIPCHK(hipMalloc(&h->actp16[i], n * sizeof(h16)));
+    HIPCHK(hipMemsetAsync(h->actp16[i], 0, n * sizeof(h16), h->stream));
+  }
+  HIPCHK(hipMalloc(&h->actp16_out, (size_t)rows * (kAP + 1) * sizeof(float)));
+  HIPCHK(hipMemsetAsync(h->actp16_out, 0, (size_t)rows * (kAP + 1) * sizeof(float), h->stream));
+  h->actp16_rows = rows;
+  return 0;
+}
+
 void drop_graphs(H* h) {
   for (auto& g : h->graph_exec) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   for (auto& g : h->graph_small) if (g) { hipGraphExecDestroy(g); g = nullptr; }
@@ -272,6 +292,8 @@ int dqnhip_destroy(dqnhip_handle h) {
   if (h->stage_dev) hipFree(h->stage_dev);
   if (h->shard_total) hipFree(h->shard_total);
   if (h->act_buf) hipFree(h->act_buf);
+  for (int i = 0; i <= h->L; ++i) if (h->actp16[i]) hipFree(h->actp16[i]);
+  if (h->actp16_out) hipFree(h->actp16_out);
   if (h->own_stream) hipStreamDestroy(h->stream);
   delete h;
   return 0;

@@ -22,6 +22,13 @@ struct dqnhip_env {
   // finished episodes) rides as extra workgroups of step t+1's first-layer launch: k_env_step resets the worker
   // itself, so nothing before the next k_env_step depends on the flush
   bool flush_deferred = false;
+  // fp16 acting (dqnhip_set_act_precision): the learner's switch as this handle last saw it — a changed epoch drops the captured
+  // steps — and fp16 panels of the env's own: p16[0] the actor's input panel k_env_step<true> writes, p16[i] layer i's output;
+  // [Npad16][k16[0][i]], whole 64-row hgemm tiles, zero-filled (the pad rows stay zero), allocated when the mode is first seen
+  unsigned long long act_epoch = 0;
+  bool f16 = false;
+  int Npad16 = 0;
+  h16* p16[kMaxL + 1] = {nullptr};
 };
 constexpr int kEnvUnroll = 16;
 
@@ -38,6 +45,20 @@ int env_alloc(dqnhip_env* e, T** p, size_t n) {
 extern "C" {
 
 static int env_create_impl(dqnhip_env* e);
+
+// the env's fp16 panels (allocated once, zero-filled) and the fp16 kernels' extra argument
+static int env_panels16(dqnhip_env* e) {
+  dqnhip_learner* h = e->h;
+  if (e->p16[0]) return 0;
+  if (h->k16[0][0] != e->d.SP) return fail("internal: the fp16 actor input panel is %d wide, the env's state rows %d", h->k16[0][0], e->d.SP);
+  e->Npad16 = act16_rows(e->d.N);
+  for (int i = 0; i <= h->L; ++i) RC(env_alloc(e, &e->p16[i], (size_t)e->Npad16 * h->k16[0][i]));
+  return 0;
+}
+static Env16 env16_of(const dqnhip_env* e, bool fused) {
+  Env16 x{}; x.x16 = e->p16[0]; x.ldx16 = e->h->k16[0][0]; x.head_x16 = fused ? e->p16[e->h->L] : nullptr;
+  return x;
+}
 
 int dqnhip_env_create(dqnhip_handle h, const dqnhip_env_config* cfg, dqnhip_env_handle* out) {
   if (!h || !cfg || !out) return fail("null argument");
@@ -74,7 +95,11 @@ static int env_create_impl(dqnhip_env* e) {
   for (int i = 1; i <= h->L; ++i) RC(env_alloc(e, &e->acts[i], Np * h->la.kp[i]));
   RC(env_alloc(e, &e->eps_dev, 16)); d.eps = e->eps_dev;
   RC(env_alloc(e, &e->commit_ticket, 32));
-  HIPCHK(launch(h->stream, k_env_init, dim3(d.N), dim3(64), d.SP * sizeof(float), d));
+  e->act_epoch = h->act_epoch; e->f16 = h->act_fp16;
+  if (e->f16) {
+    RC(env_panels16(e));
+    HIPCHK(launch(h->stream, k_env_init<true>, dim3(d.N), dim3(64), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}));
+  } else HIPCHK(launch(h->stream, k_env_init<false>, dim3(d.N), dim3(64), d.SP * sizeof(float), EnvArgs<false>{d}));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -106,7 +131,9 @@ static __global__ __launch_bounds__(256) void k_env_l0_flush(const GemmBatch bat
 }
 // one batched env step on the learner's stream: SelectActionGreedily for all workers, then the
 // per-worker epsilon draw / GetAction / reward / episode bookkeeping / AddTransitions
+static int env_one_step16(dqnhip_env* e);
 static int env_one_step(dqnhip_env* e, bool more_follow) {
+  if (e->f16) return env_one_step16(e);
   dqnhip_learner* h = e->h;
   EnvDev d = e->d;
   hipStream_t st = h->stream;
@@ -148,13 +175,60 @@ static int env_one_step(dqnhip_env* e, bool more_follow) {
     a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.b = wat(h, DQNHIP_ACTOR, la.hb_off); a.out16 = d.out16;
     RC((head_forward<kNO, HEAD_ACTOR>(h, st, a)));
   }
-  HIPCHK(launch(st, k_env_step, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), d));
+  HIPCHK(launch(st, k_env_step<false>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<false>{d}));
   if (more_follow && fused && l0_direct && !h->timing) { e->flush_deferred = true; return 0; }
   HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring,
                      (const DevState*)RO(h)->st, h->cfg.gamma));
   if (d.commit_ticket == nullptr) {
     HIPCHK(launch(st, k_env_commit, dim3(1), dim3(256), 0, d, RO(h)->ring, RO(h)->st));
   }
+  return 0;
+}
+
+// the same step in fp16 acting mode: L hgemm tower layers on the actor's fp16 mirror (tower_forward16_on, learner.hip), the heads on
+// the fp16 tower top — inside k_env_step<true> up to 512 workers, head_forward with HeadArgs::X16 above — then k_env_step<true>, which
+// writes the next fp16 input row itself (no pack launch), and the episode flush as a launch of its own: the deferred form rides in
+// the fp32 first-layer launch (k_env_l0_flush), which this mode does not have.  L + 2 launches per step at <= 512 workers (fp32 mode:
+// L + 1 inside a sequence), L + 4 above (as fp32 mode).
+static int env_one_step16(dqnhip_env* e) {
+  dqnhip_learner* h = e->h;
+  EnvDev d = e->d;
+  hipStream_t st = h->stream;
+  const NetLayout& la = h->la;
+  const bool fused = la.dims[la.L] % 4 == 0 && d.N <= 512;
+  if (fused) {
+    d.head_h = la.dims[la.L];
+    d.head_w = wat(h, DQNHIP_ACTOR, la.hw_off); d.head_b = wat(h, DQNHIP_ACTOR, la.hb_off);
+    d.commit_ticket = e->commit_ticket;
+  }
+  RC(tower_forward16_on(h, st, DQNHIP_ACTOR, e->p16, e->Npad16));
+  if (!fused) {
+    HeadArgs a{}; a.X16 = e->p16[la.L]; a.ldx = la.dims[la.L]; a.H = la.dims[la.L]; a.rows = e->Npad;
+    a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.b = wat(h, DQNHIP_ACTOR, la.hb_off); a.out16 = d.out16;
+    RC((head_forward<kNO, HEAD_ACTOR>(h, st, a)));
+  }
+  HIPCHK(launch(st, k_env_step<true>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, fused)}));
+  HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring,
+                     (const DevState*)RO(h)->st, h->cfg.gamma));
+  if (d.commit_ticket == nullptr) {
+    HIPCHK(launch(st, k_env_commit, dim3(1), dim3(256), 0, d, RO(h)->ring, RO(h)->st));
+  }
+  return 0;
+}
+
+// the learner's acting precision changed since this handle last looked: the captured steps are those of the other mode
+static int env_follow_act_precision(dqnhip_env* e) {
+  dqnhip_learner* h = e->h;
+  if (e->act_epoch == h->act_epoch) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 2; ++i) if (e->graph[i]) { HIPCHK(hipGraphExecDestroy(e->graph[i])); e->graph[i] = nullptr; }
+  e->graph_failed = false;
+  if (h->act_fp16) {
+    // the actor's input panel from the fp32 state rows, once; from here on k_env_step<true> keeps it current
+    RC(env_panels16(e));
+    RC(pack_rows16_launch(h->stream, e->d.cur, e->d.N, e->d.SP, e->d.SP, e->p16[0], e->Npad16, h->k16[0][0]));
+  }
+  e->f16 = h->act_fp16; e->act_epoch = h->act_epoch;
   return 0;
 }
 
@@ -184,6 +258,8 @@ int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
   RingUse ring_use(h);
+  RC(env_follow_act_precision(e));
+  if (e->f16) RC(sync_dirty16(h));          // (outside any capture: a captured step holds the tower launches only)
   HIPCHK(launch(st, k_set_float<0>, dim3(1), dim3(1), 0, e->eps_dev, epsilon));
   // the step is a fixed launch sequence (9 launches at L = 4, ~6 us each when launch-bound): replay it
   // as a hipGraph unless the learner's layers may be re-pointed (sharing) or graphs are off

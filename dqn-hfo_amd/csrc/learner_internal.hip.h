@@ -204,6 +204,15 @@ struct dqnhip_learner {
   h16* dZ16[2][kMaxL + 1] = {{nullptr}};     // [B][k16]   per net kind
   bool w16_dirty[4] = {true, true, true, true};
   std::vector<void*> allocs16;
+  // fp16 acting (dqnhip_set_act_precision): a host flag and an epoch (an env handle compares it and drops its captured steps),
+  // and acting panels of their own — act16[] belong to the update and hold B rows.  actp16[i]: [actp16_rows][max(k16[0][i],
+  // k16[1][i])] (a pass uses its net kind's k16 as the row pitch), actp16_out: [actp16_rows][kAP + 1] floats (head outputs / q);
+  // rows are a multiple of 64, the smallest hgemm tile (ensure_act16 grows them, zero-filled)
+  bool act_fp16 = false;
+  unsigned long long act_epoch = 0;
+  h16* actp16[kMaxL + 1] = {nullptr};
+  float* actp16_out = nullptr;
+  int actp16_rows = 0;
   // host-staging for add_transitions / acting
   void* stage_dev = nullptr; size_t stage_bytes = 0;
   float* act_buf = nullptr; size_t act_floats = 0;
@@ -306,6 +315,10 @@ struct FwdPass { int net; const NetLayout* l; float** act; const float* seed_w =
 
 int layer_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, int i);
 int tower_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, int first_layer = 0);   // first_layer 1: layer 0 came out of a FirstLayerRider
+// the fp16 tower of `net` on caller-supplied panels: panels[i] is [rows][k16[net & 1][i]] fp16, rows % 64 == 0; layer i reads
+// panels[i] and the net's fp16 weight mirror and writes panels[i + 1].  A dirty mirror (set_params, Load*, Restore*, CloneNet) is
+// brought up to date first — not while `st` is capturing: the caller of a capture runs sync_dirty16 before it begins
+int tower_forward16_on(H* h, hipStream_t st, int net, h16* const* panels, int rows);
 // head_forward<NH, MODE>: head_fwd_kernels.hip.h (a template that names kernels: its users include it)
 constexpr int kMultiU = 16;    // updates per replay of the multi-update graph (dqnhip_update_async_n; see learner_update.hip)
 // Philox key of SampleTransitionsFromMemory: cfg.seed on rank 0 (what oracle/c_oracle.philox_indices
@@ -364,6 +377,9 @@ int ix_harvest_all(H* h);                                // waits for every inde
 // learner_create.hip
 int ensure_stage(H* h, size_t bytes);
 int ensure_act(H* h, int rows);
+inline int act16_rows(int n) { return round_up(n, 64); }                  // acting-panel rows for n inputs: whole 64-row hgemm tiles
+inline int act16_width(const H* h, int i) { return std::max(h->k16[0][i], h->k16[1][i]); }
+int ensure_act16(H* h, int rows);                        // the fp16 acting panels (H::actp16, actp16_out) for `rows` rows
 void drop_graphs(H* h);                                  // every captured launch sequence of this learner
 // learner_dp.hip
 int dp_reduce_slice(H* h, hipStream_t st, int net, size_t off, size_t count);
@@ -372,5 +388,7 @@ int dp_destroy_impl(H* h, bool keep_learner);
 const char* rccl_path();
 // learner_io.hip
 bool same_nets(const H* a, const H* b);
+// k_pack_rows16: fp32 [n][ld_src] (the first S columns of each row) -> fp16 [rows][k16], pad rows and columns zero
+int pack_rows16_launch(hipStream_t st, const float* src, int n, int S, int ld_src, h16* dst, int rows, int k16);
 
 }  // namespace dqnhip_host

@@ -11,9 +11,27 @@ extern "C" {
 
 // ---- acting ------------------------------------------------------------------------
 
+static int pack_blocks16(int rows, int k16) { return (rows * ((k16 + 511) / 512) + 3) / 4; }   // 4 waves per block, one per row piece
+
+// fp16 acting (dqnhip_set_act_precision): the forward the update's own passes compute — fp16 input panel, hgemm layers on the
+// net's fp16 mirror (tower_forward16_on, learner.hip), the fp32 heads on the fp16 tower top
+static int actor_forward16_dev(H* h, int net, const float* states_dev, int n, float* out_dev) {
+  const int rows = act16_rows(n);
+  RC(ensure_act16(h, rows));
+  const NetLayout& l = h->la;
+  RC(pack_rows16_launch(h->stream, states_dev, n, h->S, h->S, h->actp16[0], rows, h->k16[0][0]));
+  RC(tower_forward16_on(h, h->stream, net, h->actp16, rows));
+  HeadArgs a{}; a.X16 = h->actp16[l.L]; a.ldx = l.dims[l.L]; a.H = l.dims[l.L]; a.rows = rows;
+  a.W = wat(h, net, l.hw_off); a.b = wat(h, net, l.hb_off); a.out16 = h->actp16_out;
+  RC((head_forward<kNO, HEAD_ACTOR>(h, h->stream, a)));
+  HIPCHK(launch(h->stream, k_unpack_out, dim3((n * kNO + 255) / 256), dim3(256), 0, (const float*)h->actp16_out, n, out_dev));
+  return 0;
+}
+
 static int actor_forward_dev(H* h, int net, const float* states_dev, int n, float* out_dev) {
   if (n < 1) return fail("n must be >= 1");
   if (net != DQNHIP_ACTOR && net != DQNHIP_ACTOR_TARGET) return fail("net must be an actor");
+  if (h->act_fp16) return actor_forward16_dev(h, net, states_dev, n, out_dev);
   const int rows = round_up(n, 32);
   RC(ensure_act(h, rows));
   const NetLayout& l = h->la;
@@ -57,12 +75,34 @@ int dqnhip_select_actions(dqnhip_handle h, const float* states_host, int32_t n, 
   return dqnhip_select_actions_net(h, DQNHIP_ACTOR, states_host, n, actor_out_host);
 }
 
+static int critic_forward16(H* h, int net, const float* states_host, const float* actor_out_host, int n, float* q_host) {
+  const int rows = act16_rows(n);
+  const size_t sb = round_up_z((size_t)n * h->S * sizeof(float), 256), ab = round_up_z((size_t)n * kNO * sizeof(float), 256);
+  RC(ensure_stage(h, sb + ab));
+  float* sdev = (float*)h->stage_dev;
+  float* adev = (float*)((char*)h->stage_dev + sb);
+  HIPCHK(hipMemcpyAsync(sdev, states_host, (size_t)n * h->S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(adev, actor_out_host, (size_t)n * kNO * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  RC(ensure_act16(h, rows));
+  const NetLayout& l = h->lc;
+  HIPCHK(launch(h->stream, k_pack_critic16, dim3(pack_blocks16(rows, h->k16[1][0])), dim3(256), 0,
+                Pack16Args{sdev, adev, n, h->S, h->S, h->actp16[0], rows, h->k16[1][0]}));
+  RC(tower_forward16_on(h, h->stream, net, h->actp16, rows));
+  HeadArgs a{}; a.X16 = h->actp16[l.L]; a.ldx = l.dims[l.L]; a.H = l.dims[l.L]; a.rows = rows;
+  a.W = wat(h, net, l.hw_off); a.b = wat(h, net, l.hb_off); a.q = h->actp16_out;      // [rows] floats of the [rows][kAP + 1] scratch
+  RC((head_forward<1, HEAD_Q>(h, h->stream, a)));
+  HIPCHK(hipMemcpyAsync(q_host, h->actp16_out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int dqnhip_critic_forward(dqnhip_handle h, int32_t net, const float* states_host, const float* actor_out_host,
                           int32_t n, float* q_host) {
   if (!h) return fail("null handle");
   if (n < 1) return fail("n must be >= 1");
   if (net != DQNHIP_CRITIC && net != DQNHIP_CRITIC_TARGET) return fail("net must be a critic");
   HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->act_fp16) return critic_forward16(h, net, states_host, actor_out_host, n, q_host);
   const int rows = round_up(n, 32);
   const size_t sb = round_up_z((size_t)n * h->S * sizeof(float), 256), ab = round_up_z((size_t)n * kNO * sizeof(float), 256);
   RC(ensure_stage(h, sb + ab + (size_t)rows * sizeof(float)));
@@ -85,6 +125,22 @@ int dqnhip_critic_forward(dqnhip_handle h, int32_t net, const float* states_host
   RC((head_forward<1, HEAD_Q>(h, h->stream, a)));
   HIPCHK(hipMemcpyAsync(q_host, qdev, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dqnhip_set_act_precision(dqnhip_handle h, int32_t precision) {
+  if (!h) return fail("null handle");
+  if (precision != DQNHIP_FP32 && precision != DQNHIP_FP16) return fail("act precision must be DQNHIP_FP32 or DQNHIP_FP16 (got %d)", precision);
+  if (precision == DQNHIP_FP16 && !h->fp16)
+    return fail("act precision DQNHIP_FP16 needs a learner created with precision = DQNHIP_FP16 (this one has precision = DQNHIP_FP32: no fp16 weight mirrors)");
+  const bool on = precision == DQNHIP_FP16;
+  if (on != h->act_fp16) { h->act_fp16 = on; h->act_epoch += 1; }     // (env handles compare the epoch; the update path reads neither)
+  return 0;
+}
+
+int dqnhip_get_act_precision(dqnhip_handle h, int32_t* precision) {
+  if (!h || !precision) return fail("null argument");
+  *precision = h->act_fp16 ? DQNHIP_FP16 : DQNHIP_FP32;
   return 0;
 }
 
@@ -434,6 +490,10 @@ int dqnhip_clone_to_target(dqnhip_handle h, int32_t net) {
 
 }  // extern "C"
 namespace dqnhip_host {
+int pack_rows16_launch(hipStream_t st, const float* src, int n, int S, int ld_src, h16* dst, int rows, int k16) {
+  HIPCHK(launch(st, k_pack_rows16, dim3(pack_blocks16(rows, k16)), dim3(256), 0, Pack16Args{src, nullptr, n, S, ld_src, dst, rows, k16}));
+  return 0;
+}
 bool same_nets(const H* a, const H* b) {
   if (a->S != b->S || a->L != b->L) return false;
   for (int i = 0; i < a->L; ++i) if (a->cfg.hidden[i] != b->cfg.hidden[i]) return false;

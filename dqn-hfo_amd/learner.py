@@ -85,7 +85,8 @@ class DQN:
                  momentum=0.95, momentum2=0.999, clip_grad=10.0, memory_threshold=1000, seed=1,
                  device=0, dp_world=1, dp_rank=0, use_graph=False, stream=None, grad_arena=None,
                  grad_arena_bytes=0, tid=0, save_path="state/dqn", precision="fp32", loss_scale=0.0, tuning=0,
-                 loss_scale_mode="static", loss_scale_growth_interval=None, loss_scale_min_mult=None, loss_scale_max_mult=None):
+                 loss_scale_mode="static", loss_scale_growth_interval=None, loss_scale_min_mult=None, loss_scale_max_mult=None,
+                 act_precision="fp32"):
         self.lib = capi.load()
         cfg = capi.Config()
         self.lib.dqnhip_default_config(C.byref(cfg), state_size)
@@ -130,6 +131,12 @@ class DQN:
         self.last_snapshot_iter_ = 0
         self.snapshot_freq = 10000                      # FLAGS_snapshot_freq, src/dqn.cpp:28
         self.select_actions_cap = 0                     # 0: the reference's cap (the minibatch, src/dqn.cpp:699); -1: none; n: n
+        if act_precision != "fp32":
+            try:
+                self.set_act_precision(act_precision)
+            except Exception:
+                self.close()
+                raise
 
     # -- plumbing -----------------------------------------------------------------
     @staticmethod
@@ -297,6 +304,19 @@ class DQN:
         ao[8] = g.uniform(0.0, 100.0)
         ao[9] = g.uniform(-180.0, 180.0)
         return ao
+
+    def set_act_precision(self, precision):
+        """"fp32" (default): acting runs the exact-fp32 kernels on the master weights.  "fp16" (fp16 learners only): acting computes
+        what the update's own forward passes compute, on the fp16 weight mirrors (dqnhip_set_act_precision).  Launches nothing."""
+        if precision not in ("fp32", "fp16"):
+            raise DQNFatal("act_precision must be 'fp32' or 'fp16' (got %r)" % (precision,))
+        self._ck(self.lib.dqnhip_set_act_precision(self.h, {"fp32": capi.FP32, "fp16": capi.FP16}[precision]))
+
+    @property
+    def act_precision(self):
+        v = C.c_int32()
+        self._ck(self.lib.dqnhip_get_act_precision(self.h, C.byref(v)))
+        return "fp16" if v.value == capi.FP16 else "fp32"
 
     def SelectActionGreedily(self, states_batch, net=ACTOR):
         s = _f32(states_batch).reshape(-1, self.state_size_)

@@ -461,6 +461,24 @@ int dqnhip_select_actions_net(dqnhip_handle h, int32_t net,
 int dqnhip_critic_forward(dqnhip_handle h, int32_t net, const float* states_host,
                           const float* actor_out_host, int32_t n, float* q_host);
 
+/* Acting precision of an fp16 learner (no reference counterpart: the reference acts and trains with one
+ * Caffe net, src/dqn.cpp:734-766 and :982-1020 run the nets :828-972 updates).  A runtime switch, per learner:
+ *   DQNHIP_FP32 (default)  dqnhip_select_actions*, dqnhip_critic_forward and the greedy branch of
+ *                          dqnhip_env_step run the exact-fp32 GEMMs on the fp32 master weights, with the
+ *                          kernels and launch arguments they had before this switch existed;
+ *   DQNHIP_FP16            the same entry points compute what the update's own forward passes compute:
+ *                          inputs (states; [s | a | p] for a critic) rounded to fp16, round to nearest even;
+ *                          every tower layer an fp16-MFMA GEMM on the net's fp16 weight mirror with fp32
+ *                          accumulation, fp32 bias, leaky ReLU, stored as an fp16 panel; the heads fp32
+ *                          weights on the fp16 tower top with fp32 accumulation.  The behaviour policy is
+ *                          then the function mu(s) the update differentiates.  Inputs beyond the fp16
+ *                          range (|x| > 65504 becomes +-Inf) are the caller's business.
+ * DQNHIP_FP16 needs cfg.precision == DQNHIP_FP16 (refused otherwise).  The call launches nothing and does
+ * not wait: an env handle notices the change at its next dqnhip_env_step and captures its step anew; the
+ * learner's captured updates are untouched (the update path does not read the switch). */
+int dqnhip_set_act_precision(dqnhip_handle h, int32_t precision);   /* DQNHIP_FP32 (default) | DQNHIP_FP16 */
+int dqnhip_get_act_precision(dqnhip_handle h, int32_t* precision);
+
 /* Replaces DQN::AddTransitions (src/dqn.cpp:775-781): FIFO-evicts while
  * size + n >= capacity, then appends n transitions.  terminal[i] != 0 means
  * next_state == boost::none (src/dqn.cpp:878); next_states rows of terminal
