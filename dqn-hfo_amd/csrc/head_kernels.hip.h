@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
   int blk = (int)blockIdx.x;
   if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred), "s"(a.ls_mult));
   else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
-  const int tiles = a.row_tiles * ((a.H + 255) >> 8);
+  const int tiles = a.row_tiles * (a.dxc != nullptr ? 1 : (a.H + 255) >> 8);
   if (blk >= tiles) { q_head_rider(rider, blk - tiles); return; }
   const int rt = blk % a.row_tiles, cc = blk / a.row_tiles;
   const int tid = threadIdx.x, q0 = rt * 16;
@@ -399,6 +399,10 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
     s_d[li][(lg << 2) + 0] = v.x; s_d[li][(lg << 2) + 1] = v.y; s_d[li][(lg << 2) + 2] = v.z; s_d[li][(lg << 2) + 3] = v.w;
   }
   __syncthreads();
+  if (a.dxc != nullptr) {                  // (uniform) the separate form: dQ/da itself, for k_head_bwd<10>
+    if (tid < 16 * kNO) a.dxc[(size_t)(q0 + tid / kNO) * a.lddxc + tid % kNO] = s_d[tid / kNO][tid % kNO];
+    return;
+  }
   if (tid < 16 * kNO) {                    // inverting gradients (k_head_bwd<10>'s staging loop)
     const int r = tid / kNO, j = tid % kNO;
     float d = s_d[r][j];
@@ -430,7 +434,8 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
 inline hipError_t dqda_head_bwd_launch(DqdaHeadArgs& a, const QHeadRider& rider, const LaunchOn& on) {
   a.row_tiles = a.rows / 16;
   a.pr.tiles_p = 1; a.pr.tiles_q = a.row_tiles; a.pr.tile_base = 0;
-  const dim3 grid(a.row_tiles * ((a.H + 255) / 256) + rider.blocks);
+  // (dxc given: the tile alone, column chunk 0 of every row tile)
+  const dim3 grid(a.row_tiles * (a.dxc != nullptr ? 1 : (a.H + 255) / 256) + rider.blocks);
   if (a.dZ16 != nullptr) return launch(on, k_dqda_head_bwd<true>, grid, dim3(256), kNarrowDgradLds, a, rider);
   return launch(on, k_dqda_head_bwd<false>, grid, dim3(256), kNarrowDgradLds, a, rider);
 }

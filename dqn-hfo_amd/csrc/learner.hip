@@ -618,14 +618,19 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       if (head_big_ok(h, B, Hc)) { a.dZ = nullptr; RC(head_backward_big<1>(h, st, a, h->dZ16[1][L], h->ls_q)); }
       else { a.dZ16 = h->dZ16[1][L]; a.scale16 = h->ls_q; RC(head_backward<1>(h, st, a)); }
     }
-    RC(tower_backward16(h, st, DQNHIP_CRITIC, 4, nullptr, h->dZc[0], B, false, !P.fuse_head, h->ls_q, lsm_a));       // (fuse_head: layers L-1 .. 1 only)
-    if (P.fuse_head) {
+    // DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD where the fused form would apply: the same tile in a launch of its own (k_dqda_head_bwd<true> with
+    // DqdaHeadArgs::dxc: dQ/da into the action columns of dZc[0], no head part) + k_head_bwd<10> below — the fused form's arithmetic, cut in
+    // two, as on the fp32 path.  Other shapes: the fp16-MFMA layer-0 dgrad launch of tower_backward16
+    const bool tile_alone = !P.fuse_head && P.head_rides_a && dqda_head_shape_ok(h, h->k16[1][0]);
+    RC(tower_backward16(h, st, DQNHIP_CRITIC, 4, nullptr, h->dZc[0], B, false, !P.fuse_head && !tile_alone, h->ls_q, lsm_a));       // (else: layers L-1 .. 1 only)
+    if (P.fuse_head || tile_alone) {
       DqdaHeadArgs fz{};
+      if (tile_alone) { fz.dxc = h->dZc[0] + h->S; fz.lddxc = lc.kp[0]; }
       fz.aout16 = h->aout16; fz.dA16 = h->dA16; fz.W = wat(h, DQNHIP_ACTOR, la.hw_off); fz.H = Hh; fz.rows = B;
       fz.t16 = NarrowTile16{h->w16[DQNHIP_CRITIC][0] + h->S, h->k16[1][0], h->dZ16[1][1], lc.dims[1], lc.dims[1]}; fz.inv_ls = 1.0f / h->ls_q;
       fz.X416 = h->act16[1][L]; fz.dZ16 = h->dZ16[0][L]; fz.scale16 = h->ls_a; fz.ls_mult = lsm_a;
       // (DQNHIP_TUNE_SEPARATE_HEAD_SEED: q(s, mu(s)) came out of the dq = -1 head launch — no rider blocks)
-      const QHeadRider qr{nullptr, wat(h, DQNHIP_CRITIC, lc.hw_off), wat(h, DQNHIP_CRITIC, lc.hb_off), h->q2, h->q_partial, Hc, B, fused_seed ? (B + 3) / 4 : 0, h->act16[4][L]};
+      const QHeadRider qr{nullptr, wat(h, DQNHIP_CRITIC, lc.hw_off), wat(h, DQNHIP_CRITIC, lc.hb_off), h->q2, h->q_partial, Hc, B, fused_seed && !tile_alone ? (B + 3) / 4 : 0, h->act16[4][L]};
       HIPCHK(dqda_head_bwd_launch(fz, qr, st));
     }
     {

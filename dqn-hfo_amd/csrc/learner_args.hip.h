@@ -226,6 +226,10 @@ struct DqdaHeadArgs {
   // dynamic loss scaling: {mult, 1 / mult} of the actor (DevState::ls_mult[0]) — inv_ls is multiplied by ls_mult[1] (the incoming panel
   // carries ls_q x mult), scale16 by ls_mult[0] (the outgoing one carries ls_a x mult); null: static
   const float* ls_mult;
+  // DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD on the fp16 learner: the launch only forms the tile and leaves its ten action columns, times
+  // inv_ls, at dxc[row * lddxc + j] (the critic's first-layer input gradient panel at its first action column) for k_head_bwd<10>;
+  // one workgroup per row tile, no head part.  Null: the fused form
+  float* dxc; int lddxc;
 };
 
 // k_head_bwd_big / k_head_wred

@@ -305,6 +305,7 @@ bool is_pow2(float x);                                   // a positive, normal p
 bool bwd_layer_is_pair(const NetLayout& l, int i, int rows);
 bool bwd_is_shifted(const H* h, const NetLayout& l, int rows);
 bool head_big_ok(const H* h, int rows, int Hd);
+bool dqda_head_shape_ok(const H* h, int panel_w);   // k_dqda_head_bwd's shapes (the fused form, and the fp16 learner's tile-alone launch)
 bool early_l0(const H* h);                               // plan_of(h).early_l0 while a multi-update graph is being captured
 inline size_t grad_arena_floats(const NetLayout& la, const NetLayout& lc) { return la.arena + 64 + lc.arena + 64; }
 

@@ -612,6 +612,33 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
     } else HIPCHK(hipMemcpy(host, h->act[p][i], B * W * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   }
+  else if (!strcmp(name, "dq")) src = h->dq;
+  else if (!strcmp(name, "actor_target_out")) { src = h->aout_t16; pad16 = true; n = B * kNO; }
+  else if (!strcmp(name, "dz_c") || !strcmp(name, "dz_a")) {
+    // the tower-top gradient the head-backward forms leave for the tower, dense [B][H] (the pitch the head kernels write with);
+    // fp16 learner: the scaled fp16 panel, widened as stored
+    const int kind = name[3] == 'c';
+    const NetLayout& l = layout_of(h, kind);
+    const size_t W = l.dims[h->L];
+    if (count < B * W) return fail("buffer too small for '%s': %zu < %zu", name, count, B * W);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->fp16) {
+      std::vector<h16> t16(B * W);
+      HIPCHK(hipMemcpy(t16.data(), h->dZ16[kind][h->L], t16.size() * sizeof(h16), hipMemcpyDeviceToHost));
+      for (size_t e = 0; e < t16.size(); ++e) host[e] = (float)t16[e];
+    } else HIPCHK(hipMemcpy(host, kind ? h->dZc[h->L] : h->dZa[h->L], B * W * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  else if (!strcmp(name, "dxc")) {
+    if (plan_of(h).fuse_head) return fail("debug buffer 'dxc': this learner's plan fuses dQ/da into the actor heads' backward (k_dqda_head_bwd) and never writes it; create the learner with DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD");
+    const size_t ld = h->lc.kp[0];
+    if (count < B * kNO) return fail("buffer too small for '%s': %zu < %zu", name, count, B * (size_t)kNO);
+    std::vector<float> t(B * ld);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(t.data(), h->dZc[0], t.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < B; ++r) for (int c = 0; c < kNO; ++c) host[r * kNO + c] = t[r * ld + h->S + c];
+    return 0;
+  }
   else return fail("unknown debug buffer '%s'", name);
   if (count < n) return fail("buffer too small for '%s': %zu < %zu", name, count, n);
   std::vector<float> tmp(pad16 ? B * kAP : B);

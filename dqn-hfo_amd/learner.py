@@ -617,7 +617,12 @@ class DQN:
             out = np.empty(B * width, np.float32)
             self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
             return out.reshape(B, width)
-        wide = name in ("actor_out", "dq_da")
+        if name in ("dz_c", "dz_a"):      # tower-top gradients [B][last hidden width] (fp16 learner: the scaled panel, widened)
+            width = self.cfg.hidden[self.cfg.num_hidden - 1]
+            out = np.empty(B * width, np.float32)
+            self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
+            return out.reshape(B, width)
+        wide = name in ("actor_out", "dq_da", "actor_target_out", "dxc")
         out = np.empty(B * (10 if wide else 1), np.float32)
         self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
         return out.reshape(B, 10) if wide else out

@@ -149,8 +149,8 @@ typedef struct dqnhip_config {
 #define DQNHIP_TUNE_BWD_UNSHIFTED 4
 /* The critic's first-layer action-column input gradient in a launch of its own (+ the q riders) and the inverting gradients + actor
  * heads' backward in another (k_head_bwd<10>), instead of all three in one launch (k_dqda_head_bwd, round 5; any tower-top width and
- * the fp16 learner below 1024 rows since round 6 — there the separate form is the fp16-MFMA layer-0 dgrad launch, and the two agree
- * to fp32 round-off instead of bit for bit). */
+ * the fp16 learner below 1024 rows since round 6 — there the launch of its own is k_dqda_head_bwd<true> forming the tile alone,
+ * DqdaHeadArgs::dxc, so that both precisions cut the fused form's arithmetic in two: bit-identical dQ/da). */
 #define DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD 8
 /* fp32 learner: Step(1)'s head arithmetic (q', q, TD target, loss, dq, the tower-top gradient) in a launch of its own
  * (k_head_q_train) instead of inside the critic's top-layer dgrad launch (k_dgrad_qtrain, round 5: the two head dot products
@@ -615,6 +615,18 @@ int dqnhip_remove_snapshots(const char* regexp, int32_t min_iter);
  * inverting-gradients), "idx" [B] (as float), "terminal" [B];
  * "indexed_graph_launches" [1]: the kernel nodes of the sixteen-update graph dqnhip_update_indexed_n has captured (0: none
  * captured, or dropped since - sharing, set-up of data parallelism).
+ * What the head layers hand on, for per-element tests between the phases of dqnhip_update_phase:
+ * "dq" [B]: Step(1)'s loss diff (q - y) / B, valid after phase 0;
+ * "actor_target_out" [B,10]: mu'(s'), valid after phase 0;
+ * "dz_c" / "dz_a" [B,H]: the critic's / actor's tower-top gradient (H = the last hidden width).  dz_c holds Step(1)'s after
+ *   phase 0; phase 1 OVERWRITES it with the dq = -1 seed of the dQ/da pass (read Step(1)'s between the phases).  dz_a is
+ *   written by phase 1.  The fp16 learner returns its fp16 panels widened to float as stored, i.e. still times the pass's
+ *   loss scale (critic: loss_scale, seed: the dQ/da pass's, actor: the actor's);
+ * "dxc" [B,10]: the action columns of the critic's first-layer input gradient, i.e. dQ/da BEFORE the inverting gradients,
+ *   valid after phase 1.  Fails on a learner whose plan has DQNHIP_PLAN_DQDA_HEAD_BWD: that form keeps dQ/da in LDS and
+ *   never writes the buffer (DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD restores it).
+ * Nothing else in an update overwrites these before the phase that wrote them returns; after a whole update they hold what
+ * phase 1 left (dz_c: the seed).
  * count = floats the caller's buffer holds; fails if too small. */
 int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
 

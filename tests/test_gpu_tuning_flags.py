@@ -323,10 +323,10 @@ def test_early_gather_and_next_update_first_layers_equal_the_late_form(pkg, gpu,
 @pytest.mark.parametrize("B,hidden", [(128, (256, 128, 128)), (512, (1024, 1024, 1024, 1024)), (256, (256, 256))])
 def test_fp16_fused_dqda_head_bwd_against_separate_launches(pkg, gpu, B, hidden):
     """fp16 learner (round 6): the critic's layer-0 input gradient (ten action columns), the inverting gradients and the actor heads'
-    backward in ONE launch (k_dqda_head_bwd<true>) against the fp16-MFMA layer-0 dgrad launch + k_head_bwd<10>
-    (DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD).  Same fp16 operands, exact products; the fp32 additions of the 16-column tile run in
-    another order (16x16x4 fp32 MFMA chains on converted operands against the 32x32x16 fp16 MFMA), so the two agree to fp32
-    round-off before the tower-top gradient is rounded to fp16 — not bit for bit."""
+    backward in ONE launch (k_dqda_head_bwd<true>) against the separate launches (DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD): the same
+    tile in a launch of its own (DqdaHeadArgs::dxc) + k_head_bwd<10>.  (Until the head-layer tests the separate form was the
+    fp16-MFMA layer-0 dgrad launch, which adds the same exact products in another order: the tolerances below date from then;
+    tests/test_gpu_head_layers.py holds dq_da of the pair to bit identity.)"""
     a = _run(pkg, 0, B, hidden)
     b = _run(pkg, pkg.capi.TUNE_SEPARATE_ACTOR_HEAD_BWD, B, hidden)
     assert np.allclose(a[0], b[0], rtol=2e-4, atol=2e-6), (a[0], b[0])
