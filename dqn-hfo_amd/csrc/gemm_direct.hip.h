@@ -33,6 +33,7 @@
 #include <cstdlib>
 
 #include "gemm_bodies.hip.h"
+#include "gemm_plan.hip.h"         // GemmForm, gemm_form_accepts
 
 namespace dqnhip {
 
@@ -339,6 +340,35 @@ inline hipError_t bwd_seq_launch(GemmBatch& batch, const LaunchOn& on) {
   GemmArgs<2> args;
   if (batch.n != 2 || !pack_args(batch, args, false)) return hipErrorInvalidValue;
   return launch(on, gemm_bwd_seq<DLDS>, dim3(grid), dim3(256), kBwdTileLds, args);
+}
+// ONE launch of a form of gemm_plan.hip.h: the only place that names the launcher instances.  Refuses what the form does not accept
+// before anything is launched.  rider / tails: the head's dW / db rider blocks and the tails block, which the tail forms alone carry.
+// (A template, like direct_prepare_all below: only a unit that calls it instantiates — and embeds — the kernels it names.)
+template <int UNUSED = 0>
+inline hipError_t gemm_form_launch(int form, GemmBatch& b, const LaunchOn& on, const HeadWgradRider* rider = nullptr, const TailsArgs* tails = nullptr) {
+  if (!gemm_form_accepts(form, b)) return hipErrorInvalidValue;
+  const bool tail = form == GEMM_FORM_WGRAD_TAIL_1 || form == GEMM_FORM_WGRAD_TAIL_NO;
+  if (!tail && (rider != nullptr || tails != nullptr)) return hipErrorInvalidValue;
+  const HeadWgradRider no_rider{};     // blocks = 0
+  switch (form) {
+    case GEMM_FORM_FWD_DIRECT_2x2: return fwd_direct_launch<2, 2>(b, on);
+    case GEMM_FORM_FWD_DIRECT_4x2: return fwd_direct_launch<4, 2>(b, on);
+    case GEMM_FORM_FWD_LDS_1x1: return fwd_lds_launch<1, 1, true>(b, on);
+    case GEMM_FORM_FWD_LDS_2x2: return fwd_lds_launch<2, 2, true>(b, on);
+    case GEMM_FORM_FWD_LDS_4x2: return fwd_lds_launch<4, 2, true>(b, on);
+    case GEMM_FORM_FWD_LDS_4x2_ONE_IMAGE: return fwd_lds_launch<4, 2, true, 1>(b, on);
+    case GEMM_FORM_DGRAD_DIRECT: return dgrad_direct_launch<1, 1>(b, on);
+    case GEMM_FORM_DGRAD_LDS: return dgrad_lds_launch<1, 1>(b, on);
+    case GEMM_FORM_DGRAD_NARROW: return dgrad_narrow_launch(b, on);
+    case GEMM_FORM_WGRAD_NARROW: return wgrad_narrow_launch<1>(b, on);
+    case GEMM_FORM_BWD_SEQ: return bwd_seq_launch<false>(b, on);
+    case GEMM_FORM_BWD_SEQ_LDS: return bwd_seq_launch<true>(b, on);
+    case GEMM_FORM_BWD_PAIR: return bwd_pair_direct_launch<1, false>(b, on);
+    case GEMM_FORM_BWD_PAIR_LDS: return bwd_pair_direct_launch<1, true>(b, on);
+    case GEMM_FORM_WGRAD_TAIL_1: return wgrad_tail_launch<1>(b, rider ? *rider : no_rider, on, tails);
+    case GEMM_FORM_WGRAD_TAIL_NO: return wgrad_tail_launch<kNO>(b, rider ? *rider : no_rider, on, tails);
+  }
+  return hipErrorInvalidValue;
 }
 template <typename K>
 inline hipError_t direct_prepare(K kernel, int lds_bytes) {

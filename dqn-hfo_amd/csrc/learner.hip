@@ -21,6 +21,28 @@ namespace dqnhip_host {
 
 const char* const kFamily[kNumFamily] = {"gemm_fwd_lds_4x2", "gemm_dgrad", "gemm_wgrad", "adam", "gemm_bwd_pair", "gemm_fwd_lds_2x2", "gemm_fwd_direct",
                                          "hgemm_fwd", "hgemm_dgrad", "hgemm_wgrad"};      // by Family
+// The timing family of a launch of an fp32 GEMM form (gemm_plan.hip.h) with n problems.  The forward LDS families go by the number
+// of problems, not by the tile: a single problem — the 16x16 tile included — files under gemm_fwd_lds_2x2, a grouped launch of any
+// tile under gemm_fwd_lds_4x2.
+static Family family_of(GemmForm f, int n) {
+  switch (kGemmForms[f].kind) {
+    case GEMM_KIND_FWD_DIRECT: return kFamFwdDirect;
+    case GEMM_KIND_FWD_LDS: return n == 1 ? kFamFwdLds2x2 : kFamFwdLds4x2;
+    case GEMM_KIND_DGRAD: case GEMM_KIND_DGRAD_NARROW: return kFamDgrad;
+    case GEMM_KIND_BWD: return kFamBwdPair;
+    case GEMM_KIND_WGRAD_NARROW: case GEMM_KIND_TAIL: break;
+  }
+  return kFamWgrad;
+}
+// a rider launcher (head_kernels.hip.h) is keyed on the form it extends and takes that form's problems: the same precondition
+static int form_check(GemmForm f, const GemmBatch& b) {
+  return gemm_form_accepts(f, b) ? 0 : fail("internal: the carrier %s of a rider does not accept its problems", kGemmForms[f].name);
+}
+// one launch of form f (rider / tails: what a tail form carries), timed under its family
+static int form_launch(H* h, hipStream_t st, GemmForm f, GemmBatch& b, const HeadWgradRider* rider = nullptr, const TailsArgs* tails = nullptr) {
+  HIPCHK(gemm_form_launch(f, b, timed(h, family_of(f, b.n), st), rider, tails));
+  return 0;
+}
 
 // ---- forward / backward building blocks ----------------------------------------
 
@@ -38,32 +60,7 @@ int layer_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, 
     if (i == l.L - 1 && passes[j].seed_w != nullptr) { p.seed_w = passes[j].seed_w; p.C2 = passes[j].seed_out; }
     if (i == l.L - 1 && passes[j].dot_w != nullptr) { p.dot_w = passes[j].dot_w; p.dot_out = passes[j].dot_out; }
   }
-  // K >= 512 and K % 256 == 0: full-line loads + wave-private LDS transpose; else (first
-  // layer, narrow towers) the plain direct kernel.  One problem: 32x32 tiles (256 workgroups
-  // for a 256x1024 layer); grouped: 64x32.
-  const bool lds_ok = (l.kp[i] >= 512) && (l.kp[i] % 256 == 0);
-  const LaunchOn on = timed(h, !lds_ok ? kFamFwdDirect : (n == 1 ? kFamFwdLds2x2 : kFamFwdLds4x2), st);
-  // acting-time batches (<= 128 rows, e.g. 64 env workers): 16x16 tiles so that one layer still spreads
-  // over 256 workgroups (64 rows x 1024 outputs = 256 tiles) instead of 64
-  if (n == 1 && rows <= 128 && lds_ok) HIPCHK((fwd_lds_launch<1, 1, true>(b, on)));
-  else if (n == 1 && rows >= 512 && lds_ok && l.dims[i + 1] % 64 == 0) HIPCHK((fwd_lds_launch<4, 2, true>(b, on)));   // enough rows to fill the chip with 64x32 tiles (fewer bytes per FLOP)
-  else if (n == 1) { if (lds_ok) HIPCHK((fwd_lds_launch<2, 2, true>(b, on))); else HIPCHK((fwd_direct_launch<2, 2>(b, on))); }
-  else {
-    // grouped launches: 64x32 tiles when they still give the chip something to do; small minibatches / narrow layers
-    // (the reference's defaults: 32 rows into 512 outputs = 16 such tiles for two problems, one long chain each) take
-    // 32x32 or 16x16 tiles — same K split over the four waves, same reduction order, more workgroups
-    const long P = l.dims[i + 1];
-    const long t42 = (long)n * (P / 64) * (rows / 32), t22 = (long)n * (P / 32) * (rows / 32);
-    if (lds_ok) {
-      if (t42 >= 192) HIPCHK((fwd_lds_launch<4, 2, true, 1>(b, on)));   // one LDS image per wave (48 KiB): both tiles of a CU resident at once — same-box A/B +0.6 %
-      else if (t22 >= 128 || rows > 128 || rows % 16) HIPCHK((fwd_lds_launch<2, 2, true>(b, on)));
-      else HIPCHK((fwd_lds_launch<1, 1, true>(b, on)));
-    } else {
-      if (t42 >= 64) HIPCHK((fwd_direct_launch<4, 2>(b, on)));
-      else HIPCHK((fwd_direct_launch<2, 2>(b, on)));
-    }
-  }
-  return 0;
+  return form_launch(h, st, fwd_form(l.kp[i], l.dims[i + 1], rows, n), b);
 }
 int tower_forward(H* h, hipStream_t st, const FwdPass* passes, int n, int rows, int first_layer) {
   for (int i = first_layer; i < passes[0].l->L; ++i) RC(layer_forward(h, st, passes, n, rows, i));
@@ -112,8 +109,6 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
     p.partial = partial ? partial + l.part_off[i] : nullptr;
     return p;
   };
-  // reduction width (the layer's outputs) wide enough: dY through the LDS transpose, scheduled form
-  auto lds_ok_of = [&](int i) { return l.dims[i + 1] >= 512 && l.dims[i + 1] % 256 == 0; };
   auto layer_slice = [&](int i) { return (i + 1 < l.L ? l.w_off[i + 1] : l.hw_off) - l.w_off[i]; };
   // SHIFTED schedule (weights wanted, no input gradient, every layer above the first on the one-workgroup-type form):
   //   dgrad(L-1) | wgrad(L-1) + dgrad(L-2) | ... | wgrad(2) + dgrad(1) | wgrad(1) + wgrad(0) + the head's riders
@@ -121,25 +116,25 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
   // count, same workgroups, same arithmetic: the chain's last launch — 64-128 short workgroups, 6 us of launch floor —
   // is absorbed into a full wgrad launch (+~1 us), at the price of splitting one pair (8.3 + 7.9 instead of 14.5 us).
   const bool shifted = want_w && !input_grad && bwd_is_shifted(h, l, rows);
-  if (r.qtrain != nullptr && !(shifted && lds_ok_of(l.L - 1))) return fail("internal: k_dgrad_qtrain needs the shifted schedule and an LDS-staged top layer");
+  if (r.qtrain != nullptr && !(shifted && dgrad_form(l.dims[l.L]) == GEMM_FORM_DGRAD_LDS)) return fail("internal: k_dgrad_qtrain needs the shifted schedule and an LDS-staged top layer");
   if (shifted) {
     {
       GemmBatch bd{}; bd.n = 1; bd.prob[0] = dgrad_of(l.L - 1);
-      const LaunchOn on = timed(h, kFamDgrad, st);
-      if (r.qtrain != nullptr) { bd.prob[0].Q = r.qtrain_seed; HIPCHK(dgrad_qtrain_launch(bd, *r.qtrain, on)); }
-      else if (lds_ok_of(l.L - 1)) HIPCHK((dgrad_lds_launch<1, 1>(bd, on))); else HIPCHK((dgrad_direct_launch<1, 1>(bd, on)));
+      const GemmForm f = dgrad_form(l.dims[l.L]);
+      if (r.qtrain != nullptr) {             // (f is GEMM_FORM_DGRAD_LDS: checked above)
+        bd.prob[0].Q = r.qtrain_seed;
+        RC(form_check(f, bd));
+        HIPCHK(dgrad_qtrain_launch(bd, *r.qtrain, timed(h, family_of(f, 1), st)));
+      } else RC(form_launch(h, st, f, bd));
     }
     for (int i = l.L - 2; i >= 1; --i) {
       GemmBatch b{}; b.n = 2; b.prob[0] = dgrad_of(i); b.prob[1] = wgrad_of(i + 1);
-      const LaunchOn on = timed(h, kFamBwdPair, st);
-      if (lds_ok_of(i)) HIPCHK((bwd_seq_launch<true>(b, on))); else HIPCHK((bwd_seq_launch<false>(b, on)));
+      RC(form_launch(h, st, bwd_shifted_mid_form(l.dims[i + 1]), b));
       if (h->comm && h->dp_per_layer) RC(dp_reduce_slice(h, st, net, l.w_off[i + 1], layer_slice(i + 1)));
     }
     {
       GemmBatch b{}; b.n = 2; b.prob[0] = wgrad_of(1); b.prob[1] = wgrad_of(0);
-      const HeadWgradRider none{};
-      const LaunchOn on = timed(h, kFamWgrad, st);
-      if (l.NH == 1) HIPCHK((wgrad_tail_launch<1>(b, r.rider ? *r.rider : none, on, r.tails))); else HIPCHK((wgrad_tail_launch<kNO>(b, r.rider ? *r.rider : none, on, r.tails)));
+      RC(form_launch(h, st, bwd_shifted_tail_form(l.NH), b, r.rider, r.tails));
       if (h->comm && h->dp_per_layer) RC(dp_reduce_slice(h, st, net, l.w_off[0], layer_slice(0) + layer_slice(1)));
     }
     if (qrider) return fail("internal: the q-head rider found no carrier launch");
@@ -151,16 +146,9 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
     const bool need_dx = (i > 0 || input_grad);
     if (need_dx) bd.prob[bd.n++] = dgrad_of(i);
     if (want_w) bw.prob[bw.n++] = wgrad_of(i);
-    const bool lds_ok = lds_ok_of(i);
-    if (need_dx && want_w) {               // ONE workgroup type: its wgrad tile, then its dgrad tile (gemm_bwd_seq)
+    if (need_dx && want_w) {
       GemmBatch b{}; b.n = 2; b.prob[0] = bd.prob[0]; b.prob[1] = bw.prob[0];
-      const LaunchOn on = timed(h, kFamBwdPair, st);
-      // small minibatches / narrow layers: when the dgrad's 64x16 tiles and the wgrad's 64x64 tiles together still fit
-      // the chip in one round, they run side by side on their own workgroups (one tile's chain per launch, not two)
-      if (bwd_layer_is_pair(l, i, rows)) {
-        if (lds_ok) HIPCHK((bwd_pair_direct_launch<1, true>(b, on))); else HIPCHK((bwd_pair_direct_launch<1, false>(b, on)));
-      } else if (lds_ok) HIPCHK((bwd_seq_launch<true>(b, on)));
-      else HIPCHK((bwd_seq_launch<false>(b, on)));
+      RC(form_launch(h, st, bwd_form(l.kp[i], l.dims[i + 1], rows), b));
     } else if (need_dx && i == 0 && r.fuse != nullptr) {
       GemmProblem p = bd.prob[0];
       p.P += r.in_lo; p.C = nullptr; p.Pdim = 16; p.mask = nullptr;
@@ -173,20 +161,19 @@ int tower_backward(H* h, hipStream_t st, const NetLayout& l, int net, float* gar
       const int c0 = (r.in_lo / 16) * 16, c1 = std::min(l.kp[0], (r.in_hi + 15) / 16 * 16);
       p.P += c0; p.C += c0; p.Pdim = c1 - c0;
       if (p.mask) p.mask += c0;
-      const LaunchOn on = timed(h, kFamDgrad, st);
-      if (qrider) { HIPCHK(dgrad_narrow_qrider_launch(bd, *qrider, on)); qrider = nullptr; }
-      else HIPCHK(dgrad_narrow_launch(bd, on));
-    } else if (need_dx) {
-      const LaunchOn on = timed(h, kFamDgrad, st);
-      if (lds_ok) HIPCHK((dgrad_lds_launch<1, 1>(bd, on)));
-      else HIPCHK((dgrad_direct_launch<1, 1>(bd, on)));
-    } else {
-      // wgrad alone = the first layer (K_in = 64 / 128 columns): 16-output tiles, 4x the workgroups
-      const LaunchOn on = timed(h, kFamWgrad, st);
-      if (r.rider) {                                    // + the head's dW / db as rider blocks (head_wgrad_can_ride)
-        if (l.NH == 1) HIPCHK((wgrad_narrow_rider_launch<1>(bw, *r.rider, on))); else HIPCHK((wgrad_narrow_rider_launch<kNO>(bw, *r.rider, on)));
-      } else HIPCHK((wgrad_narrow_launch<1>(bw, on)));
-    }
+      const GemmForm f = dgrad_form(l.dims[1], true);
+      if (qrider) {
+        RC(form_check(f, bd));
+        HIPCHK(dgrad_narrow_qrider_launch(bd, *qrider, timed(h, family_of(f, 1), st)));
+        qrider = nullptr;
+      } else RC(form_launch(h, st, f, bd));
+    } else if (need_dx) RC(form_launch(h, st, dgrad_form(l.dims[i + 1]), bd));
+    else if (r.rider) {                                  // + the head's dW / db as rider blocks (head_wgrad_can_ride)
+      const GemmForm f = wgrad_form();
+      RC(form_check(f, bw));
+      const LaunchOn on = timed(h, family_of(f, 1), st);
+      if (l.NH == 1) HIPCHK((wgrad_narrow_rider_launch<1>(bw, *r.rider, on))); else HIPCHK((wgrad_narrow_rider_launch<kNO>(bw, *r.rider, on)));
+    } else RC(form_launch(h, st, wgrad_form(), bw));
     // data parallel, bucketed: layer i's dW/db are final once this launch has run -> start their
     // all-reduce on the communication stream while the chain continues with layer i-1
     if (want_w && h->comm && h->dp_per_layer) RC(dp_reduce_slice(h, st, net, l.w_off[i], layer_slice(i)));
@@ -691,8 +678,7 @@ int first_layers_launch(H* h, hipStream_t st, int rows, bool with_actor) {
   fill(b.prob[2], DQNHIP_CRITIC_TARGET, lc, h->act[2][0], h->Zs, round_up(h->S, 64), false);
   b.prob[2].xcopy_dst = h->Wact_t; b.prob[2].xcopy_col = h->S; b.prob[2].xcopy_n = kNO;
   if (with_actor) fill(b.prob[3], DQNHIP_ACTOR, la, h->act[1][0], h->act[1][1], la.kp[0], true);
-  HIPCHK((fwd_direct_launch<4, 2>(b, timed(h, kFamFwdDirect, st))));
-  return 0;
+  return form_launch(h, st, first_layers_form(), b);
 }
 int run_phase(H* h, int phase, const int* idx_dev) {
   const UpdatePlan P = plan_of(h);

@@ -1,7 +1,8 @@
 // learner_args.hip.h — the ARGUMENT layer: the plain structs and constants that host code and kernels share.  No __global__,
 // no launcher, nothing that instantiates a kernel: a host-only translation unit includes this (through learner_internal.hip.h)
 // and embeds no device code.  Layers, includes pointing downwards only:
-//   arguments   gemm_common.hip.h (GEMM problems, LaunchOn / launch, tails, flags), this header, hgemm_plan.hip.h
+//   arguments   gemm_common.hip.h (GEMM problems, LaunchOn / launch, tails, flags), this header, gemm_plan.hip.h (the fp32 family's
+//               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
 //   bodies      gemm_bodies.hip.h, update_bodies.hip.h: __device__ functions only
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
 //               io_kernels.hip.h, env.hip.h: __global__ functions and their launchers, grouped by the unit that launches them

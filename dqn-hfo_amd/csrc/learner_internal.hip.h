@@ -40,6 +40,7 @@
 #include "../../include/dqnhip_env.h"
 #include "gemm_common.hip.h"      // LaunchOn, launch, TailsArgs, the flags
 #include "learner_args.hip.h"
+#include "gemm_plan.hip.h"        // the fp32 forms and their choosers (bwd_layer_is_pair)
 #include "hgemm_plan.hip.h"
 
 namespace dqnhip_host {

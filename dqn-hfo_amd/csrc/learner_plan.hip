@@ -117,10 +117,7 @@ int validate(const dqnhip_config* c) {
 
 // ---- shape predicates of the launch schedules (learner.hip branches on them, plan_of reports them) -----------------------------
 // does layer i's backward (dgrad + wgrad) take the side-by-side pair launch (small minibatches / narrow layers)?
-bool bwd_layer_is_pair(const NetLayout& l, int i, int rows) {
-  const long tiles = (long)(l.kp[i] / 64) * (rows / 16) + (long)(l.kp[i] / 64) * (l.dims[i + 1] / 64);
-  return tiles <= 256 && rows % 16 == 0 && l.kp[i] % 64 == 0 && l.dims[i + 1] % 64 == 0;
-}
+bool bwd_layer_is_pair(const NetLayout& l, int i, int rows) { return dqnhip::bwd_layer_is_pair(l.kp[i], l.dims[i + 1], rows); }     // (gemm_plan.hip.h)
 // may the head's weight / bias gradients ride in the first tower layer's wgrad launch (gemm_wgrad_narrow_rider: the last
 // launch of a net's backward, input_grad == false)?
 bool head_wgrad_can_ride(const NetLayout& l, int rows) {

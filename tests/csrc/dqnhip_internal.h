@@ -44,7 +44,8 @@ typedef struct dqnhip_test_problem {
   dqnhip_test_buf P, Q, bias, mask, seed_w, dot_w;      /* inputs */
   dqnhip_test_buf C, db, partial, C2, dot_out, xcopy_dst; /* in/out: arrive prefilled with the caller's sentinel */
 } dqnhip_test_problem;
-/* form: one id per launcher template instance learner.hip reaches for the fp32 tower (riders aside) */
+/* form: one id per launcher template instance learner.hip reaches for the fp32 tower (riders aside): the values of GemmForm
+ * (dqn-hfo_amd/csrc/gemm_plan.hip.h, which holds the table and the preconditions; gemm_forms.hip static_asserts the two enums agree) */
 enum dqnhip_test_form {
   DQNHIP_FORM_FWD_DIRECT_2x2 = 0, DQNHIP_FORM_FWD_DIRECT_4x2 = 1,
   DQNHIP_FORM_FWD_LDS_1x1 = 2, DQNHIP_FORM_FWD_LDS_2x2 = 3, DQNHIP_FORM_FWD_LDS_4x2 = 4, DQNHIP_FORM_FWD_LDS_4x2_ONE_IMAGE = 5,
