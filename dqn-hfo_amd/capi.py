@@ -158,6 +158,24 @@ SIGNATURES.update({
     "dqnhip_env_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, fp, C.c_size_t]),
 })
 
+ENV_NO_RECORD = 1        # DQNHIP_ENV_NO_RECORD
+
+
+class EnvEpisode(C.Structure):
+    """struct dqnhip_env_episode (include/dqnhip_env.h)."""
+    _fields_ = [("total_reward", C.c_double), ("extrinsic_reward", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
+                ("worker", C.c_int32), ("reserved", C.c_int32), ("step_index", C.c_int64)]
+
+
+SIGNATURES.update({
+    "dqnhip_env_create_external": (C.c_int, [H, C.POINTER(EnvConfig), C.c_int32, fp, C.POINTER(C.c_void_p)]),
+    "dqnhip_env_act": (C.c_int, [C.c_void_p, C.c_float, ip, fp, fp]),
+    "dqnhip_env_act_device": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dqnhip_env_observe": (C.c_int, [C.c_void_p, fp, ip, ip]),
+    "dqnhip_env_observe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dqnhip_env_read_episodes": (C.c_int, [C.c_void_p, C.POINTER(EnvEpisode), C.c_int32, ip, C.POINTER(C.c_int64)]),
+})
+
 _lib = None
 
 

@@ -1,6 +1,7 @@
 // env.hip.h — device side of the batched env front-end (include/dqnhip_env.h): per-worker
 // epsilon-greedy selection + GetAction, synthetic HFO state stream, HFOGameState reward
-// shaping, per-episode buffers, LabelTransitions + AddTransitions at episode end.
+// shaping, per-episode buffers, LabelTransitions + AddTransitions at episode end; and the same step on caller-supplied states, cut in
+// two where the caller's simulator sits (k_env_act / k_env_observe).
 // Reference lines: src/dqn_main.cpp:97-153, src/dqn.cpp:162-208, 664-711, 768-797,
 // src/hfo_game.cpp:109-236.
 #pragma once
@@ -265,6 +266,185 @@ __global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a) {
         e.game[w] = gs; e.len[w] = len + 1; e.g[w] = g + 1;
       }
       e.done[w] = status != 0 ? len + 1 : 0;           // length of the finished episode (0: still open)
+      e.n_steps[w] += 1; e.reward_sum[w] += (double)r; e.n_goals[w] += goal;
+    }
+  }
+}
+
+// ---- the external kind of handle (dqnhip_env_create_external): the step cut in two where the caller's simulator sits -------------
+// k_env_act is k_env_step up to GetAction, k_env_observe the rest with the caller's arrays in the place of env_feature and of the
+// status / player-on-ball draws.  The bodies below restate k_env_step's (whose text and code stay what they were) and share its
+// game_update / game_reward / game_reset.
+
+// one finished episode: the layout of dqnhip_env_episode (include/dqnhip_env.h)
+struct EnvEpisode { double total_reward, extrinsic_reward; int steps, status, worker, reserved; long long step_index; };
+constexpr int kEnvRecRing = 8;           // episode records kept per worker between two dqnhip_env_read_episodes
+
+// what only k_env_ext_init / k_env_act / k_env_observe take, beside EnvDev (and Env16)
+struct EnvExt {
+  float epsilon;                         // act: this call's epsilon (eager launches: a kernel argument)
+  int record;                            // 0: DQNHIP_ENV_NO_RECORD — no episode rows exist, nothing is handed to k_env_flush
+  int* out_action; float* out_args; float* out_ao;       // act -> caller: [N], [N][2], [N][10] or null
+  const float* next; const int* status; const int* pob;  // observe <- caller: [N][S] dense, [N], [N]
+  EnvEpisode* rec; unsigned long long* rec_n;            // [N][kEnvRecRing] records, [N] records written so far
+  double* tot; double* ext;              // [N] HFOGameState::total_reward / extrinsic_reward of the open episode
+  unsigned long long* truncated;         // [N] episodes closed as OUT_OF_TIME by max_steps
+  int* flag;                             // sticky: bit 0 SERVER_DOWN seen, bit 1 a status outside 0..5
+  long long step_index;                  // observe: the handle's observe count including this one
+};
+
+// first states from the caller: the row, HFOGameState() and the initial update (player on ball 0), as env_reset_worker; the draw
+// counter starts at 1, where env_reset_worker leaves it after drawing the first synthetic state at 0
+template <bool F16>
+__global__ void k_env_ext_init(const EnvArgs<F16> a, const EnvExt x) {
+  extern __shared__ float s_state[];
+  const EnvDev& e = a.e;
+  const int w = blockIdx.x, lane = threadIdx.x;
+  for (int f = lane; f < e.SP; f += 64) {
+    const float v = f < e.S ? x.next[(size_t)w * e.S + f] : 0.0f;
+    s_state[f] = v; e.cur[(size_t)w * e.SP + f] = v;
+    if constexpr (F16) { if (f < a.x.ldx16) a.x.x16[(size_t)w * a.x.ldx16 + f] = (_Float16)v; }
+  }
+  __syncthreads();
+  if (lane == 0) {
+    GameState gs; game_reset(gs);
+    game_update(gs, s_state, 0, 0, game_angle(s_state[51], s_state[52]), game_angle(s_state[13], s_state[14]));
+    e.game[w] = gs; e.len[w] = 0; e.g[w] = 1;
+  }
+}
+
+// SelectAction + GetAction of every worker (src/dqn.cpp:684-711, 196-208): block = one worker, 4 waves, as k_env_step
+template <bool F16>
+__global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const EnvExt x) {
+  const EnvDev& e = a.e;
+  bool fused_heads = e.head_x != nullptr;
+  if constexpr (F16) fused_heads = a.x.head_x16 != nullptr;
+  __shared__ float s_ao[16];
+  __shared__ float s_part[4][16];
+  const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int len = e.len[w];
+  const unsigned long long g = e.g[w];
+  const float head_bias = (fused_heads && tid < kNO) ? e.head_b[tid] : 0.0f;
+  const bool rnd = env_u01(e.seed, g, w, 0) < x.epsilon;          // ONE epsilon draw per call (src/dqn.cpp:700)
+  if (fused_heads) {
+    // the 10 head outputs of this worker's tower-top row; thread t owns the float4 k-strip t (+ 256 strips per round)
+    const size_t x0 = (size_t)w * e.head_h;
+    const _Float16* x16 = nullptr;
+    if constexpr (F16) x16 = a.x.head_x16;
+    float acc[kNO];
+#pragma unroll
+    for (int j = 0; j < kNO; ++j) acc[j] = 0.0f;
+    for (int k = tid * 4; k < e.head_h; k += 1024) {
+      const f32x4 xv = head_ld4t<F16>(e.head_x, x16, x0 + k);
+#pragma unroll
+      for (int j = 0; j < kNO; ++j) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(e.head_w + (size_t)j * e.head_h + k);
+        acc[j] = fmaf(xv.x, wv.x, acc[j]); acc[j] = fmaf(xv.y, wv.y, acc[j]); acc[j] = fmaf(xv.z, wv.z, acc[j]); acc[j] = fmaf(xv.w, wv.w, acc[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kNO; ++j) { acc[j] = wave_sum64(acc[j]); if (lane == 0) s_part[wave][j] = acc[j]; }
+  }
+  if (x.record) {                                                  // the state the action is chosen in: the open episode's next row
+    float* eps_row = e.ep_s + ((size_t)w * e.T + len) * e.SP;
+    const float* cur = e.cur + (size_t)w * e.SP;
+    for (int f = tid; f < e.SP; f += 256) eps_row[f] = cur[f];
+  }
+  __syncthreads();
+  if (tid < kAP) {
+    float v = 0.0f;
+    if (tid < kNO) {
+      if (fused_heads) v = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) + head_bias;
+      else v = e.out16[(size_t)w * kAP + tid];       // written by the separate head launch
+    }
+    if (fused_heads) e.out16[(size_t)w * kAP + tid] = v;
+    if (tid < kNO && rnd) {                          // GetRandomActorOutput (src/dqn.cpp:664-682)
+      const float u = env_u01(e.seed, g, w, 1 + tid);
+      if (tid < kNA) v = fmaf(2.0f, u, -1.0f);
+      else if (tid == kNA + 0) v = fmaf(200.0f, u, -100.0f);
+      else if (tid == kNA + 4) v = 100.0f * u;
+      else v = fmaf(360.0f, u, -180.0f);
+    }
+    s_ao[tid] = v;
+    if (x.record) e.ep_a[((size_t)w * e.T + len) * kAP + tid] = v;
+    if (x.out_ao != nullptr && tid < kNO) x.out_ao[(size_t)w * kNO + tid] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    // GetAction (src/dqn.cpp:196-208)
+    const float c0 = s_ao[0], c1 = s_ao[1], c3 = s_ao[3];
+    const float c2 = -99999.0f;
+    int best = 0; float bv = c0;
+    if (c1 > bv) { best = 1; bv = c1; }
+    if (c2 > bv) { best = 2; bv = c2; }
+    if (c3 > bv) { best = 3; bv = c3; }
+    const int o1 = best == 0 ? 0 : best == 1 ? 2 : best == 2 ? 3 : 4;
+    const int o2 = best == 0 ? 1 : best == 3 ? 5 : -1;
+    const float a1 = s_ao[kNA + o1], a2 = o2 < 0 ? 0.0f : s_ao[kNA + o2];
+    e.act[w] = best; e.arg1[w] = a1; e.arg2[w] = a2;
+    x.out_action[w] = best; x.out_args[2 * (size_t)w] = a1; x.out_args[2 * (size_t)w + 1] = a2;
+  }
+}
+
+// what the simulator answered: HFOGameState::update + reward on the caller's row / status / player on ball, the episode's reward
+// row and totals, and at an episode's end its record and the next episode's HFOGameState.  next[w] is the row the worker shows the
+// actor next: the successor state, or — the status is terminal — the first state of the worker's next episode (a terminal
+// transition has no next state, src/dqn_main.cpp:138-140, and :164-168 zeroes the deltas the row would feed).
+template <bool F16>
+__global__ __launch_bounds__(256) void k_env_observe(const EnvArgs<F16> a, const EnvExt x) {
+  const EnvDev& e = a.e;
+  extern __shared__ float s_next[];                  // [SP]
+  const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int len = e.len[w];
+  const unsigned long long g = e.g[w];
+  GameState gs;
+  if (tid == 0) gs = e.game[w];
+  const int status_in = x.status[w];
+  const int pob = x.pob[w];
+  int status = status_in;
+  const bool truncated = status == 0 && len + 1 >= e.T;          // max_steps reached while IN_GAME: closed as OUT_OF_TIME
+  if (truncated) status = 4;
+  const float* row = x.next + (size_t)w * e.S;       // dense: leading dimension S
+  float* cur = e.cur + (size_t)w * e.SP;
+  for (int f = tid; f < e.SP; f += 256) {
+    const float v = f < e.S ? row[f] : 0.0f;         // the pad columns of the actor's input panel stay zero
+    s_next[f] = v; cur[f] = v;
+    if constexpr (F16) { if (f < a.x.ldx16) a.x.x16[(size_t)w * a.x.ldx16 + f] = (_Float16)v; }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    // lanes 0 / 1: the ball and goal angles of the row — of this step's update, and (the row being the next episode's first state
+    // when this one ends) of the new episode's initial update as well
+    float ang = 0.0f;
+    if (lane < 2) ang = game_angle(s_next[lane == 0 ? 51 : 13], s_next[lane == 0 ? 52 : 14]);
+    const float goal_ang = __shfl(ang, 1, 64);
+    if (lane == 0) {
+      if (status_in < 0 || status_in > 4) atomicOr(x.flag, status_in == 5 ? 1 : 2);   // src/hfo_game.cpp:124-126
+      game_update(gs, s_next, status, pob, ang, goal_ang);
+      int goal = 0;
+      const float r = game_reward(gs, e.unum, &goal);
+      const float eot = goal ? (gs.pob == e.unum ? 5.0f : 1.0f) : 0.0f;
+      if (x.record) e.ep_r[(size_t)w * e.T + len] = r;
+      e.rew[w] = r;
+      const double tot = x.tot[w] + (double)r, ext = x.ext[w] + (double)eot;
+      if (status != 0) {
+        const unsigned long long n = x.rec_n[w];
+        EnvEpisode ep;
+        ep.total_reward = tot; ep.extrinsic_reward = ext; ep.steps = gs.steps; ep.status = status; ep.worker = w; ep.reserved = 0;
+        ep.step_index = x.step_index;
+        x.rec[(size_t)w * kEnvRecRing + (n % kEnvRecRing)] = ep; x.rec_n[w] = n + 1;
+        x.tot[w] = 0.0; x.ext[w] = 0.0;
+        if (truncated) x.truncated[w] += 1;
+        if (!x.record) e.n_episodes[w] += 1;         // (a recording handle's k_env_flush counts the episodes it appends)
+        // new episode: HFOGameState() and the initial update after the forced DASH(0,0) (src/dqn_main.cpp:103-105)
+        GameState g0; game_reset(g0);
+        game_update(g0, s_next, 0, 0, ang, goal_ang);
+        e.game[w] = g0; e.len[w] = 0; e.g[w] = g + 2;
+      } else {
+        x.tot[w] = tot; x.ext[w] = ext;
+        e.game[w] = gs; e.len[w] = len + 1; e.g[w] = g + 1;
+      }
+      if (x.record) e.done[w] = status != 0 ? len + 1 : 0;
       e.n_steps[w] += 1; e.reward_sum[w] += (double)r; e.n_goals[w] += goal;
     }
   }

@@ -29,8 +29,23 @@ struct dqnhip_env {
   bool f16 = false;
   int Npad16 = 0;
   h16* p16[kMaxL + 1] = {nullptr};
+  // the external kind (dqnhip_env_create_external): the caller's simulator sits between dqnhip_env_act and dqnhip_env_observe
+  bool external = false, record = true;
+  bool acted = false;                   // an act is waiting for its observe
+  EnvExt x{};
+  long long observes = 0;
+  // the host variants' staging: device copies of what act hands out / observe takes in, and their pinned host mirrors
+  int* d_action = nullptr; float* d_args = nullptr; float* d_ao = nullptr;
+  float* d_next = nullptr; int* d_status = nullptr; int* d_pob = nullptr;
+  void* pinned = nullptr;               // [action N | status N | pob N | args 2N | actor_out 10N | next N*S]
+  // episode records: what each worker's ring has handed out so far, and the merged records not yet read
+  std::vector<unsigned long long> rec_read;
+  std::deque<dqnhip_env_episode> pending;
+  long long dropped = 0;
 };
 constexpr int kEnvUnroll = 16;
+static_assert(sizeof(EnvEpisode) == sizeof(dqnhip_env_episode) && offsetof(EnvEpisode, step_index) == offsetof(dqnhip_env_episode, step_index) &&
+              offsetof(EnvEpisode, steps) == offsetof(dqnhip_env_episode, steps), "k_env_observe writes dqnhip_env_episode records");
 
 namespace {
 template <typename T>
@@ -44,7 +59,15 @@ int env_alloc(dqnhip_env* e, T** p, size_t n) {
 
 extern "C" {
 
-static int env_create_impl(dqnhip_env* e);
+static int env_create_impl(dqnhip_env* e, const float* first_states_host);
+
+// the pinned staging block's parts (dqnhip_env::pinned)
+static int32_t* pin_action(dqnhip_env* e) { return (int32_t*)e->pinned; }
+static int32_t* pin_status(dqnhip_env* e) { return (int32_t*)e->pinned + e->d.N; }
+static int32_t* pin_pob(dqnhip_env* e) { return (int32_t*)e->pinned + 2 * (size_t)e->d.N; }
+static float* pin_args(dqnhip_env* e) { return (float*)e->pinned + 3 * (size_t)e->d.N; }
+static float* pin_ao(dqnhip_env* e) { return (float*)e->pinned + 5 * (size_t)e->d.N; }
+static float* pin_next(dqnhip_env* e) { return (float*)e->pinned + (5 + kNO) * (size_t)e->d.N; }
 
 // the env's fp16 panels (allocated once, zero-filled) and the fp16 kernels' extra argument
 static int env_panels16(dqnhip_env* e) {
@@ -60,25 +83,37 @@ static Env16 env16_of(const dqnhip_env* e, bool fused) {
   return x;
 }
 
-int dqnhip_env_create(dqnhip_handle h, const dqnhip_env_config* cfg, dqnhip_env_handle* out) {
+static int env_create_any(dqnhip_handle h, const dqnhip_env_config* cfg, bool external, int32_t flags, const float* first_states_host,
+                          dqnhip_env_handle* out) {
   if (!h || !cfg || !out) return fail("null argument");
   *out = nullptr;
+  const bool record = !(flags & DQNHIP_ENV_NO_RECORD);
   if (cfg->struct_size != (int32_t)sizeof(dqnhip_env_config)) return fail("dqnhip_env_config.struct_size mismatch");
   if (cfg->workers < 1 || cfg->workers > (1 << 20)) return fail("workers out of range");
   if (cfg->max_steps < 1 || cfg->max_steps > 4096) return fail("max_steps out of range");
   if (h->S < 56) return fail("HFOGameState reads state indices up to 55: state_size must be >= 56 (src/hfo_game.cpp:130-152)");
-  if ((long long)cfg->workers * cfg->max_steps >= RO(h)->ring.cap)
+  if (record && (long long)cfg->workers * cfg->max_steps >= RO(h)->ring.cap)
     return fail("replay capacity %d must exceed workers*max_steps = %lld", RO(h)->ring.cap, (long long)cfg->workers * cfg->max_steps);
   HIPCHK(hipSetDevice(h->cfg.device));
   dqnhip_env* e = new dqnhip_env();
-  e->h = h; e->cfg = *cfg;
-  const int rc = env_create_impl(e);
+  e->h = h; e->cfg = *cfg; e->external = external; e->record = record;
+  const int rc = env_create_impl(e, first_states_host);
   if (rc) { const std::string msg = g_err; dqnhip_env_destroy(e); g_err = msg; return rc; }
   *out = e;
   return 0;
 }
 
-static int env_create_impl(dqnhip_env* e) {
+int dqnhip_env_create(dqnhip_handle h, const dqnhip_env_config* cfg, dqnhip_env_handle* out) {
+  return env_create_any(h, cfg, false, 0, nullptr, out);
+}
+int dqnhip_env_create_external(dqnhip_handle h, const dqnhip_env_config* cfg, int32_t flags, const float* first_states_host,
+                               dqnhip_env_handle* out) {
+  if (flags & ~DQNHIP_ENV_NO_RECORD) return fail("unknown flags %d", (int)flags);
+  if (!first_states_host) return fail("null argument");
+  return env_create_any(h, cfg, true, flags, first_states_host, out);
+}
+
+static int env_create_impl(dqnhip_env* e, const float* first_states_host) {
   dqnhip_learner* h = e->h;
   const dqnhip_env_config* cfg = &e->cfg;
   EnvDev& d = e->d;
@@ -87,7 +122,7 @@ static int env_create_impl(dqnhip_env* e) {
   e->Npad = round_up(d.N, 32);
   const size_t N = d.N, Np = e->Npad;
   RC(env_alloc(e, &d.cur, Np * d.SP)); RC(env_alloc(e, &d.out16, Np * kAP));
-  RC(env_alloc(e, &d.ep_s, N * d.T * d.SP)); RC(env_alloc(e, &d.ep_a, N * d.T * kAP)); RC(env_alloc(e, &d.ep_r, N * d.T));
+  if (e->record) { RC(env_alloc(e, &d.ep_s, N * d.T * d.SP)); RC(env_alloc(e, &d.ep_a, N * d.T * kAP)); RC(env_alloc(e, &d.ep_r, N * d.T)); }
   RC(env_alloc(e, &d.game, N)); RC(env_alloc(e, &d.len, N)); RC(env_alloc(e, &d.done, N)); RC(env_alloc(e, &d.g, N));
   RC(env_alloc(e, &d.act, N)); RC(env_alloc(e, &d.arg1, N)); RC(env_alloc(e, &d.arg2, N)); RC(env_alloc(e, &d.rew, N));
   RC(env_alloc(e, &d.n_steps, N)); RC(env_alloc(e, &d.n_episodes, N)); RC(env_alloc(e, &d.n_goals, N)); RC(env_alloc(e, &d.reward_sum, N));
@@ -96,6 +131,25 @@ static int env_create_impl(dqnhip_env* e) {
   RC(env_alloc(e, &e->eps_dev, 16)); d.eps = e->eps_dev;
   RC(env_alloc(e, &e->commit_ticket, 32));
   e->act_epoch = h->act_epoch; e->f16 = h->act_fp16;
+  if (e->external) {
+    EnvExt& x = e->x;
+    x.record = e->record ? 1 : 0;
+    RC(env_alloc(e, &x.rec, N * kEnvRecRing)); RC(env_alloc(e, &x.rec_n, N)); RC(env_alloc(e, &x.tot, N)); RC(env_alloc(e, &x.ext, N));
+    RC(env_alloc(e, &x.truncated, N)); RC(env_alloc(e, &x.flag, 1));
+    RC(env_alloc(e, &e->d_action, N)); RC(env_alloc(e, &e->d_args, 2 * N)); RC(env_alloc(e, &e->d_ao, kNO * N));
+    RC(env_alloc(e, &e->d_next, N * d.S)); RC(env_alloc(e, &e->d_status, N)); RC(env_alloc(e, &e->d_pob, N));
+    HIPCHK(hipHostMalloc(&e->pinned, N * 4 * (3 + 2 + kNO + (size_t)d.S), hipHostMallocDefault));
+    e->rec_read.assign(N, 0);
+    memcpy(pin_next(e), first_states_host, N * d.S * sizeof(float));
+    HIPCHK(hipMemcpyAsync(e->d_next, pin_next(e), N * d.S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    x.next = e->d_next;
+    if (e->f16) {
+      RC(env_panels16(e));
+      HIPCHK(launch(h->stream, k_env_ext_init<true>, dim3(d.N), dim3(64), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}, x));
+    } else HIPCHK(launch(h->stream, k_env_ext_init<false>, dim3(d.N), dim3(64), d.SP * sizeof(float), EnvArgs<false>{d}, x));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  }
   if (e->f16) {
     RC(env_panels16(e));
     HIPCHK(launch(h->stream, k_env_init<true>, dim3(d.N), dim3(64), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}));
@@ -109,6 +163,7 @@ int dqnhip_env_destroy(dqnhip_env_handle e) {
   hipSetDevice(e->h->cfg.device);
   hipStreamSynchronize(e->h->stream);
   for (void* p : e->allocs) hipFree(p);
+  if (e->pinned) hipHostFree(e->pinned);
   for (int i = 0; i < 2; ++i) if (e->graph[i]) hipGraphExecDestroy(e->graph[i]);
   delete e;
   return 0;
@@ -251,6 +306,7 @@ static int env_capture(dqnhip_env* e, int which) {
 
 int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
   if (!e) return fail("null env");
+  if (e->external) return fail("dqnhip_env_step: this handle takes its states from the caller: use dqnhip_env_act / dqnhip_env_observe");
   if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail("Check failed: epsilon >= 0.0 && epsilon <= 1.0");   // src/dqn.cpp:698
   if (n_steps < 1) return fail("n_steps must be >= 1");
   dqnhip_learner* h = e->h;
@@ -284,10 +340,153 @@ int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
   return 0;
 }
 
+// ---- the external kind: dqnhip_env_act / dqnhip_env_observe ----------------------------------------------------------------------
+// A pair is L + 3 launches at L = 4 up to 512 workers (L tower layers, k_env_act with the heads inside, k_env_observe, k_env_flush
+// with the commit in its last block), L + 5 above (head_forward and k_env_commit on their own); a NO_RECORD handle has no flush.
+// Eager launches: the caller's pointers are kernel arguments.
+
+int dqnhip_env_act_device(dqnhip_env_handle e, float epsilon, int32_t* action_dev, float* args_dev, float* actor_out_dev) {
+  if (!e) return fail("null env");
+  if (!e->external) return fail("dqnhip_env_act: this handle generates its own states: use dqnhip_env_step");
+  if (!action_dev || !args_dev) return fail("null argument");
+  if (e->acted) return fail("dqnhip_env_act: the previous act has not been answered by dqnhip_env_observe");
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail("Check failed: epsilon >= 0.0 && epsilon <= 1.0");   // src/dqn.cpp:698
+  dqnhip_learner* h = e->h;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = h->stream;
+  RC(env_follow_act_precision(e));
+  EnvDev d = e->d;
+  const NetLayout& la = h->la;
+  // the forward pass and the heads' place are those of env_one_step / env_one_step16: the same launches at the same padded rows
+  const bool fused = la.dims[la.L] % 4 == 0 && d.N <= 512;
+  if (fused) {
+    d.head_h = la.dims[la.L];
+    d.head_w = wat(h, DQNHIP_ACTOR, la.hw_off); d.head_b = wat(h, DQNHIP_ACTOR, la.hb_off);
+    if (!e->f16) d.head_x = e->acts[la.L];
+  }
+  HeadArgs ha{}; ha.ldx = la.dims[la.L]; ha.H = la.dims[la.L]; ha.rows = e->Npad;
+  ha.W = wat(h, DQNHIP_ACTOR, la.hw_off); ha.b = wat(h, DQNHIP_ACTOR, la.hb_off); ha.out16 = d.out16;
+  if (e->f16) {
+    RC(sync_dirty16(h));
+    RC(tower_forward16_on(h, st, DQNHIP_ACTOR, e->p16, e->Npad16));
+    ha.X16 = e->p16[la.L];
+  } else {
+    FwdPass fp{DQNHIP_ACTOR, &la, e->acts};
+    for (int i = 0; i < la.L; ++i) RC(layer_forward(h, st, &fp, 1, e->Npad, i));
+    ha.X = e->acts[la.L];
+  }
+  if (!fused) RC((head_forward<kNO, HEAD_ACTOR>(h, st, ha)));
+  EnvExt x = e->x;
+  x.epsilon = epsilon; x.out_action = action_dev; x.out_args = args_dev; x.out_ao = actor_out_dev;
+  if (e->f16) HIPCHK(launch(st, k_env_act<true>, dim3(d.N), dim3(256), 0, EnvArgs<true>{d, env16_of(e, fused)}, x));
+  else HIPCHK(launch(st, k_env_act<false>, dim3(d.N), dim3(256), 0, EnvArgs<false>{d}, x));
+  e->acted = true;
+  return 0;
+}
+
+int dqnhip_env_act(dqnhip_env_handle e, float epsilon, int32_t* action, float* args, float* actor_out) {
+  if (!e || !action || !args) return fail("null argument");
+  RC(dqnhip_env_act_device(e, epsilon, e->d_action, e->d_args, actor_out ? e->d_ao : nullptr));
+  hipStream_t st = e->h->stream;
+  const size_t N = e->d.N;
+  HIPCHK(hipMemcpyAsync(pin_action(e), e->d_action, N * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(pin_args(e), e->d_args, 2 * N * 4, hipMemcpyDeviceToHost, st));
+  if (actor_out) HIPCHK(hipMemcpyAsync(pin_ao(e), e->d_ao, kNO * N * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  memcpy(action, pin_action(e), N * 4); memcpy(args, pin_args(e), 2 * N * 4);
+  if (actor_out) memcpy(actor_out, pin_ao(e), kNO * N * 4);
+  return 0;
+}
+
+int dqnhip_env_observe_device(dqnhip_env_handle e, const float* next_states_dev, const int32_t* status_dev, const int32_t* player_on_ball_dev) {
+  if (!e || !next_states_dev || !status_dev || !player_on_ball_dev) return fail("null argument");
+  if (!e->external) return fail("dqnhip_env_observe: this handle generates its own states: use dqnhip_env_step");
+  if (!e->acted) return fail("dqnhip_env_observe: no dqnhip_env_act is waiting for its observation");
+  dqnhip_learner* h = e->h;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = h->stream;
+  EnvDev d = e->d;
+  EnvExt x = e->x;
+  x.next = next_states_dev; x.status = status_dev; x.pob = player_on_ball_dev; x.step_index = e->observes + 1;
+  auto observe = [&]() -> int {
+    if (e->f16) HIPCHK(launch(st, k_env_observe<true>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}, x));
+    else HIPCHK(launch(st, k_env_observe<false>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<false>{d}, x));
+    e->observes += 1; e->acted = false;
+    return 0;
+  };
+  if (!e->record) return observe();   // PlayOneEpisode(update = false): the replay memory, and with it an update chain, is left alone
+  RO(h)->epoch += 1;            // episodes may end inside: the ring changes on the device
+  RingUse ring_use(h);
+  if (d.N <= 512) d.commit_ticket = e->commit_ticket;
+  RC(observe());
+  HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring, (const DevState*)RO(h)->st, h->cfg.gamma));
+  if (d.commit_ticket == nullptr) HIPCHK(launch(st, k_env_commit, dim3(1), dim3(256), 0, d, RO(h)->ring, RO(h)->st));
+  RO(h)->ring_stale = true;
+  return 0;
+}
+
+int dqnhip_env_observe(dqnhip_env_handle e, const float* next_states, const int32_t* status, const int32_t* player_on_ball) {
+  if (!e || !next_states || !status || !player_on_ball) return fail("null argument");
+  if (!e->external) return fail("dqnhip_env_observe: this handle generates its own states: use dqnhip_env_step");
+  if (!e->acted) return fail("dqnhip_env_observe: no dqnhip_env_act is waiting for its observation");
+  hipStream_t st = e->h->stream;
+  const size_t N = e->d.N, S = e->d.S;
+  HIPCHK(hipSetDevice(e->h->cfg.device));
+  HIPCHK(hipStreamSynchronize(st));           // the previous observe's copies out of the pinned block have run
+  memcpy(pin_next(e), next_states, N * S * 4); memcpy(pin_status(e), status, N * 4); memcpy(pin_pob(e), player_on_ball, N * 4);
+  HIPCHK(hipMemcpyAsync(e->d_next, pin_next(e), N * S * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->d_status, pin_status(e), N * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(e->d_pob, pin_pob(e), N * 4, hipMemcpyHostToDevice, st));
+  return dqnhip_env_observe_device(e, e->d_next, e->d_status, e->d_pob);
+}
+
+// the sticky status flag of an external handle (src/hfo_game.cpp:124-126 throws "Server Down!"); the stream is idle
+static int env_check_flag(dqnhip_env* e) {
+  if (!e->external) return 0;
+  int flag = 0;
+  HIPCHK(hipMemcpy(&flag, e->x.flag, sizeof flag, hipMemcpyDeviceToHost));
+  if (flag & 1) return fail("Server Down!");
+  if (flag & 2) return fail("dqnhip_env_observe: status out of range (the HFO status values are 0..4)");
+  return 0;
+}
+
+int dqnhip_env_read_episodes(dqnhip_env_handle e, dqnhip_env_episode* out, int32_t cap, int32_t* n_out, int64_t* dropped) {
+  if (!e || !n_out || (cap > 0 && !out)) return fail("null argument");
+  *n_out = 0;
+  if (!e->external) return fail("dqnhip_env_read_episodes: only a handle of dqnhip_env_create_external keeps episode records");
+  if (cap < 0) return fail("cap must be >= 0");
+  dqnhip_learner* h = e->h;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  RC(env_check_flag(e));
+  const size_t N = e->d.N;
+  std::vector<unsigned long long> n(N);
+  std::vector<dqnhip_env_episode> rec(N * kEnvRecRing);
+  HIPCHK(hipMemcpy(n.data(), e->x.rec_n, N * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec.data(), e->x.rec, rec.size() * sizeof(dqnhip_env_episode), hipMemcpyDeviceToHost));
+  std::vector<dqnhip_env_episode> fresh;
+  for (size_t w = 0; w < N; ++w) {
+    unsigned long long from = e->rec_read[w];
+    if (n[w] - from > (unsigned long long)kEnvRecRing) { e->dropped += (long long)(n[w] - from) - kEnvRecRing; from = n[w] - kEnvRecRing; }
+    for (unsigned long long i = from; i < n[w]; ++i) fresh.push_back(rec[w * kEnvRecRing + i % kEnvRecRing]);
+    e->rec_read[w] = n[w];
+  }
+  // every fresh record ended later than every pending one, so sorting the fresh ones keeps the whole queue in (step_index, worker) order
+  std::sort(fresh.begin(), fresh.end(), [](const dqnhip_env_episode& a, const dqnhip_env_episode& b) {
+    return a.step_index != b.step_index ? a.step_index < b.step_index : a.worker < b.worker; });
+  e->pending.insert(e->pending.end(), fresh.begin(), fresh.end());
+  int32_t k = 0;
+  for (; k < cap && !e->pending.empty(); ++k) { out[k] = e->pending.front(); e->pending.pop_front(); }
+  *n_out = k;
+  if (dropped) *dropped = e->dropped;
+  return 0;
+}
+
 int dqnhip_env_stats(dqnhip_env_handle e, int64_t* env_steps, int64_t* episodes, double* reward_sum, int64_t* goals) {
   if (!e) return fail("null env");
   dqnhip_learner* h = e->h;
   HIPCHK(hipSetDevice(h->cfg.device));
+  if (e->external) { HIPCHK(hipStreamSynchronize(h->stream)); RC(env_check_flag(e)); }
   const size_t N = e->d.N;
   std::vector<unsigned long long> a(N), b(N), c(N); std::vector<double> r(N);
   HIPCHK(hipMemcpyAsync(a.data(), e->d.n_steps, N * 8, hipMemcpyDeviceToHost, h->stream));
@@ -313,6 +512,18 @@ int dqnhip_env_debug_read(dqnhip_env_handle e, const char* name, float* host, si
     std::vector<int> t(N);
     HIPCHK(hipMemcpy(t.data(), !strcmp(name, "action") ? e->d.act : e->d.len, N * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < N; ++i) host[i] = (float)t[i];
+    return 0;
+  }
+  if (!strcmp(name, "truncated")) {
+    // episodes that reached max_steps while IN_GAME and were closed as OUT_OF_TIME (external handles; a synthetic one reports 0)
+    if (count < 1) return fail("buffer too small");
+    unsigned long long total = 0;
+    if (e->external) {
+      std::vector<unsigned long long> t(N);
+      HIPCHK(hipMemcpy(t.data(), e->x.truncated, N * 8, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < N; ++i) total += t[i];
+    }
+    host[0] = (float)total;
     return 0;
   }
   const float* src = nullptr; size_t n = N;

@@ -750,6 +750,10 @@ class EnvFrontEnd:
 
     def debug_read(self, name):
         N, S = self.N, self.dqn.state_size_
+        if name == "truncated":
+            out = np.empty(1, np.float32)
+            self.dqn._ck(self.lib.dqnhip_env_debug_read(self.h, name.encode(), _p(out), 1))
+            return int(out[0])
         n = N * (S if name == "state" else 10 if name == "actor_out" else 1)
         out = np.empty(n, np.float32)
         self.dqn._ck(self.lib.dqnhip_env_debug_read(self.h, name.encode(), _p(out), n))
@@ -763,3 +767,87 @@ class EnvFrontEnd:
         if self.h:
             self.lib.dqnhip_env_destroy(self.h)
             self.h = None
+
+
+EnvEpisode = namedtuple("EnvEpisode", "total_reward extrinsic_reward steps status worker step_index")
+
+
+class ExternalEnv(EnvFrontEnd):
+    """N concurrent HFO workers whose states the caller supplies (a rack of HFO servers, any batched simulator that emits HFO
+    low-level features): `act` is the batched step up to GetAction, `observe` takes what the simulator answered and does the rest
+    of PlayOneEpisode's learner side on the device.  record=False plays PlayOneEpisode(update = false), the mode of Evaluate()
+    (src/dqn_main.cpp:171-204): nothing reaches the replay memory.  See include/dqnhip_env.h."""
+
+    def __init__(self, dqn, workers, first_states, max_steps=500, unum=7, seed=1, record=True):
+        self.dqn, self.N = dqn, workers
+        self.lib = dqn.lib
+        cfg = capi.EnvConfig()
+        cfg.struct_size = C.sizeof(capi.EnvConfig)
+        cfg.workers, cfg.max_steps, cfg.unum, cfg.seed = workers, max_steps, unum, seed
+        first = _f32(first_states)
+        if first.shape != (workers, dqn.state_size_):
+            raise ValueError("first_states must be [workers, state_size]")
+        self.h = C.c_void_p()
+        dqn._ck(self.lib.dqnhip_env_create_external(dqn.h, C.byref(cfg), 0 if record else capi.ENV_NO_RECORD, _p(first), C.byref(self.h)))
+
+    def step(self, epsilon, n_steps=1):
+        self.dqn._ck(self.lib.dqnhip_env_step(self.h, float(epsilon), int(n_steps)))      # refused: names act / observe
+
+    def act(self, epsilon, actor_out=False):
+        """-> (action [N] int32, args [N,2]) and, with actor_out=True, the chosen ActorOutputs [N,10]."""
+        action, args = np.empty(self.N, np.int32), np.empty((self.N, 2), np.float32)
+        ao = np.empty((self.N, 10), np.float32) if actor_out else None
+        self.dqn._ck(self.lib.dqnhip_env_act(self.h, float(epsilon), action.ctypes.data_as(capi.ip), _p(args), _p(ao) if actor_out else None))
+        return (action, args, ao) if actor_out else (action, args)
+
+    def observe(self, next_states, status, player_on_ball):
+        nx = _f32(next_states)
+        st, pob = np.ascontiguousarray(status, np.int32), np.ascontiguousarray(player_on_ball, np.int32)
+        if nx.shape != (self.N, self.dqn.state_size_) or st.shape != (self.N,) or pob.shape != (self.N,):
+            raise ValueError("observe takes next_states [workers, state_size], status [workers], player_on_ball [workers]")
+        self.dqn._ck(self.lib.dqnhip_env_observe(self.h, _p(nx), st.ctypes.data_as(capi.ip), pob.ctypes.data_as(capi.ip)))
+
+    def act_device(self, epsilon, action_ptr, args_ptr, actor_out_ptr=None):
+        """Device pointers (ints): int32 [N], float [N,2], float [N,10] or None.  Asynchronous on the learner's stream."""
+        self.dqn._ck(self.lib.dqnhip_env_act_device(self.h, float(epsilon), action_ptr, args_ptr, actor_out_ptr))
+
+    def observe_device(self, next_states_ptr, status_ptr, player_on_ball_ptr):
+        """Device pointers (ints): float [N,S] dense, int32 [N], int32 [N].  Asynchronous on the learner's stream."""
+        self.dqn._ck(self.lib.dqnhip_env_observe_device(self.h, next_states_ptr, status_ptr, player_on_ball_ptr))
+
+    def episodes(self, cap=None):
+        """The finished episodes not handed out yet (at most `cap`), in (step_index, worker) order; also sets self.dropped."""
+        out = []
+        while cap is None or len(out) < cap:
+            want = 256 if cap is None else min(256, cap - len(out))
+            buf = (capi.EnvEpisode * want)()
+            n, dropped = C.c_int32(), C.c_int64()
+            self.dqn._ck(self.lib.dqnhip_env_read_episodes(self.h, buf, want, C.byref(n), C.byref(dropped)))
+            self.dropped = dropped.value
+            out += [EnvEpisode(r.total_reward, r.extrinsic_reward, r.steps, r.status, r.worker, r.step_index) for r in buf[:n.value]]
+            if n.value < want:
+                break
+        return out
+
+
+def get_avg_std(values):
+    """src/dqn_main.cpp:155-166: the mean and the standard deviation with the n - 1 divisor (nan where the reference divides 0 by 0)."""
+    v = np.asarray(list(values), np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        avg = np.float64(v.sum()) / np.float64(v.size)
+        std = np.sqrt(np.float64(((v - avg) ** 2).sum()) / np.float64(v.size - 1.0))
+    return float(avg), float(std)
+
+
+def evaluation_summary(episodes):
+    """The fields of Evaluate()'s log line (src/dqn_main.cpp:171-204) from finished episodes (ExternalEnv.episodes(), or anything
+    with total_reward / steps / status): a trial is successful when its status is GOAL (1); goal_perc is the function's result."""
+    eps = list(episodes)
+    if not eps:
+        raise ValueError("evaluation_summary needs at least one episode")
+    avg_reward, reward_std = get_avg_std(e.total_reward for e in eps)
+    avg_steps, steps_std = get_avg_std(e.steps for e in eps)
+    success_steps, success_std = get_avg_std(e.steps for e in eps if e.status == 1)
+    goals = sum(1 for e in eps if e.status == 1)
+    return dict(episodes=len(eps), avg_reward=avg_reward, reward_std=reward_std, avg_steps=avg_steps, steps_std=steps_std,
+                success_steps=success_steps, success_std=success_std, goals=goals, goal_perc=float(np.float32(goals) / np.float32(len(eps))))
