@@ -18,7 +18,7 @@ TUNE_SEPARATE_CRITIC_FIRST_LAYERS = 64
 TUNE_LATE_GATHER = 128
 # dqnhip_update_plan.forms bits (DQNHIP_PLAN_*), in bit order
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
-              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride")
+              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized")
 LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
 FP32, FP16 = 0, 1                                   # DQNHIP_FP32 / DQNHIP_FP16: dqnhip_config.precision, dqnhip_set_act_precision
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
@@ -54,6 +54,19 @@ class UpdatePlan(C.Structure):
     """struct dqnhip_update_plan (include/dqnhip.h)."""
     _fields_ = [("struct_size", C.c_int32), ("forms", C.c_int32), ("launches_single", C.c_int32), ("launches_graph_first", C.c_int32),
                 ("launches_in_graph", C.c_int32), ("updates_per_graph", C.c_int32), ("collectives", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PerConfig(C.Structure):
+    """struct dqnhip_per_config (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("alpha", C.c_float), ("beta0", C.c_float), ("beta_anneal_iters", C.c_int32),
+                ("eps", C.c_float), ("seed", C.c_uint64)]
+
+
+class PerState(C.Structure):
+    """struct dqnhip_per_state (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("enabled", C.c_int32), ("levels", C.c_int32), ("size", C.c_int32),
+                ("total", C.c_float), ("p_max", C.c_float), ("beta_now", C.c_float), ("reserved", C.c_float),
+                ("next_counter", C.c_uint64), ("syncs", C.c_int64)]
 
 
 fp = C.POINTER(C.c_float)
@@ -141,6 +154,13 @@ SIGNATURES = {
     "dqnhip_get_stream": (C.c_int, [H, C.POINTER(C.c_void_p)]),
     "dqnhip_set_kernel_timing": (C.c_int, [H, C.c_int32]),
     "dqnhip_get_kernel_timing": (C.c_int, [H, C.c_char_p, fp, C.POINTER(C.c_int64), C.c_int32]),
+    "dqnhip_per_default_config": (None, [C.POINTER(PerConfig)]),
+    "dqnhip_per_enable": (C.c_int, [H, C.POINTER(PerConfig)]),
+    "dqnhip_per_get_state": (C.c_int, [H, C.POINTER(PerState)]),
+    "dqnhip_per_get_priorities": (C.c_int, [H, C.c_int32, C.c_int32, fp]),
+    "dqnhip_per_set_priorities": (C.c_int, [H, C.c_int32, C.c_int32, fp]),
+    "dqnhip_per_sample": (C.c_int, [H, C.c_uint64, C.c_int32, ip, fp]),
+    "dqnhip_per_debug_read": (C.c_int, [H, C.c_char_p, fp, C.c_size_t]),
 }
 
 class EnvConfig(C.Structure):

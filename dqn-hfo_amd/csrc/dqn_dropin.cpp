@@ -47,6 +47,13 @@ DEFINE_bool(dynamic_loss_scale, false, "-precision fp16 only: the learner halves
                                        "finite (the step is skipped, nothing is reported) and doubles it after -loss_scale_growth_interval finite "
                                        "steps, on the device (dqnhip_config.loss_scale_mode). Off: the static scales; an overflow is fatal.");
 DEFINE_int32(loss_scale_growth_interval, 2000, "-dynamic_loss_scale: finite steps in a row before a multiplier doubles (0: never grow).");
+DEFINE_bool(prioritized_replay, false, "Proportional prioritized experience replay (Schaul et al. 2016) on the device: minibatches are drawn with "
+            "probability p^alpha / sum from a sum tree over the replay memory, the critic's loss carries importance weights, |TD error| is "
+            "written back. UpdateActorCritic() then draws nothing from the host engine. Not combinable with -deferred_updates, "
+            "-pipelined_stats or -dp_rendezvous.");
+DEFINE_double(per_alpha, 0.6, "-prioritized_replay: the priority exponent (0: uniform). The paper's customary value, not measured on this workload.");
+DEFINE_double(per_beta, 0.4, "-prioritized_replay: the importance exponent at critic iteration 0. The paper's customary value, not measured on this workload.");
+DEFINE_int32(per_beta_anneal_iters, 0, "-prioritized_replay: critic iterations over which the importance exponent rises linearly to 1 (0: constant).");
 DEFINE_bool(device_sampling, false, "Sample minibatch indices on the device (counter-based) instead of the host std::mt19937.");
 DEFINE_bool(chained_updates, true, "UpdateActorCritic() tells the library which indices the NEXT call will draw (a copy of the engine runs ahead; "
             "dqnhip_update_chained): bursts of Update() get the launch schedule of a multi-update graph.  Same results, same RNG order.");
@@ -228,6 +235,11 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
                << "(libdqnhip.so has no CPU backend). Run the reference's own Caffe build for the CPU solver, or start this binary with -gpu=true.";
   CHECK(!(FLAGS_deferred_updates && FLAGS_pipelined_stats)) << "-deferred_updates cannot be combined with -pipelined_stats (both decide when an update's (loss, avg_q) reach the host)";
   CHECK(!(FLAGS_deferred_updates && FLAGS_device_sampling)) << "-deferred_updates cannot be combined with -device_sampling (deferred updates run on the indices random_engine draws)";
+  if (FLAGS_prioritized_replay) {
+    CHECK(!FLAGS_deferred_updates) << "-prioritized_replay cannot be combined with -deferred_updates (a deferred burst runs on indices drawn ahead; a prioritized update's indices do not exist before its predecessor's write-back)";
+    CHECK(!FLAGS_pipelined_stats) << "-prioritized_replay cannot be combined with -pipelined_stats";
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-prioritized_replay is a single-learner option (-dp_world 1, no -dp_rendezvous)";
+  }
   std::vector<int> wa = TowerWidths(actor_solver_param_.net_param()), wc = TowerWidths(critic_solver_param_.net_param());
   if (wa.empty()) wa = kDefaultTower;
   if (wc.empty()) wc = kDefaultTower;
@@ -285,6 +297,13 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   }
   DQNHIP_CK(dqnhip_create(&c, &h_));
   if (FLAGS_act_precision == "fp16") DQNHIP_CK(dqnhip_set_act_precision(h_, DQNHIP_FP16));
+  if (FLAGS_prioritized_replay) {
+    dqnhip_per_config pc;
+    dqnhip_per_default_config(&pc);
+    pc.alpha = (float)FLAGS_per_alpha; pc.beta0 = (float)FLAGS_per_beta; pc.beta_anneal_iters = FLAGS_per_beta_anneal_iters;
+    pc.seed = (uint64_t)seed;
+    DQNHIP_CK(dqnhip_per_enable(h_, &pc));
+  }
   if (dp_) {
     // one communicator per agent thread's learner: agents are independent DQNs (src/dqn_main.cpp:264), each its own group
     const std::string rv = FLAGS_dp_rendezvous + "_agent" + std::to_string(tid);
@@ -578,7 +597,8 @@ std::vector<InputStates> DQN::SampleStatesFromMemory(int n) {
 std::pair<float, float> DQN::UpdateActorCritic() {
   CollectDeferred();
   SyncReplicasIfPending();
-  if (FLAGS_device_sampling) {
+  // -prioritized_replay: the indices come from the device's sum tree — random_engine is not drawn from for sampling
+  if (FLAGS_device_sampling || FLAGS_prioritized_replay) {
     float loss = 0, avgq = 0;
     if (dp_) { DQNHIP_CK(dqnhip_dp_update(h_, nullptr)); DQNHIP_CK(dqnhip_read_stats(h_, &loss, &avgq)); }
     else DQNHIP_CK(dqnhip_update(h_, nullptr, &loss, &avgq));                 // CHECK(isfinite(target / loss)): the call fails

@@ -68,6 +68,80 @@ static __global__ __launch_bounds__(256) void k_head_q_train(HeadTrainArgs a) {
   if (threadIdx.x == 0) a.loss_partial[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
 }
 
+// Prioritized replay: k_head_q_train restated with per-row importance weights (a copy, so that k_head_q_train keeps its instruction
+// stream).  Every wave forms pmin = min_j prob[j] over the minibatch (the customary normalisation by the batch's largest weight
+// (N pmin)^-beta; N cancels) and beta from the live critic iteration, so graph replays anneal without host traffic; the row's weight
+// is w = (pmin / prob[row])^beta, 1.0f exactly when beta == 0.  dq_row = (inv_batch d) w, the loss partial (d d) w: with w = 1.0f both
+// are k_head_q_train's bits.  Everything downstream reads dq from its buffer (the head's dW / db riders) or gets it here (dZ / dZ16).
+// Also stores w[row] and td_abs[row] = |d| for the write-back (k_per_update).
+__device__ __forceinline__ float per_beta_now(float beta0, int anneal, int critic_iter) {
+  if (anneal <= 0) return beta0;
+  return fminf(1.0f, beta0 + (1.0f - beta0) * ((float)critic_iter / (float)anneal));
+}
+static __global__ __launch_bounds__(256) void k_head_q_train_w(HeadTrainWArgs aw) {
+  const HeadTrainArgs& a = aw.t;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  __shared__ float s_part[4];
+  float at = 0.0f, ao = 0.0f;
+  float bt0 = 0.0f, b0 = 0.0f, r = 0.0f, mcv = 0.0f, tm = 0.0f, pr = 1.0f;
+  if (row < a.rows && lane == 0) { bt0 = a.bt[0]; b0 = a.b[0]; r = a.reward[row]; mcv = a.mc[row]; tm = a.term[row]; pr = aw.prob[row]; }
+  float pmin = INFINITY;
+  for (int j = lane; j < a.rows; j += 64) pmin = fminf(pmin, aw.prob[j]);
+  if (row < a.rows) {
+    const size_t x0 = (size_t)row * a.H;
+    auto dots = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 v0 = head_ld4t<decltype(tag)::value>(a.Xt, a.Xt16, x0 + k), w0 = *reinterpret_cast<const f32x4*>(a.Wt + k);
+        const f32x4 v1 = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), w1 = *reinterpret_cast<const f32x4*>(a.W + k);
+        at = fmaf(v0.x, w0.x, at); at = fmaf(v0.y, w0.y, at); at = fmaf(v0.z, w0.z, at); at = fmaf(v0.w, w0.w, at);
+        ao = fmaf(v1.x, w1.x, ao); ao = fmaf(v1.y, w1.y, ao); ao = fmaf(v1.z, w1.z, ao); ao = fmaf(v1.w, w1.w, ao);
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, dots);
+  }
+  at = wave_sum64(at); ao = wave_sum64(ao);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) pmin = fminf(pmin, __shfl_xor(pmin, off, 64));
+  float d2 = 0.0f, dq_row = 0.0f;
+  if (row < a.rows && lane == 0) {
+    const float qt = at + bt0, q = ao + b0;
+    a.q_target[row] = qt; a.q[row] = q;
+    const float off_policy = tm != 0.0f ? r : (float)((double)r + a.gamma * (double)qt);
+    const float target = (float)(a.beta * (double)mcv + (1 - a.beta) * (double)off_policy);
+    a.y[row] = target;
+    if (!isfinite(target)) atomicOr(&a.st->flags, kFlagTarget);   // CHECK(std::isfinite(target)), src/dqn.cpp:898
+    const float beta = per_beta_now(aw.beta0, aw.beta_anneal_iters, a.st->critic_iter);
+    const float w = beta == 0.0f ? 1.0f : powf(__fdiv_rn(pmin, pr), beta);
+    const float d = q - target;
+    dq_row = (a.inv_batch * d) * w;
+    a.dq[row] = dq_row;
+    d2 = (d * d) * w;
+    aw.w[row] = w; aw.td_abs[row] = fabsf(d);
+  }
+  if ((a.dZ != nullptr || a.dZ16 != nullptr) && row < a.rows) {     // (wave-uniform condition)
+    const float dqv = __shfl(dq_row, 0, 64);
+    const size_t x0 = (size_t)row * a.H;
+    const float sc16 = a.dZ16 != nullptr ? ls_live(a.scale16, a.ls_mult) : 0.0f;
+    auto seed = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 xv = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), wv = *reinterpret_cast<const f32x4*>(a.W + k);
+        f32x4 dz;
+        dz.x = (dqv * wv.x) * lrelu_mask(xv.x); dz.y = (dqv * wv.y) * lrelu_mask(xv.y);
+        dz.z = (dqv * wv.z) * lrelu_mask(xv.z); dz.w = (dqv * wv.w) * lrelu_mask(xv.w);
+        if constexpr (decltype(tag)::value)
+          *reinterpret_cast<head_h4*>(a.dZ16 + x0 + k) = head_h4{(_Float16)(dz.x * sc16), (_Float16)(dz.y * sc16), (_Float16)(dz.z * sc16), (_Float16)(dz.w * sc16)};
+        else
+          *reinterpret_cast<f32x4*>(a.dZ + x0 + k) = dz;
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, seed);
+  }
+  if (lane == 0) s_part[wave] = d2;
+  __syncthreads();
+  if (threadIdx.x == 0) a.loss_partial[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
 // ---- Step(1)'s head arithmetic inside the critic's first backward launch (round 5) -------------------------------------------
 // k_head_q_train sits between the critics' last forward launch and the critic's top-layer dgrad: a 4.9-us launch-floor link
 // whose output the dgrad needs only as a PER-ROW SCALAR.  dZ_L[r][n] = (dq_r w_n) lrelu'(x_rn) = (-dq_r) U[r][n] with

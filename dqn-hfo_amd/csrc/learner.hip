@@ -20,7 +20,8 @@ using namespace dqnhip_host;
 namespace dqnhip_host {
 
 const char* const kFamily[kNumFamily] = {"gemm_fwd_lds_4x2", "gemm_dgrad", "gemm_wgrad", "adam", "gemm_bwd_pair", "gemm_fwd_lds_2x2", "gemm_fwd_direct",
-                                         "hgemm_fwd", "hgemm_dgrad", "hgemm_wgrad"};      // by Family
+                                         "hgemm_fwd", "hgemm_dgrad", "hgemm_wgrad",
+                                         "per_sync", "per_sample", "per_update"};      // by Family
 // The timing family of a launch of an fp32 GEMM form (gemm_plan.hip.h) with n problems.  The forward LDS families go by the number
 // of problems, not by the tile: a single problem — the 16x16 tile included — files under gemm_fwd_lds_2x2, a grouped launch of any
 // tile under gemm_fwd_lds_4x2.
@@ -505,6 +506,11 @@ static HeadTrainArgs q_train_args(const H* h) {
   t.gamma = h->cfg.gamma; t.beta = h->cfg.beta; t.inv_batch = inv_batch_of(h); t.st = h->st;
   return t;
 }
+// prioritized replay: k_head_q_train's arguments + the sampling probabilities in, the weights and |TD errors| out
+static HeadTrainWArgs q_train_w_args(const H* h, const HeadTrainArgs& t) {
+  const PerHost* p = h->per;
+  return HeadTrainWArgs{t, p->prob, p->w, p->td_abs, p->cfg.beta0, p->cfg.beta_anneal_iters};
+}
 // data parallel: the [loss, q, flag] tails for the exchange — one more block of a net's last backward launch (UpdatePlan::tails_ride)
 // or a launch of its own (tails_launch)
 static TailsArgs critic_tails(const H* h) {
@@ -565,7 +571,8 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       // with the head's dW / db riding in the net's last backward launch, the scaled fp16 tower-top gradient comes out of
       // this launch too (HeadTrainArgs::dZ16) — Step(1) has no head-backward launch (as on the fp32 path)
       if (P.fuse_q) { t.dZ16 = h->dZ16[1][L]; t.scale16 = h->ls_c; t.ls_mult = lsm_c; }
-      HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
+      if (P.prioritized) HIPCHK(launch(st, k_head_q_train_w, dim3((B + 3) / 4), dim3(256), 0, q_train_w_args(h, t)));
+      else HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
     }
     const TailsArgs tails_c = critic_tails(h);
     {
@@ -737,7 +744,8 @@ int run_phase(H* h, int phase, const int* idx_dev) {
     // with the head's dW / db riding in the net's last backward launch, the head's dZ comes out of this launch too
     if (P.head_rides_c) qt_args.dZ = h->dZc[L];
     qt_args.pdt = h->qdot[0]; qt_args.pd = h->qdot[1];
-    if (!fuse_q) HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, qt_args));
+    if (P.prioritized) HIPCHK(launch(st, k_head_q_train_w, dim3((B + 3) / 4), dim3(256), 0, q_train_w_args(h, qt_args)));      // (plan_of: never with fuse_q)
+    else if (!fuse_q) HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, qt_args));
     // critic backward (rest of Step(1)): head (dgrad + ReLU' + wgrad fused), then tower; wgrad
     // writes (beta=0) so ClearParamDiffs/ZeroGradParameters (src/dqn.cpp:63-78, 908-909) vanish
     {

@@ -5,7 +5,8 @@
 //               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
 //   bodies      gemm_bodies.hip.h, update_bodies.hip.h: __device__ functions only
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
-//               io_kernels.hip.h, env.hip.h: __global__ functions and their launchers, grouped by the unit that launches them
+//               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), env.hip.h: __global__ functions and their
+//               launchers, grouped by the unit that launches them
 // One include points upwards: head_fwd_kernels.hip.h holds the launcher head_forward<>, which takes the learner and reports through
 // HIPCHK, and so includes learner_internal.hip.h.
 #pragma once
@@ -183,6 +184,14 @@ struct HeadTrainArgs {
   // k_dgrad_qtrain: the two head dot products in 16-column pieces, [rows][H / 16], left by the top forward layers (GemmProblem::dot_w)
   const float* pdt; const float* pd;
   const float* ls_mult;                                 // dynamic loss scaling: scale16 is multiplied by *ls_mult (DevState::ls_mult[1]; null: static)
+};
+
+// k_head_q_train_w (prioritized replay): k_head_q_train's arguments + the importance weights' inputs and outputs
+struct HeadTrainWArgs {
+  HeadTrainArgs t;
+  const float* prob;                   // [rows]: the sampling probability of each row's transition (k_per_sample / k_per_fill)
+  float* w; float* td_abs;             // [rows] out: the row's weight, |q - target|
+  float beta0; int beta_anneal_iters;  // beta = min(1, beta0 + (1 - beta0) critic_iter / beta_anneal_iters); 0 iterations: constant
 };
 
 // k_head_bwd

@@ -26,6 +26,7 @@ struct dqnhip_env {
   // steps — and fp16 panels of the env's own: p16[0] the actor's input panel k_env_step<true> writes, p16[i] layer i's output;
   // [Npad16][k16[0][i]], whole 64-row hgemm tiles, zero-filled (the pad rows stay zero), allocated when the mode is first seen
   unsigned long long act_epoch = 0;
+  bool slack_counted = false;           // this handle's workers x max_steps is in the ring owner's per_env_slack
   bool f16 = false;
   int Npad16 = 0;
   h16* p16[kMaxL + 1] = {nullptr};
@@ -99,6 +100,7 @@ static int env_create_any(dqnhip_handle h, const dqnhip_env_config* cfg, bool ex
   e->h = h; e->cfg = *cfg; e->external = external; e->record = record;
   const int rc = env_create_impl(e, first_states_host);
   if (rc) { const std::string msg = g_err; dqnhip_env_destroy(e); g_err = msg; return rc; }
+  if (record) { RO(h)->per_env_slack += (long long)cfg->workers * cfg->max_steps; e->slack_counted = true; }   // (prioritized replay: what this handle may hold back)
   *out = e;
   return 0;
 }
@@ -160,6 +162,7 @@ static int env_create_impl(dqnhip_env* e, const float* first_states_host) {
 
 int dqnhip_env_destroy(dqnhip_env_handle e) {
   if (!e) return 0;
+  if (e->slack_counted) RO(e->h)->per_env_slack -= (long long)e->cfg.workers * e->cfg.max_steps;
   hipSetDevice(e->h->cfg.device);
   hipStreamSynchronize(e->h->stream);
   for (void* p : e->allocs) hipFree(p);
@@ -326,6 +329,7 @@ int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
       const int n = which ? kEnvUnroll : 1;
       while (n_steps - s >= n) {
         if (!e->graph[which] && env_capture(e, which)) { e->graph_failed = true; break; }
+        per_note_append(h, (long long)e->d.N * n);      // (prioritized replay: at most one transition per worker and step reaches the ring)
         HIPCHK(hipGraphLaunch(e->graph[which], st));
         s += n;
       }
@@ -333,6 +337,7 @@ int dqnhip_env_step(dqnhip_env_handle e, float epsilon, int32_t n_steps) {
     }
   }
   for (; s < n_steps; ++s) {
+    per_note_append(h, e->d.N);
     const int rc = env_one_step(e, s + 1 < n_steps);
     if (rc) { e->flush_deferred = false; return rc; }
   }
@@ -417,6 +422,7 @@ int dqnhip_env_observe_device(dqnhip_env_handle e, const float* next_states_dev,
   if (!e->record) return observe();   // PlayOneEpisode(update = false): the replay memory, and with it an update chain, is left alone
   RO(h)->epoch += 1;            // episodes may end inside: the ring changes on the device
   RingUse ring_use(h);
+  per_note_append(h, d.N);
   if (d.N <= 512) d.commit_ticket = e->commit_ticket;
   RC(observe());
   HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring, (const DevState*)RO(h)->st, h->cfg.gamma));

@@ -8,7 +8,8 @@
 //   learner_update.hip  index staging, graph capture (capture_updates), dqnhip_update* / dqnhip_get_update_plan / dqnhip_read_stats,
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
-//   learner_io.hip      acting, replay memory (+ .replaymemory files), parameters, multi-agent sharing, introspection
+//   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
+//                       introspection
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   snapshot.cpp        Caffe snapshot layout (no device code)
 // This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
@@ -96,7 +97,8 @@ struct NetLayout {
 void layout_init(NetLayout& l, int in_dim, const dqnhip_config& c, bool actor);
 
 // the kernel families of timing mode (dqnhip_get_kernel_timing), named by kFamily[] (learner.hip)
-enum Family { kFamFwdLds4x2, kFamDgrad, kFamWgrad, kFamAdam, kFamBwdPair, kFamFwdLds2x2, kFamFwdDirect, kFamHgemmFwd, kFamHgemmDgrad, kFamHgemmWgrad, kNumFamily };
+enum Family { kFamFwdLds4x2, kFamDgrad, kFamWgrad, kFamAdam, kFamBwdPair, kFamFwdLds2x2, kFamFwdDirect, kFamHgemmFwd, kFamHgemmDgrad, kFamHgemmWgrad,
+              kFamPerSync, kFamPerSample, kFamPerUpdate, kNumFamily };
 extern const char* const kFamily[kNumFamily];
 struct TimingRec { Family family; hipEvent_t a, b; };
 
@@ -111,6 +113,20 @@ enum GraphSlot {
   kGraphChainPar1,    // ... continued at panel parity 1 ...
   kGraphChainPar0,    // ... and at parity 0
   kNumGraphSlots
+};
+
+// Prioritized replay (dqnhip_per_enable; the kernels and the tree's definition: per_kernels.hip.h).  Owned by the learner that owns the
+// ring; a prioritized learner shares no ring (v1), so that is the learner itself.
+struct PerTreeHost { float* lvl[8] = {nullptr}; int n[8] = {0}; int levels = 0; };      // PerTree's members (per_kernels.hip.h: device code)
+struct PerHost {
+  dqnhip_per_config cfg{};
+  PerTreeHost tree; float* tree_base = nullptr; size_t tree_floats = 0;
+  void* dev = nullptr;                  // PerDev
+  int* idx = nullptr; int* slot = nullptr;          // [B]: the sampler's logical indices (what the gather reads) and physical slots
+  float *prob = nullptr, *u = nullptr, *w = nullptr, *td_abs = nullptr;   // [B]
+  // the host's upper bound on the transitions appended since the last k_per_sync, and whether the ring may have changed at all
+  long long pending = 0; bool changed = false;
+  long long syncs = 0;                  // k_per_sync launches so far
 };
 
 }  // namespace dqnhip_host
@@ -257,6 +273,8 @@ struct dqnhip_learner {
   std::deque<std::pair<unsigned long long, int>> ix_flagged;   // (sequence number, flags that update raised) of harvested updates
   unsigned long long ix_harvested = 0, ix_collected = 0;       // sequence numbers: updates harvested / handed out so far
   int ix_prev_flags = 0;                // the sticky device flags as the last harvested update left them (a raise = a bit not in here)
+  long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
+  PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
 };
 
 namespace dqnhip_host {
@@ -344,6 +362,7 @@ struct UpdatePlan {
   bool first_layers_merged;         // Step(1)'s four first layers in one launch (critic_target's action half in the head kernel)
   bool early_l0;                    // multi-update graphs: next gather in the critic's optimiser launch, next first layers in the actor's
   bool tails_ride;                  // data parallel: the [loss, q, flag] tails block rides in each net's last backward launch (no k_tails launches)
+  bool prioritized;                 // prioritized replay: k_per_sample / k_per_fill before, k_head_q_train_w inside, k_per_update behind every update
 };
 UpdatePlan plan_of(const H* h);
 // the current update's copies of the two double-buffered panels (by update parity inside a multi-update graph that gathers early;
@@ -392,5 +411,14 @@ const char* rccl_path();
 bool same_nets(const H* a, const H* b);
 // k_pack_rows16: fp32 [n][ld_src] (the first S columns of each row) -> fp16 [rows][k16], pad rows and columns zero
 int pack_rows16_launch(hipStream_t st, const float* src, int n, int S, int ld_src, h16* dst, int rows, int k16);
+// prioritized replay: the host launchers of per_kernels.hip.h (learner_io.hip) and what the other units need of it
+int per_sync_if_needed(H* h);                            // k_per_sync, if the ring may have changed since the last one
+void per_note_append(H* h, long long n);                 // BEFORE up to n transitions are appended: keeps the bound below cap (may enqueue a sync)
+int per_sample_launch(H* h);                             // k_per_sample on the live counter -> per->idx / slot / prob
+int per_fill_launch(H* h, const int* idx_dev);           // k_per_fill: explicit indices -> per->slot / prob
+int per_update_launch(H* h);                             // k_per_update
+int per_clear(H* h);                                     // dqnhip_clear_memory: the tree zero, p_max stays
+void per_free(H* h);
+int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
 
 }  // namespace dqnhip_host

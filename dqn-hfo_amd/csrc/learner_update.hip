@@ -38,8 +38,15 @@ int stage_indices(H* h, const int32_t* idx_host, const int** idx_dev) {
   return 0;
 }
 
+// A prioritized learner's update: [sampler | fill for explicit indices] . the stand-alone sequence on the sampler's buffer . write-back
 int run_update(H* h, const int* idx_dev) {
+  if (h->per) {
+    if (h->cap_u >= 0) return fail("internal: a prioritized update inside a multi-update schedule");
+    if (idx_dev) RC(per_fill_launch(h, idx_dev));
+    else { RC(per_sample_launch(h)); idx_dev = h->per->idx; }
+  }
   for (int p = 0; p < 3; ++p) RC(run_phase(h, p, idx_dev));
+  if (h->per) RC(per_update_launch(h));
   return 0;
 }
 
@@ -85,7 +92,8 @@ int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out, int* kernel_no
 // first kernel of the next (kernel trace, profiles/r04_graph_gap.txt; two instances of the graph launched alternately: the same) -
 // 2.8 % of a 300-us update; inside a graph the same boundary is a plain kernel boundary, and the gather of update u + 1 rides in
 // update u's last launch (adam_launch, DevState::gbase).
-static CaptureSpec multi_spec(int n) { CaptureSpec s; s.updates = n; s.multi = true; s.of = n; return s; }
+// (a prioritized learner's graph: n stand-alone sequences back to back — no rider serves a successor)
+static CaptureSpec multi_spec(const H* h, int n) { CaptureSpec s; s.updates = n; s.multi = h->per == nullptr; s.of = n; return s; }
 
 // what each slot of graph_exec captures.  idx_dev: the pipelined slots' index buffer (already on the device)
 static CaptureSpec slot_spec(const H* h, GraphSlot slot, const int* idx_dev) {
@@ -93,7 +101,7 @@ static CaptureSpec slot_spec(const H* h, GraphSlot slot, const int* idx_dev) {
   switch (slot) {
     case kGraphExplicit: s.idx_dev = h->idx_pinned_dev; break;
     case kGraphPipe0: case kGraphPipe1: s.idx_dev = idx_dev; break;
-    case kGraphMulti: s = multi_spec(kMultiU); break;
+    case kGraphMulti: s = multi_spec(h, kMultiU); break;
     // dqnhip_update_chained: ONE update captured as position 0 (head: own gather), 1 or 2 (continued at parity 1 / 0) of a
     // multi-update graph, its riders reading the next update's explicit indices
     case kGraphChainHead: s.chain_pos = 0; s.idx_dev = h->idx_pinned_dev; break;
@@ -143,7 +151,7 @@ static int count_kernel_nodes(hipGraph_t g, int* out) {
 // the kernels `updates` consecutive updates launch — as a multi-update graph captures them (multi) or stand-alone.  A capture that
 // is thrown away: nothing executes, nothing is instantiated.
 static int count_launches(H* h, bool multi, int updates, int* out) {
-  CaptureSpec s; s.updates = updates; s.multi = multi;
+  CaptureSpec s; s.updates = updates; s.multi = multi && h->per == nullptr;
   hipGraph_t graph = nullptr;
   RC(capture_updates(h, s, &graph));
   const int rc = count_kernel_nodes(graph, out);
@@ -243,7 +251,8 @@ int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
                (p.head_rides_a ? DQNHIP_PLAN_HEAD_WGRAD_RIDES_ACTOR : 0) | (p.fuse_q ? DQNHIP_PLAN_Q_TRAIN_IN_DGRAD : 0) |
                (p.fused_seed ? DQNHIP_PLAN_HEAD_SEED_FUSED : 0) | (p.fuse_head ? DQNHIP_PLAN_DQDA_HEAD_BWD : 0) |
                (p.critic_l0 ? DQNHIP_PLAN_CRITIC_L0_RIDES : 0) | (p.first_layers_merged ? DQNHIP_PLAN_FIRST_LAYERS_MERGED : 0) |
-               (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0);
+               (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0) |
+               (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0);
   out->updates_per_graph = kMultiU;
   // per net and update: one all-reduce (per-layer buckets: one per tower layer + the head slice; bf16 exchange: the tails travel in a
   // second call beside the actor's; sharded optimiser: reduce-scatter + the 4-float all-reduce + 2 (fp16 learner: 4) all-gathers)
@@ -269,6 +278,7 @@ int dqnhip_update_async(dqnhip_handle h, const int32_t* idx_host) {
   RC(sync_dirty16(h));
   const int* idx_dev = nullptr;
   RC(stage_indices(h, idx_host, &idx_dev));
+  RC(per_sync_if_needed(h));
   return replay_or_run(h, idx_host ? kGraphExplicit : kGraphSampled, idx_dev);
 }
 
@@ -283,6 +293,7 @@ int dqnhip_update_async_n(dqnhip_handle h, int32_t n) {
   RC(sync_dirty16(h));
   if (RO(h)->h_size < 1) RC(refresh_ring(h));
   if (RO(h)->h_size < 1) return fail("replay memory is empty");
+  RC(per_sync_if_needed(h));
   hipGraphExec_t g;
   while (n >= kMultiU && (g = graph_of(h, kGraphMulti)) != nullptr) { RC(replay(h, g, kMultiU)); n -= kMultiU; }
   // the remainder as graphs of 8 / 4 / 2 updates (the same launch sequence as the sixteen-update graph, cut shorter), then one by
@@ -290,7 +301,7 @@ int dqnhip_update_async_n(dqnhip_handle h, int32_t n) {
   // (the driver's 20 timed steps are 16 + 4)
   for (int k = 0; k < 3; ++k) {
     const int sz = 8 >> k;
-    if (n >= sz && (g = graph_of(h, &h->graph_small[k], multi_spec(sz))) != nullptr) { RC(replay(h, g, sz)); n -= sz; }
+    if (n >= sz && (g = graph_of(h, &h->graph_small[k], multi_spec(h, sz))) != nullptr) { RC(replay(h, g, sz)); n -= sz; }
   }
   for (; n > 0; --n) RC(replay_or_run(h, kGraphSampled, nullptr));
   return 0;
@@ -303,6 +314,7 @@ int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host, int32_t n)
   if (!h) return fail("null handle");
   h->epoch += 1;
   if (n < 0) return fail("dqnhip_update_indexed_n: n must be >= 0");
+  RC(per_refuse(h, "dqnhip_update_indexed_n"));
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_indexed_n: a phased update is in progress (next phase %d)", h->next_phase);
@@ -370,6 +382,7 @@ int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss, float* avg_q, int3
 
 int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host) {
   if (!h) return fail("null handle");
+  RC(per_refuse(h, "dqnhip_update_phase"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   // (with DQNHIP_DP_HALF_GRADS the exchange — bf16 image, all-reduce, widening by the clip-norm pass — lives inside
@@ -496,6 +509,7 @@ int dqnhip_update(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, 
 int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_t* idx_next, float* critic_loss, float* avg_q) {
   if (!h) return fail("null handle");
   if (!idx_host) return fail("dqnhip_update_chained: explicit indices required (on-device sampling: dqnhip_update_async_n)");
+  RC(per_refuse(h, "dqnhip_update_chained"));
   HIPCHK(hipSetDevice(h->cfg.device));
   const UpdatePlan P = plan_of(h);
   const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && h->sharers == 0 && h->w_owner == nullptr;
@@ -542,6 +556,7 @@ int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_
 // every call.  Indices and scalars use two pinned slots each (nothing in flight is overwritten).
 int dqnhip_update_pipelined(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, float* avg_q) {
   if (!h) return fail("null handle");
+  RC(per_refuse(h, "dqnhip_update_pipelined"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");

@@ -647,6 +647,53 @@ class DQN:
                 "launches_graph_first": p.launches_graph_first, "launches_in_graph": p.launches_in_graph,
                 "updates_per_graph": p.updates_per_graph, "collectives": p.collectives}
 
+    # -- prioritized replay (include/dqnhip.h: no reference counterpart, off unless enabled) -----------------
+    def enable_prioritized_replay(self, alpha=None, beta0=None, beta_anneal_iters=None, eps=None, seed=None):
+        """dqnhip_per_enable.  Arguments left None keep dqnhip_per_default_config's values: the customary ones of Schaul et al.
+        2016, not measured on this workload."""
+        c = capi.PerConfig()
+        self.lib.dqnhip_per_default_config(C.byref(c))
+        for name, v in (("alpha", alpha), ("beta0", beta0), ("beta_anneal_iters", beta_anneal_iters), ("eps", eps), ("seed", seed)):
+            if v is not None:
+                setattr(c, name, v)
+        self._ck(self.lib.dqnhip_per_enable(self.h, C.byref(c)))
+
+    def per_state(self):
+        """dqnhip_per_get_state as a dict."""
+        s = capi.PerState()
+        s.struct_size = C.sizeof(capi.PerState)
+        self._ck(self.lib.dqnhip_per_get_state(self.h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in capi.PerState._fields_ if name not in ("struct_size", "reserved")}
+
+    def per_priorities(self, first, n):
+        """the stored leaves (p^alpha) of the logical range [first, first + n)"""
+        out = np.empty(int(n), np.float32)
+        self._ck(self.lib.dqnhip_per_get_priorities(self.h, int(first), int(n), _p(out)))
+        return out
+
+    def set_per_priorities(self, first, p):
+        a = _f32(p)
+        self._ck(self.lib.dqnhip_per_set_priorities(self.h, int(first), a.size, _p(a)))
+
+    def per_sample(self, counter, n_batches=1):
+        """The sampler alone -> (idx [n_batches][B] int32, prob [n_batches][B] float32)."""
+        B = self.kMinibatchSize
+        idx, prob = np.empty((int(n_batches), B), np.int32), np.empty((int(n_batches), B), np.float32)
+        self._ck(self.lib.dqnhip_per_sample(self.h, int(counter), int(n_batches), idx.ctypes.data_as(capi.ip), _p(prob)))
+        return idx, prob
+
+    def per_debug_read(self, name):
+        """"level<k>" (every real node of the level) or one of "u", "slot", "prob", "w", "td_abs" ([B], "slot" as int64)."""
+        if name.startswith("level"):
+            n = self.cfg.replay_capacity
+            for _ in range(int(name[5:])):
+                n = (n + 63) // 64
+        else:
+            n = self.kMinibatchSize
+        out = np.empty(n, np.float32)
+        self._ck(self.lib.dqnhip_per_debug_read(self.h, name.encode(), _p(out), out.size))
+        return out.astype(np.int64) if name == "slot" else out
+
     def set_kernel_timing(self, enable):
         self._ck(self.lib.dqnhip_set_kernel_timing(self.h, int(enable)))
 

@@ -322,6 +322,7 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world);
 #define DQNHIP_PLAN_FIRST_LAYERS_MERGED 1024    /* Step(1)'s four first layers in one launch (DQNHIP_TUNE_SEPARATE_CRITIC_FIRST_LAYERS) */
 #define DQNHIP_PLAN_EARLY_GATHER_L0 2048        /* multi-update graphs: next gather / next first layers ride in the two optimiser launches (DQNHIP_TUNE_LATE_GATHER) */
 #define DQNHIP_PLAN_DP_TAILS_RIDE 4096          /* data parallel: the [loss, q, flag] tails of the exchange ride in each net's last backward launch */
+#define DQNHIP_PLAN_PRIORITIZED 8192            /* prioritized replay (dqnhip_per_enable): sampler / fill before, k_head_q_train_w inside, the write-back behind every update */
 typedef struct dqnhip_update_plan {
   int32_t struct_size;          /* in: sizeof(dqnhip_update_plan) */
   int32_t forms;                /* DQNHIP_PLAN_* bits */
@@ -652,6 +653,61 @@ int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
  * slices go stale: dqnhip_dp_gather_state (collective) brings them back before a snapshot / dqnhip_get_params(KIND_M, KIND_V);
  * dqnhip_dp_destroy refuses until it has been called since the last update.  Combines with DQNHIP_DP_HALF_GRADS, not with
  * DQNHIP_DP_PER_LAYER; the arena must be divisible by 4 x dp_world.  dqnhip_apply_update_sharded pins its slice arithmetic on one GPU. */
+
+/* ---- prioritized experience replay (opt-in) -------------------------------------------------------------------------------
+ * No reference counterpart: the reference samples its deque uniformly (SampleTransitionsFromMemory, src/dqn.cpp:501-509), and so
+ * does every learner that never calls dqnhip_per_enable — it launches exactly the kernels it launched before this section existed.
+ * Proportional prioritization (Schaul et al. 2016): a transition is drawn with probability p^alpha / sum, the critic's loss is
+ * corrected by the importance weight (pmin / prob)^beta (normalised by the minibatch's largest weight), and |TD error| + eps is written
+ * back as the new priority.  All of it on the device: a radix-64 float32 sum tree over the ring's physical slots (a node = the sum
+ * of its 64 children in one fixed order, always recomputed from them — csrc/per_kernels.hip.h has the definition), a stratified
+ * sampler in front of every update, k_head_q_train_w in k_head_q_train's place, the write-back behind the update's last launch.  A
+ * new transition gets p_max, the largest priority written so far (initially 1); FIFO eviction zeroes its slot's leaf.
+ * Schedule: fp32 learners take the DQNHIP_TUNE_SEPARATE_Q_TRAIN form; inside dqnhip_update_async_n's graphs the updates are the
+ * stand-alone sequence back to back (no rider carries the next update's gather: its indices do not exist before this update's
+ * write-back).  Explicit indices (dqnhip_update(h, idx, ...), dqnhip_update_async(h, idx)) skip the sampler: their slots and
+ * probabilities are read from the tree, the rest is the same.
+ * v1 refuses, on a prioritized learner: dqnhip_update_chained / _pipelined / _indexed_n / _phase, dqnhip_dp_init*, dp_world > 1,
+ * dqnhip_share_replay_memory in either role (and enabling on a learner that already shares a ring).
+ * The defaults are the customary values of the paper, NOT measured on this workload. */
+typedef struct dqnhip_per_config {
+  int32_t struct_size;       /* in: sizeof(dqnhip_per_config) */
+  float alpha;               /* 0.6; 0: uniform */
+  float beta0;               /* 0.4; the importance exponent at critic iteration 0 */
+  int32_t beta_anneal_iters; /* 0: constant; else beta = min(1, beta0 + (1 - beta0) critic_iter / beta_anneal_iters), on the device */
+  float eps;                 /* 1e-6 */
+  uint64_t seed;             /* Philox key of the sampler */
+} dqnhip_per_config;
+void dqnhip_per_default_config(dqnhip_per_config* cfg);
+
+/* Once per learner; freed by dqnhip_destroy; drops the captured update graphs; transitions already in the memory get p_max. */
+int dqnhip_per_enable(dqnhip_handle h, const dqnhip_per_config* cfg);
+
+typedef struct dqnhip_per_state {
+  int32_t struct_size;       /* in: sizeof(dqnhip_per_state) */
+  int32_t enabled;           /* 0: every other field is 0 */
+  int32_t levels;            /* tree levels above the leaves */
+  int32_t size;              /* transitions in the window the tree describes */
+  float total, p_max, beta_now, reserved;
+  uint64_t next_counter;     /* the Philox counter the next device-sampled update draws on */
+  int64_t syncs;             /* k_per_sync launches so far */
+} dqnhip_per_state;
+/* Stream-ordered, blocks; brings the tree in step with the ring first. */
+int dqnhip_per_get_state(dqnhip_handle h, dqnhip_per_state* out);
+
+/* The leaves (p^alpha, as stored) of the logical range [first, first + n); syncs first. */
+int dqnhip_per_get_priorities(dqnhip_handle h, int32_t first, int32_t n, float* leaf_host);
+/* Finite, >= 0; stored as given; the nodes above are recomputed; raises p_max to the largest of them. */
+int dqnhip_per_set_priorities(dqnhip_handle h, int32_t first, int32_t n, const float* leaf_host);
+
+/* The sampler alone: n_batches minibatches on the counters counter .. counter + n_batches - 1, as logical indices
+ * idx_host[n_batches][minibatch] and their probabilities prob_host (either may be NULL).  Touches neither the learner's counter
+ * nor the tree; with counter = dqnhip_per_state.next_counter the first minibatch is what the next update draws. */
+int dqnhip_per_sample(dqnhip_handle h, uint64_t counter, int32_t n_batches, int32_t* idx_host, float* prob_host);
+
+/* "level<k>" (k = 0: the cap leaves by PHYSICAL slot; level k has ceil(cap / 64^k) nodes, the last one is the total), and of the
+ * last update, [minibatch] each: "u", "slot", "prob", "w", "td_abs".  count: floats the buffer holds. */
+int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
 
 /* ---- batched env front-end (HFOGameState reward shaping, N workers) ----- */
 
