@@ -69,6 +69,17 @@ class PerState(C.Structure):
                 ("next_counter", C.c_uint64), ("syncs", C.c_int64)]
 
 
+class StateInfo(C.Structure):
+    """struct dqnhip_state_info / dqnhip_state_info_t (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("version", C.c_int32), ("flags", C.c_int32), ("precision", C.c_int32), ("minibatch", C.c_int32),
+                ("state_size", C.c_int32), ("num_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_HIDDEN), ("replay_capacity", C.c_int32),
+                ("memory_size", C.c_int32), ("actor_iter", C.c_int32), ("critic_iter", C.c_int32), ("has_memory", C.c_int32),
+                ("has_per", C.c_int32), ("has_loss_scale", C.c_int32), ("seed", C.c_uint64), ("update_counter", C.c_uint64),
+                ("user_bytes", C.c_uint64), ("file_bytes", C.c_uint64)]
+
+
+STATE_NO_MEMORY = 1      # DQNHIP_STATE_NO_MEMORY
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int32)
 up = C.POINTER(C.c_uint8)
@@ -161,6 +172,10 @@ SIGNATURES = {
     "dqnhip_per_set_priorities": (C.c_int, [H, C.c_int32, C.c_int32, fp]),
     "dqnhip_per_sample": (C.c_int, [H, C.c_uint64, C.c_int32, ip, fp]),
     "dqnhip_per_debug_read": (C.c_int, [H, C.c_char_p, fp, C.c_size_t]),
+    "dqnhip_save_state": (C.c_int, [H, C.c_char_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "dqnhip_load_state": (C.c_int, [H, C.c_char_p]),
+    "dqnhip_state_info": (C.c_int, [C.c_char_p, C.POINTER(StateInfo)]),
+    "dqnhip_state_read_user": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
 class EnvConfig(C.Structure):

@@ -16,6 +16,8 @@
 
 #include <chrono>
 #include <cstdio>
+#include <cstring>
+#include <fstream>
 #include <sstream>
 
 namespace dqn {
@@ -54,6 +56,10 @@ DEFINE_bool(prioritized_replay, false, "Proportional prioritized experience repl
 DEFINE_double(per_alpha, 0.6, "-prioritized_replay: the priority exponent (0: uniform). The paper's customary value, not measured on this workload.");
 DEFINE_double(per_beta, 0.4, "-prioritized_replay: the importance exponent at critic iteration 0. The paper's customary value, not measured on this workload.");
 DEFINE_int32(per_beta_anneal_iters, 0, "-prioritized_replay: critic iterations over which the importance exponent rises linearly to 1 (0: constant).");
+DEFINE_bool(native_state, false, "Snapshot() additionally writes <prefix>_iter_<N>.learnerstate (dqnhip_save_state: targets, sampling counters, loss-scale "
+            "state, the ring's position, priorities, this object's random_engine and smoothed sums), and RestoreCriticSolver() loads the one "
+            "that belongs to the restored iterations: resume is then bit-identical to never having stopped. The reference's files are "
+            "written and read as without the flag.");
 DEFINE_bool(device_sampling, false, "Sample minibatch indices on the device (counter-based) instead of the host std::mt19937.");
 DEFINE_bool(chained_updates, true, "UpdateActorCritic() tells the library which indices the NEXT call will draw (a copy of the engine runs ahead; "
             "dqnhip_update_chained): bursts of Update() get the launch schedule of a multi-update graph.  Same results, same RNG order.");
@@ -413,11 +419,23 @@ void DQN::Benchmark(int iterations) {
 }
 
 void DQN::RestoreActorSolver(const std::string& f) { CollectDeferred(); RearmReplicaSync("RestoreActorSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_ACTOR, f.c_str())); last_snapshot_iter_ = max_iter(); }
-void DQN::RestoreCriticSolver(const std::string& f) { CollectDeferred(); RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter(); }
+void DQN::RestoreCriticSolver(const std::string& f) {
+  CollectDeferred(); RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter();
+  if (FLAGS_native_state) LoadNativeState(f);      // (the later of the driver's two restore calls, src/dqn_main.cpp:268-275)
+}
 void DQN::LoadActorWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadActorWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_ACTOR, f.c_str())); }
 void DQN::LoadCriticWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadCriticWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_CRITIC, f.c_str())); }
 void DQN::LoadReplayMemory(const std::string& f) {
   SubmitPending();
+  if (FLAGS_native_state && native_has_memory_) {
+    // <stem>_iter_<N>.replaymemory of the prefix the learner state came from: loading it would put logical 0 back at slot 0 and reset the priorities
+    const std::string head = native_stem_ + "_iter_", tail = ".replaymemory";
+    if (f.size() > head.size() + tail.size() && f.compare(0, head.size(), head) == 0 && f.compare(f.size() - tail.size(), tail.size(), tail) == 0 &&
+        f.find_first_not_of("0123456789", head.size()) == f.size() - tail.size()) {
+      LOG(INFO) << "Skipping " << f << ": the learner state already restored the replay memory (replay_mem_size = " << memory_size() << ")";
+      return;
+    }
+  }
   LOG(INFO) << "Loading replay memory from " << f;
   DQNHIP_CK(dqnhip_load_replay_memory(h_, f.c_str()));
   LOG(INFO) << "replay_mem_size = " << memory_size();
@@ -429,7 +447,65 @@ void DQN::Snapshot(const std::string& snapshot_prefix, bool remove_old, bool sna
   SubmitPending();
   if (snapshot_memory) LOG(INFO) << "Snapshotting memory to " << snapshot_prefix << "_iter_" << max_iter() << ".replaymemory";
   DQNHIP_CK(dqnhip_snapshot(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, snapshot_memory));
+  if (FLAGS_native_state) SaveNativeState(snapshot_prefix, remove_old, snapshot_memory);
   LOG(INFO) << "Snapshotting Finished!";
+}
+
+// ---- -native_state ----------------------------------------------------------------------------------------------------------
+// What the learner-state file's user section carries of THIS object: the engine's operator<< text, the two running sums behind the
+// smoothed log lines (their float bits: nothing else accumulates, the divisor is the flag) and last_snapshot_iter_ as it stands
+// once the snapshot is done (Update()'s own snapshot assigns max_iter() right after Snapshot() returns).
+void DQN::SaveNativeState(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory) {
+  if (dp_) { LOG(WARNING) << "[Agent" << tid_ << "] -native_state: a data-parallel learner writes no learner state (not supported in this version)"; return; }
+  if (!snapshot_from_update_) CollectDeferred();   // (a snapshot the driver asks for: the sums below must hold every update the learner has run)
+  const std::string f = snapshot_prefix + "_iter_" + std::to_string(max_iter()) + ".learnerstate";
+  LOG(INFO) << "Snapshotting learner state to " << f;
+  uint32_t bits[2];
+  static_assert(sizeof(float) == sizeof(uint32_t), "the sums travel as their bits");
+  memcpy(&bits[0], &smoothed_critic_loss_, 4); memcpy(&bits[1], &smoothed_actor_loss_, 4);
+  std::ostringstream user;
+  user << "dqn_dropin_state 1\n" << random_engine << "\n" << bits[0] << " " << bits[1] << "\n"
+       << (snapshot_from_update_ ? max_iter() : last_snapshot_iter_) << "\n";
+  const std::string u = user.str();
+  DQNHIP_CK(dqnhip_save_state(h_, f.c_str(), snapshot_memory ? 0 : DQNHIP_STATE_NO_MEMORY, u.data(), u.size()));
+  if (remove_old) RemoveSnapshots(snapshot_prefix + "_iter_[0-9]+\\.learnerstate", critic_iter() - 1);      // the .replaymemory files' rule (src/dqn.cpp:612-618)
+}
+
+// f: <stem>_critic_iter_<N>.solverstate, just restored.  The learner state of the same snapshot is <stem>_iter_<max_iter()>.learnerstate
+// and says which iterations it was taken at: only a file of exactly the restored pair is loaded.
+void DQN::LoadNativeState(const std::string& f) {
+  const size_t pos = f.rfind("_critic_iter_");
+  if (pos == std::string::npos) return;
+  const std::string stem = f.substr(0, pos), file = stem + "_iter_" + std::to_string(max_iter()) + ".learnerstate";
+  if (!std::ifstream(file).good()) { LOG(INFO) << "[Agent" << tid_ << "] -native_state: no " << file << ", resuming from the solver states alone"; return; }
+  if (dp_) { LOG(WARNING) << "[Agent" << tid_ << "] -native_state: " << file << " is not loaded into a data-parallel learner (not supported in this version)"; return; }
+  dqnhip_state_info_t info;
+  info.struct_size = (int32_t)sizeof info;
+  if (dqnhip_state_info(file.c_str(), &info) != 0) {
+    LOG(WARNING) << "[Agent" << tid_ << "] -native_state: " << dqnhip_last_error() << " - resuming from the solver states alone";
+    return;
+  }
+  if (info.actor_iter != actor_iter() || info.critic_iter != critic_iter()) {
+    LOG(WARNING) << "[Agent" << tid_ << "] -native_state: " << file << " was taken at (actor_iter, critic_iter) = (" << info.actor_iter << ", " << info.critic_iter
+                 << "), the solver states restored (" << actor_iter() << ", " << critic_iter() << ") - resuming from the solver states alone";
+    return;
+  }
+  DQNHIP_CK(dqnhip_load_state(h_, file.c_str()));
+  std::string u((size_t)info.user_bytes, '\0');
+  size_t n = 0;
+  DQNHIP_CK(dqnhip_state_read_user(file.c_str(), &u[0], u.size(), &n));
+  std::istringstream in(u.substr(0, n));
+  std::string magic; int version = 0; uint32_t bits[2] = {0, 0}; int last = 0;
+  std::mt19937 engine;
+  in >> magic >> version >> engine >> bits[0] >> bits[1] >> last;
+  if (!in || magic != "dqn_dropin_state" || version != 1)
+    LOG(FATAL) << "[Agent" << tid_ << "] -native_state: " << file << ": the user section is not this adaptor's (the learner itself has been restored)";
+  random_engine = engine;
+  memcpy(&smoothed_critic_loss_, &bits[0], 4); memcpy(&smoothed_actor_loss_, &bits[1], 4);
+  last_snapshot_iter_ = last;
+  spec_valid_ = false;                             // (a prediction drawn before the restore is nobody's next minibatch)
+  native_stem_ = stem; native_has_memory_ = info.has_memory != 0;
+  LOG(INFO) << "[Agent" << tid_ << "] -native_state: resumed from " << file << (native_has_memory_ ? " (with the replay memory: replay_mem_size = " + std::to_string(memory_size()) + ")" : " (without a replay memory)");
 }
 
 ActorOutput DQN::GetRandomActorOutput() {
@@ -571,7 +647,9 @@ void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_
     LOG(INFO) << "[Agent" << tid_ << "] Loss scale: critic x" << ls.mult_critic << ", actor x" << ls.mult_actor << ", skipped steps = " << ls.skipped_steps;
   }
   if (critic_it >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_it >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
+    snapshot_from_update_ = true;
     Snapshot();
+    snapshot_from_update_ = false;
     last_snapshot_iter_ = max_iter();
   }
 }

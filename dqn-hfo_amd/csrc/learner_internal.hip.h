@@ -11,7 +11,9 @@
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
 //                       introspection
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
+//   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state; host only
 //   snapshot.cpp        Caffe snapshot layout (no device code)
+//   state_codec.cpp     the learner-state file's container (header, table, CRCs), dqnhip_state_info / _read_user (no device code, no HIP)
 // This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
 // of the kernels it launches and embeds exactly those (tests/test_kernel_inventory.py), the host-only units embed no device code.
 // A launch attribute (hipFuncSetAttribute) of a kernel with internal linkage holds for the calling unit's copy only: it is set in
@@ -419,6 +421,8 @@ int per_fill_launch(H* h, const int* idx_dev);           // k_per_fill: explicit
 int per_update_launch(H* h);                             // k_per_update
 int per_clear(H* h);                                     // dqnhip_clear_memory: the tree zero, p_max stays
 void per_free(H* h);
+int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behind everything enqueued so far
+int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
 int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
 
 }  // namespace dqnhip_host

@@ -493,6 +493,30 @@ int per_clear(H* h) {
   p->pending = 0; p->changed = false;
   return 0;
 }
+// dqnhip_save_state / dqnhip_load_state (learner_state.hip, which launches nothing and does not see PerDev)
+int per_read_p_max(H* h, float* p_max) {
+  HIPCHK(hipMemcpyAsync(p_max, &((PerDev*)h->per->dev)->p_max, sizeof *p_max, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// The tree of a window of `size` transitions at physical slot `head` (the ring's DevState already says so) with the given leaves, logical
+// order: everything zero, the leaves and the level-1 nodes above them by the set pass, every node of the levels above recomputed — a
+// node is the sum of its 64 children in one fixed order whoever computes it, so these are the bits of the tree the leaves were read from
+int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs) {
+  PerHost* p = h->per;
+  HIPCHK(hipStreamSynchronize(h->stream));         // the staging buffer may still be in flight
+  HIPCHK(hipMemsetAsync(p->tree_base, 0, p->tree_floats * sizeof(float), h->stream));
+  const PerDev d{p_max, head, size, 0};
+  HIPCHK(hipMemcpyAsync(p->dev, &d, sizeof d, hipMemcpyHostToDevice, h->stream));
+  if (size > 0) {
+    RC(ensure_stage(h, (size_t)size * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(h->stage_dev, leaves, (size_t)size * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    RC(per_sync_launch(h, (const float*)h->stage_dev, 0, size));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));         // (d is on this stack, leaves the caller's)
+  p->pending = 0; p->changed = false; p->syncs = syncs;
+  return 0;
+}
 void per_free(H* h) {
   PerHost* p = h->per;
   if (!p) return;

@@ -1,0 +1,58 @@
+// state_codec.h — the learner-state file's container (DESIGN.md 9 has the byte layout): what learner_state.hip needs of
+// state_codec.cpp.  Host code only; not installed, not part of the C-ABI.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/dqnhip.h"
+
+namespace dqnhip_state {
+
+constexpr uint32_t kVersion = 1;
+constexpr size_t kHeaderBytes = 144, kEntryBytes = 24;
+constexpr uint32_t kMaxSections = 64;
+
+constexpr uint32_t tag4(char a, char b, char c, char d) {
+  return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
+}
+// parameter sections: dense Caffe order (dqnhip_get_params), float32.  WGT<net>, ADM<net> (Adam m), ADV<net> (Adam v)
+constexpr uint32_t kTagW[4] = {tag4('W', 'G', 'T', '0'), tag4('W', 'G', 'T', '1'), tag4('W', 'G', 'T', '2'), tag4('W', 'G', 'T', '3')};
+constexpr uint32_t kTagM[2] = {tag4('A', 'D', 'M', '0'), tag4('A', 'D', 'M', '1')};
+constexpr uint32_t kTagV[2] = {tag4('A', 'D', 'V', '0'), tag4('A', 'D', 'V', '1')};
+constexpr uint32_t kTagDev = tag4('D', 'E', 'V', 'S'), kTagLossScale = tag4('L', 'S', 'C', 'L'), kTagHost = tag4('H', 'O', 'S', 'T');
+constexpr uint32_t kTagRing = tag4('R', 'I', 'N', 'G'), kTagStates = tag4('R', 'S', 'T', 'A'), kTagNext = tag4('R', 'N', 'X', 'T'),
+                   kTagAct = tag4('R', 'A', 'C', 'T'), kTagReward = tag4('R', 'R', 'E', 'W'), kTagMc = tag4('R', 'M', 'C', 'T'),
+                   kTagTerm = tag4('R', 'T', 'R', 'M');
+constexpr uint32_t kTagPerCfg = tag4('P', 'E', 'R', 'C'), kTagPerLeaves = tag4('P', 'E', 'R', 'L'), kTagUser = tag4('U', 'S', 'E', 'R');
+
+// the fixed-size sections, as they lie in the file (little endian, no padding inside)
+struct DevSection { int32_t actor_iter, critic_iter; uint64_t update_counter; float critic_loss, avg_q; int32_t flags, skipped_steps; };
+struct LossScaleSection { float mult[2]; int32_t good[2], backoffs[2], growths[2]; };      // [actor, critic]
+struct HostSection { uint64_t sample_states_calls, seed; };
+struct RingSection { int32_t ring_head, ring_size; };
+struct PerSection { float alpha, beta0; int32_t beta_anneal_iters; float eps; uint64_t seed; float p_max; int32_t reserved; int64_t syncs; };
+static_assert(sizeof(DevSection) == 32 && sizeof(LossScaleSection) == 32 && sizeof(HostSection) == 16 && sizeof(RingSection) == 8 &&
+              sizeof(PerSection) == 40, "the sections have no padding");
+
+struct Section { uint32_t tag; const void* data; uint64_t bytes; };
+struct Entry { uint32_t tag, crc; uint64_t offset, bytes; };
+
+std::string tag_name(uint32_t tag);
+
+// Writes header, table and the sections back to back into filename + ".tmp" and renames it over filename.  info: every field the
+// header stores except user_bytes and file_bytes, which are derived here.  On failure *err says why and filename is untouched.
+int write_file(const char* filename, const dqnhip_state_info_t& info, const std::vector<Section>& sections, std::string* err);
+
+struct Parsed {
+  dqnhip_state_info_t info{};
+  std::vector<Entry> table;
+  std::vector<uint8_t> file;       // the whole file (keep = true)
+  const Entry* find(uint32_t tag) const { for (const Entry& e : table) if (e.tag == tag) return &e; return nullptr; }
+  const uint8_t* at(const Entry* e) const { return file.data() + e->offset; }
+};
+// Reads and validates: magic, version, header CRC; the table's CRC and the section bounds; every section's CRC.  keep: the file
+// stays in out->file (dqnhip_load_state); else the sections are streamed through the CRC only.
+int read_file(const char* filename, Parsed* out, bool keep, std::string* err);
+
+}  // namespace dqnhip_state

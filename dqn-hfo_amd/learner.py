@@ -694,6 +694,17 @@ class DQN:
         self._ck(self.lib.dqnhip_per_debug_read(self.h, name.encode(), _p(out), out.size))
         return out.astype(np.int64) if name == "slot" else out
 
+    # -- native learner-state file (include/dqnhip.h: exact resume, opt-in) ----------------------------------
+    def save_state(self, path, memory=True, user=b""):
+        """dqnhip_save_state: everything a bit-exact resume needs, in one file; `user` is an opaque section of the caller's."""
+        user = bytes(user)
+        self._ck(self.lib.dqnhip_save_state(self.h, os.fsencode(path), 0 if memory else capi.STATE_NO_MEMORY, user or None, len(user)))
+
+    def load_state(self, path):
+        """dqnhip_load_state: validates the whole file first; a failure leaves the learner untouched."""
+        self._ck(self.lib.dqnhip_load_state(self.h, os.fsencode(path)))
+        self.cfg.seed = state_info(path)["seed"]        # the learner adopted the file's sampling key
+
     def set_kernel_timing(self, enable):
         self._ck(self.lib.dqnhip_set_kernel_timing(self.h, int(enable)))
 
@@ -710,6 +721,29 @@ def FindLatestSnapshot(snapshot_prefix):
     if lib.dqnhip_find_latest_snapshot(os.fsencode(snapshot_prefix), bufs[0], bufs[1], bufs[2], 4096) != 0:
         raise DQNFatal(lib.dqnhip_last_error().decode())
     return tuple(os.fsdecode(b.value) for b in bufs)
+
+
+def state_info(path):
+    """dqnhip_state_info as a dict (no GPU needed): validates the whole file and reports its header."""
+    lib = capi.load()
+    s = capi.StateInfo()
+    s.struct_size = C.sizeof(capi.StateInfo)
+    if lib.dqnhip_state_info(os.fsencode(path), C.byref(s)) != 0:
+        raise DQNFatal(lib.dqnhip_last_error().decode())
+    d = {name: getattr(s, name) for name, _ in capi.StateInfo._fields_ if name not in ("struct_size", "hidden")}
+    d["hidden"] = tuple(s.hidden[i] for i in range(max(0, min(s.num_hidden, capi.MAX_HIDDEN))))
+    return d
+
+
+def state_user(path):
+    """dqnhip_state_read_user: the caller's section of a learner-state file as bytes (no GPU needed)."""
+    lib = capi.load()
+    n = C.c_size_t()
+    cap = max(1, state_info(path)["user_bytes"])
+    buf = C.create_string_buffer(cap)
+    if lib.dqnhip_state_read_user(os.fsencode(path), buf, cap, C.byref(n)) != 0:
+        raise DQNFatal(lib.dqnhip_last_error().decode())
+    return buf.raw[:n.value]
 
 
 def FindHiScore(snapshot_prefix):

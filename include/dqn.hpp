@@ -162,6 +162,12 @@ class DQN {
   void SubmitPending();                                // pending indices -> dqnhip_update_indexed_n (no host wait)
   void CollectDeferred(bool bookkeep = true);          // submit, wait, replay Bookkeep for every outstanding update in order
   void StopDeferring();                                // collect, then every Update() takes the blocking path again
+  // -native_state: Snapshot() also writes <prefix>_iter_<N>.learnerstate (dqnhip_save_state), RestoreCriticSolver() loads the one
+  // that belongs to the restored iterations, and a later LoadReplayMemory of the same prefix is skipped if that file held the memory
+  bool snapshot_from_update_ = false;                  // Snapshot() is running inside Update()'s bookkeeping (which assigns last_snapshot_iter_ next)
+  std::string native_stem_; bool native_has_memory_ = false;
+  void SaveNativeState(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory);
+  void LoadNativeState(const std::string& critic_solverstate);
   dqnhip_handle h_;
 };
 

@@ -127,7 +127,8 @@ typedef struct dqnhip_config {
    *                                the multiplier doubles, up to loss_scale_max_mult.
    * Gradients (dqnhip_get_params(.., DQNHIP_KIND_G)) are unscaled in either mode, and a dynamic learner
    * whose multipliers are m computes, bit for bit, what a static one with loss_scale x m computes.
-   * dqnhip_apply_update* never move the multipliers.  Snapshots do not carry them. */
+   * dqnhip_apply_update* never move the multipliers.  The Caffe snapshots do not carry them; the learner-state file
+   * (dqnhip_save_state) does. */
   int32_t loss_scale_mode;            /* DQNHIP_LOSS_SCALE_STATIC (default) / DQNHIP_LOSS_SCALE_DYNAMIC            */
   int32_t loss_scale_growth_interval; /* finite steps in a row before the multiplier doubles; 0: never grow.
                                          Default 2000, the customary value of mixed-precision trainers —
@@ -663,6 +664,7 @@ int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
  * of its 64 children in one fixed order, always recomputed from them — csrc/per_kernels.hip.h has the definition), a stratified
  * sampler in front of every update, k_head_q_train_w in k_head_q_train's place, the write-back behind the update's last launch.  A
  * new transition gets p_max, the largest priority written so far (initially 1); FIFO eviction zeroes its slot's leaf.
+ * `.replaymemory` files carry no priorities (a load gives every transition p_max); the learner-state file (dqnhip_save_state) does.
  * Schedule: fp32 learners take the DQNHIP_TUNE_SEPARATE_Q_TRAIN form; inside dqnhip_update_async_n's graphs the updates are the
  * stand-alone sequence back to back (no rider carries the next update's gather: its indices do not exist before this update's
  * write-back).  Explicit indices (dqnhip_update(h, idx, ...), dqnhip_update_async(h, idx)) skip the sampler: their slots and
@@ -708,6 +710,53 @@ int dqnhip_per_sample(dqnhip_handle h, uint64_t counter, int32_t n_batches, int3
 /* "level<k>" (k = 0: the cap leaves by PHYSICAL slot; level k has ceil(cap / 64^k) nodes, the last one is the total), and of the
  * last update, [minibatch] each: "u", "slot", "prob", "w", "td_abs".  count: floats the buffer holds. */
 int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
+
+/* ---- native learner-state file: exact resume (opt-in) -------------------------------------------------------------------------
+ * No reference counterpart: the reference resumes from its three snapshot files (src/dqn_main.cpp:213-220, 268-286), which cannot
+ * hold what this learner keeps on the device beside the weights — the target nets (Restore re-clones them), the sampling
+ * counters, the loss-scale multipliers, the ring's physical position, the priority tree.  One file, written and read by the
+ * two calls below, holds all of it, with one guarantee: save, destroy, create, load, continue computes bit for bit what the
+ * learner would have computed had it never stopped.  A learner that never calls them does what it did; the reference's files are
+ * written and read as before.  Byte layout: DESIGN.md 9 (tests/state_ref.py reads and writes it from that description alone).
+ *
+ * dqnhip_save_state waits for the learner's stream, brings a priority tree in step with the ring, writes filename + ".tmp" and
+ * renames it over filename (a job killed mid-write never leaves a truncated latest file; a failed save leaves an existing file
+ * alone).  Saved: the four nets' weights and m / v of the two online nets (dense Caffe order); both iterations, the sampling
+ * counter, the last (critic_loss, avg_q), the sticky flags as they are, skipped_steps, the loss-scale state of a dynamic learner;
+ * the dqnhip_sample_states call count and cfg.seed; unless DQNHIP_STATE_NO_MEMORY: (ring_head, ring_size) and the window's
+ * transitions in logical order and, on a prioritized learner, dqnhip_per_config, p_max, the sync count and the window's leaves;
+ * the caller's opaque `user` bytes.  NOT saved: gradient arenas, the last update's intermediates (dqnhip_debug_read,
+ * dqnhip_get_actor_output), uncollected dqnhip_collect_stats pairs, the pipelined lag slot, the acting precision (a runtime
+ * switch), env front-end handles (their open episodes are lost, as the reference loses a half-played episode).
+ *
+ * dqnhip_load_state reads and validates the WHOLE file before it touches the learner: any failure leaves the learner bit for bit
+ * as it was, and the message names the file and what failed.  In this order: magic, version, header CRC; the table's CRC, the
+ * section bounds, every section's CRC; state_size and hidden[] equal the learner's; with a memory in the file: replay_capacity
+ * equal, prioritized on both sides or on neither, alpha equal (the leaves are p^alpha).  minibatch and precision may differ (the
+ * master weights are fp32 either way); a loss-scale section is applied to a dynamic learner only, its multipliers must lie inside
+ * the learner's [loss_scale_min_mult, loss_scale_max_mult].  Then: the arenas are filled (the fp16 mirrors become dirty), the
+ * counters and flags restored, cfg.seed adopted (dqnhip_get_config reports the file's), logical transition i placed at physical
+ * slot (ring_head + i) % capacity, the tree restored to the saved learner's bits at every level (a prioritized learner also adopts
+ * the file's beta0, beta_anneal_iters, eps and sampler seed), captured graphs dropped.
+ *
+ * v1 refuses, in both calls: a learner in any sharing relationship (parameters or replay memory, either role), dp_world > 1 or a
+ * live communicator, a phased update in progress, kernel timing on.  Env front-end handles attached to a learner that loads see
+ * what they see after dqnhip_load_replay_memory: the ring changed under them, their open episodes continue on it. */
+#define DQNHIP_STATE_NO_MEMORY 1   /* neither the replay memory nor (head,size) nor the priority tree are written / touched on load */
+int dqnhip_save_state(dqnhip_handle h, const char* filename, int32_t flags,
+                      const void* user, size_t user_bytes);          /* user: an opaque caller section (may be NULL / 0) */
+int dqnhip_load_state(dqnhip_handle h, const char* filename);
+/* host only, needs no GPU */
+typedef struct dqnhip_state_info {
+  int32_t struct_size;       /* in: sizeof(dqnhip_state_info_t) */
+  int32_t version, flags, precision, minibatch, state_size, num_hidden, hidden[DQNHIP_MAX_HIDDEN], replay_capacity, memory_size,
+      actor_iter, critic_iter, has_memory, has_per, has_loss_scale;
+  uint64_t seed, update_counter, user_bytes, file_bytes;
+} dqnhip_state_info_t;       /* (the type carries _t: in C a typedef and a function cannot share a name) */
+/* Validates the whole file (every CRC) as dqnhip_load_state does, and reports the header. */
+int dqnhip_state_info(const char* filename, dqnhip_state_info_t* out);
+/* The caller's section: *n_out = its length (0: none); fails if it exceeds cap. */
+int dqnhip_state_read_user(const char* filename, void* buf, size_t cap, size_t* n_out);
 
 /* ---- batched env front-end (HFOGameState reward shaping, N workers) ----- */
 
