@@ -80,6 +80,51 @@ class StateInfo(C.Structure):
 
 STATE_NO_MEMORY = 1      # DQNHIP_STATE_NO_MEMORY
 
+DIAG_BINS = 64                                      # DQNHIP_DIAG_BINS
+DIAG_MAX_BLOBS = 2 * (2 * MAX_HIDDEN + 4)           # DQNHIP_DIAG_MAX_BLOBS
+DIAG_MAX_PANELS = 5 * MAX_HIDDEN                    # DQNHIP_DIAG_MAX_PANELS
+
+
+class DiagMoments(C.Structure):
+    """struct dqnhip_diag_moments (include/dqnhip.h)."""
+    _fields_ = [("count", C.c_int64), ("n_zero", C.c_int64), ("n_nonfinite", C.c_int64), ("sum_abs", C.c_double), ("sum_sq", C.c_double),
+                ("max_abs", C.c_float), ("reserved", C.c_float)]
+
+
+class DiagBlob(C.Structure):
+    """struct dqnhip_diag_blob (include/dqnhip.h)."""
+    _fields_ = [("net", C.c_int32), ("layer", C.c_int32), ("is_bias", C.c_int32), ("reserved", C.c_int32),
+                ("w", DiagMoments), ("g", DiagMoments), ("lag", DiagMoments), ("step", DiagMoments), ("g_hist", C.c_int32 * DIAG_BINS)]
+
+
+class DiagPanel(C.Structure):
+    """struct dqnhip_diag_panel (include/dqnhip.h)."""
+    _fields_ = [("pass_", C.c_int32), ("layer", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_negative", C.c_int64),
+                ("dead_units", C.c_int32), ("reserved", C.c_int32), ("a", DiagMoments), ("hist", C.c_int32 * DIAG_BINS)]
+
+
+class DiagRow(C.Structure):
+    """struct dqnhip_diag_row (include/dqnhip.h)."""
+    _fields_ = [("min", C.c_float), ("max", C.c_float), ("sum", C.c_double), ("sum_sq", C.c_double), ("n_nonfinite", C.c_int64)]
+
+
+class DiagAction(C.Structure):
+    """struct dqnhip_diag_action (include/dqnhip.h)."""
+    _fields_ = [("min", C.c_float), ("max", C.c_float), ("sum", C.c_double), ("n_out_of_bounds", C.c_int64)]
+
+
+class DiagReport(C.Structure):
+    """struct dqnhip_diag_report (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_blobs", C.c_int32), ("n_panels", C.c_int32), ("has_per", C.c_int32),
+                ("blobs", DiagBlob * DIAG_MAX_BLOBS), ("panels", DiagPanel * DIAG_MAX_PANELS),
+                ("q_target", DiagRow), ("y", DiagRow), ("q_train", DiagRow), ("q_policy", DiagRow), ("td", DiagRow),
+                ("n_terminal", C.c_int64), ("actor_out", DiagAction * 10),
+                ("dq_da_sum_abs", C.c_double), ("dq_da_max_abs", C.c_float), ("per_w_min", C.c_float), ("per_w_sum", C.c_double),
+                ("per_prob_min", C.c_float), ("per_td_abs_max", C.c_float), ("actor_iter", C.c_int32), ("critic_iter", C.c_int32),
+                ("critic_loss", C.c_float), ("avg_q", C.c_float), ("grad_norm", C.c_double * 2), ("clip_scale", C.c_double * 2),
+                ("fp16", C.c_int32), ("loss_scale_mode", C.c_int32), ("loss_scale_critic", C.c_float), ("loss_scale_dqda", C.c_float),
+                ("loss_scale_actor", C.c_float), ("mult_critic", C.c_float), ("mult_actor", C.c_float), ("reserved", C.c_int32)]
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int32)
 up = C.POINTER(C.c_uint8)
@@ -165,6 +210,7 @@ SIGNATURES = {
     "dqnhip_get_stream": (C.c_int, [H, C.POINTER(C.c_void_p)]),
     "dqnhip_set_kernel_timing": (C.c_int, [H, C.c_int32]),
     "dqnhip_get_kernel_timing": (C.c_int, [H, C.c_char_p, fp, C.POINTER(C.c_int64), C.c_int32]),
+    "dqnhip_diag_collect": (C.c_int, [H, C.POINTER(DiagReport)]),
     "dqnhip_per_default_config": (None, [C.POINTER(PerConfig)]),
     "dqnhip_per_enable": (C.c_int, [H, C.POINTER(PerConfig)]),
     "dqnhip_per_get_state": (C.c_int, [H, C.POINTER(PerState)]),

@@ -15,10 +15,13 @@
 #include <gflags/gflags.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <sstream>
+#include <string>
 
 namespace dqn {
 
@@ -49,6 +52,10 @@ DEFINE_bool(dynamic_loss_scale, false, "-precision fp16 only: the learner halves
                                        "finite (the step is skipped, nothing is reported) and doubles it after -loss_scale_growth_interval finite "
                                        "steps, on the device (dqnhip_config.loss_scale_mode). Off: the static scales; an overflow is fatal.");
 DEFINE_int32(loss_scale_growth_interval, 2000, "-dynamic_loss_scale: finite steps in a row before a multiplier doubles (0: never grow).");
+DEFINE_int32(debug_info_iter, 0, "Every this many critic iterations Update() logs the update diagnostics the device reduces from what that update left "
+             "(dqnhip_diag_collect; Caffe's debug_info of the reference's debug builds): gradient norms and clip scales, per-blob mean "
+             "|w| / |g| / |step| / |lag|, per-panel mean |a|, leaky fraction and dead units, Q / TD spreads, actor outputs out of bounds. "
+             "Every line starts \"[Agent<t>] [Diag]\". 0: off, nothing is collected and the log is what it was.");
 DEFINE_bool(prioritized_replay, false, "Proportional prioritized experience replay (Schaul et al. 2016) on the device: minibatches are drawn with "
             "probability p^alpha / sum from a sum tree over the replay memory, the critic's loss carries importance weights, |TD error| is "
             "written back. UpdateActorCritic() then draws nothing from the host engine. Not combinable with -deferred_updates, "
@@ -619,6 +626,7 @@ void DQN::Update() {
     const int c = critic_iter(), a = actor_iter();                             // this update's numbers
     const bool due = c % FLAGS_loss_display_iter == 0 || a % FLAGS_loss_display_iter == 0 ||
                      c >= last_snapshot_iter_ + FLAGS_snapshot_freq || a >= last_snapshot_iter_ + FLAGS_snapshot_freq ||
+                     (FLAGS_debug_info_iter > 0 && c % FLAGS_debug_info_iter == 0) ||      // (the diagnostics describe the last update run)
                      pend_n_ + uncollected_ >= kMaxUncollected;
     if (due) CollectDeferred();              // (the last replayed Bookkeep is this update's: it logs / snapshots)
     else if (pend_n_ == kSubmitEvery) SubmitPending();
@@ -626,6 +634,49 @@ void DQN::Update() {
   }
   const std::pair<float, float> res = UpdateActorCritic();
   Bookkeep(res, critic_iter(), actor_iter());
+}
+
+// -debug_info_iter: one dqnhip_diag_collect, logged (INTEGRATION.md lists the lines).  Means are sum_abs / count.
+static void LogDiagnostics(dqnhip_handle h, int tid) {
+  std::unique_ptr<dqnhip_diag_report> rp(new dqnhip_diag_report);
+  dqnhip_diag_report& r = *rp;
+  r.struct_size = (int32_t)sizeof r;
+  DQNHIP_CK(dqnhip_diag_collect(h, &r));
+  const int L = r.n_panels / 5;
+  auto mean = [](const dqnhip_diag_moments& m) { return m.count > 0 ? m.sum_abs / (double)m.count : 0.0; };
+  auto layer_name = [&](int net, int layer) -> std::string {
+    if (layer < L) return "ip" + std::to_string(layer + 1) + "_layer";
+    if (net == DQNHIP_CRITIC) return "q_values_layer";
+    return layer == L ? "action_layer" : "actionpara_layer";
+  };
+  static const char* const kPass[5] = {"actor_target(s')", "actor(s)", "critic_target(s',mu'(s'))", "critic(s,a)", "critic(s,mu(s))"};
+  const std::string p = "[Agent" + std::to_string(tid) + "] [Diag] ";
+  long long nonfinite = 0;
+  for (int b = 0; b < r.n_blobs; ++b) nonfinite += r.blobs[b].w.n_nonfinite + r.blobs[b].g.n_nonfinite;
+  LOG(INFO) << p << "iter " << r.critic_iter << ": grad_norm actor = " << r.grad_norm[0] << " (clip x" << r.clip_scale[0] << "), critic = "
+            << r.grad_norm[1] << " (clip x" << r.clip_scale[1] << "), non-finite w/g = " << nonfinite;
+  for (int b = 0; b < r.n_blobs; ++b) {
+    const dqnhip_diag_blob& x = r.blobs[b];
+    LOG(INFO) << p << "[Update] " << (x.net == DQNHIP_ACTOR ? "actor " : "critic ") << layer_name(x.net, x.layer) << (x.is_bias ? " bias" : " weight")
+              << ": |w| = " << mean(x.w) << ", |g| = " << mean(x.g) << ", |step| = " << mean(x.step) << ", |lag| = " << mean(x.lag);
+  }
+  for (int q = 0; q < r.n_panels; ++q) {
+    const dqnhip_diag_panel& x = r.panels[q];
+    LOG(INFO) << p << "[Forward] " << kPass[x.pass] << " ip" << x.layer << "_layer: |a| = " << mean(x.a) << ", leaky = "
+              << (x.a.count > 0 ? (double)x.n_negative / (double)x.a.count : 0.0) << ", dead = " << x.dead_units << " / " << x.cols;
+  }
+  const double B = r.panels[0].rows > 0 ? (double)r.panels[0].rows : 1.0;
+  auto row = [&](const dqnhip_diag_row& x) {
+    std::ostringstream s; s << "[" << x.min << ", " << x.max << "] mean " << x.sum / B; return s.str();
+  };
+  LOG(INFO) << p << "[Q] q_target " << row(r.q_target) << ", y " << row(r.y) << ", q_train " << row(r.q_train) << ", q_policy " << row(r.q_policy)
+            << ", td " << row(r.td) << " rms " << std::sqrt(r.td.sum_sq / B) << ", terminal = " << r.n_terminal << " / " << (long long)B
+            << ", non-finite = " << (r.q_target.n_nonfinite + r.y.n_nonfinite + r.q_train.n_nonfinite + r.q_policy.n_nonfinite);
+  std::ostringstream a;
+  long long oob = 0;
+  for (int j = 0; j < DQNHIP_ACTOR_OUT; ++j) { oob += r.actor_out[j].n_out_of_bounds; a << (j ? " " : "") << r.actor_out[j].sum / B; }
+  LOG(INFO) << p << "[Action] mean actor_out = " << a.str() << ", out of bounds = " << oob << " / " << (long long)(B * DQNHIP_ACTOR_OUT)
+            << ", |dq_da| = " << r.dq_da_sum_abs / (B * DQNHIP_ACTOR_OUT) << " (max " << r.dq_da_max_abs << ")";
 }
 
 // src/dqn.cpp:806-825 behind UpdateActorCritic(), on the iteration numbers that update left
@@ -646,6 +697,9 @@ void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_
     DQNHIP_CK(dqnhip_get_loss_scale(h_, &ls));
     LOG(INFO) << "[Agent" << tid_ << "] Loss scale: critic x" << ls.mult_critic << ", actor x" << ls.mult_actor << ", skipped steps = " << ls.skipped_steps;
   }
+  // -debug_info_iter: the diagnostics of this update (deferred updates: Update() made the collection due at this update, so the
+  // replayed Bookkeep that gets here is the last update's and the device still holds what it left)
+  if (FLAGS_debug_info_iter > 0 && critic_it % FLAGS_debug_info_iter == 0) LogDiagnostics(h_, tid_);
   if (critic_it >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_it >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
     snapshot_from_update_ = true;
     Snapshot();

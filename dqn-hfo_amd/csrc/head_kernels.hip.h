@@ -313,8 +313,7 @@ __global__ __launch_bounds__(1024) void k_head_bwd(HeadBwdArgs a) {
       d = a.dXc[(size_t)m * a.ldx + a.S + j];
       const float out = a.aout16[(size_t)m * kAP + j];
       float mn, mx;
-      if (j < kNA) { mn = -1.0f; mx = 1.0f; }
-      else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+      inverting_bounds(j, mn, mx);
       if (d < 0) d *= (mx - out) / (mx - mn);
       else if (d > 0) d *= (out - mn) / (mx - mn);
       if (blockIdx.x == 0) a.dA16[(size_t)m * kAP + j] = d;
@@ -481,8 +480,7 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
     const int r = tid / kNO, j = tid % kNO;
     float d = s_d[r][j];
     float mn, mx;
-    if (j < kNA) { mn = -1.0f; mx = 1.0f; }
-    else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+    inverting_bounds(j, mn, mx);
     if (d < 0) d *= (mx - out) / (mx - mn);
     else if (d > 0) d *= (out - mn) / (mx - mn);
     if (cc == 0) a.dA16[(size_t)(q0 + r) * kAP + j] = d;
@@ -618,8 +616,7 @@ __global__ __launch_bounds__(256) void k_head_bwd_big(HeadBwdBigArgs b) {
       d = a.dXc[(size_t)m * a.ldx + a.S + j];
       const float out = a.aout16[(size_t)m * kAP + j];
       float mn, mx;
-      if (j < kNA) { mn = -1.0f; mx = 1.0f; }
-      else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+      inverting_bounds(j, mn, mx);
       if (d < 0) d *= (mx - out) / (mx - mn);
       else if (d > 0) d *= (out - mn) / (mx - mn);
       if (blockIdx.y == 0) a.dA16[(size_t)m * kAP + j] = d;

@@ -5,8 +5,8 @@
 //               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
 //   bodies      gemm_bodies.hip.h, update_bodies.hip.h: __device__ functions only
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
-//               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), env.hip.h: __global__ functions and their
-//               launchers, grouped by the unit that launches them
+//               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), diag_kernels.hip.h (update diagnostics;
+//               learner_io.hip), env.hip.h: __global__ functions and their launchers, grouped by the unit that launches them
 // One include points upwards: head_fwd_kernels.hip.h holds the launcher head_forward<>, which takes the learner and reports through
 // HIPCHK, and so includes learner_internal.hip.h.
 #pragma once
@@ -21,6 +21,14 @@ constexpr int kNA = 4;    // kActionSize       src/dqn.hpp:20
 constexpr int kNP = 6;    // kActionParamSize  src/dqn.hpp:21
 constexpr int kNO = 10;   // ActorOutput       src/dqn.hpp:28
 constexpr int kAP = 16;   // padded ActorOutput row (64 B)
+
+// The bounds the inverting gradients push ActorOutput column j against (src/dqn.cpp:927-957): the four action logits in [-1, 1], the
+// two powers (parameters 0 and 4) in [0, 100], the four angles in [-180, 180].  One definition: the head-backward kernels
+// (head_kernels.hip.h) and the diagnostics' out-of-bounds counts (diag_kernels.hip.h) read it.
+__host__ __device__ __forceinline__ void inverting_bounds(int j, float& mn, float& mx) {
+  if (j < kNA) { mn = -1.0f; mx = 1.0f; }
+  else { const int p = j - kNA; if (p == 0 || p == 4) { mn = 0.0f; mx = 100.0f; } else { mn = -180.0f; mx = 180.0f; } }
+}
 
 // Device-resident scalars of one learner (graph-replayable: nothing that
 // changes per update is a kernel argument).

@@ -265,6 +265,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   drop_graphs(h);
   per_free(h);
+  diag_free(h);
   for (int i = 0; i < 2; ++i) {
     if (h->pipe_ev[i]) hipEventDestroy(h->pipe_ev[i]);
     if (h->pipe_idx_pinned[i]) hipHostFree(h->pipe_idx_pinned[i]);

@@ -9,7 +9,7 @@
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
-//                       introspection
+//                       introspection, update diagnostics (dqnhip_diag_collect)
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state; host only
 //   snapshot.cpp        Caffe snapshot layout (no device code)
@@ -130,6 +130,7 @@ struct PerHost {
   long long pending = 0; bool changed = false;
   long long syncs = 0;                  // k_per_sync launches so far
 };
+struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
 
 }  // namespace dqnhip_host
 
@@ -277,6 +278,7 @@ struct dqnhip_learner {
   int ix_prev_flags = 0;                // the sticky device flags as the last harvested update left them (a raise = a bit not in here)
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
+  DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
 };
 
 namespace dqnhip_host {
@@ -424,5 +426,6 @@ void per_free(H* h);
 int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behind everything enqueued so far
 int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
 int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
+void diag_free(H* h);                                    // dqnhip_diag_collect's scratch
 
 }  // namespace dqnhip_host

@@ -1,9 +1,10 @@
 // learner_io.hip — everything of the C-ABI around the update: acting (SelectActions / CriticForward), the replay memory and
-// its .replaymemory files, parameter access, multi-agent sharing, introspection (include/dqnhip.h).
+// its .replaymemory files, parameter access, multi-agent sharing, introspection, update diagnostics (include/dqnhip.h).
 #include "learner_internal.hip.h"
 #include "head_fwd_kernels.hip.h"
 #include "io_kernels.hip.h"
 #include "per_kernels.hip.h"
+#include "diag_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;
@@ -919,6 +920,154 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   if (pad16) { for (size_t r = 0; r < B; ++r) for (int c = 0; c < kNO; ++c) host[r * kNO + c] = tmp[r * kAP + c]; }
   else if (is_int) { for (size_t r = 0; r < B; ++r) host[r] = (float)reinterpret_cast<const int*>(tmp.data())[r]; }
   else memcpy(host, tmp.data(), B * sizeof(float));
+  return 0;
+}
+
+// ---- update diagnostics (include/dqnhip.h has the definitions; the kernels and the order of every sum: diag_kernels.hip.h) ---------
+
+}  // extern "C"
+namespace dqnhip_host {
+
+struct DiagHost {
+  std::vector<DiagSeg> segs;            // blobs (actor's, then critic's, dense Caffe order), then panels (pass-major)
+  int n_blobs = 0, n_panels = 0, n_items = 0;
+  DiagSeg* segs_dev = nullptr; DiagItem* items_dev = nullptr;
+  DiagPart* parts = nullptr; DiagPart* out = nullptr; DiagRows* rows = nullptr;
+  std::vector<int> blob_layer, blob_bias;
+};
+void diag_free(H* h) {
+  DiagHost* d = h->diag;
+  if (!d) return;
+  hipFree(d->segs_dev); hipFree(d->items_dev); hipFree(d->parts); hipFree(d->out); hipFree(d->rows);
+  delete d;
+  h->diag = nullptr;
+}
+// the work table: one segment per blob and per panel, one item per (segment, chunk), the rows items first (they are the longest)
+static int diag_build(H* h) {
+  DiagHost* d = new DiagHost();
+  h->diag = d;                          // (from here on diag_free releases whatever was allocated)
+  std::vector<DiagItem> items;
+  for (int r = 0; r < kDiagRowItems; ++r) items.push_back(DiagItem{-1, r});
+  auto add = [&](DiagSeg s, int n_items) {
+    s.first_item = d->n_items; s.n_items = n_items;
+    for (int c = 0; c < n_items; ++c) items.push_back(DiagItem{(int)d->segs.size(), c});
+    d->segs.push_back(s); d->n_items += n_items;
+  };
+  for (int net = 0; net < 2; ++net) {
+    const NetLayout& l = layout_of(h, net);
+    auto blob = [&](size_t off, int rows, int cols, int pitch, int layer, int is_bias) {
+      DiagSeg s{};
+      s.w = h->w[net] + off; s.wt = h->w[net + 2] + off; s.g = h->g[net] + off; s.m = h->m[net] + off; s.v = h->v[net] + off;
+      s.type = DIAG_BLOB; s.net = net; s.rows = rows; s.cols = cols; s.pitch = pitch;
+      add(s, (int)(((size_t)rows * pitch + kDiagChunk - 1) / kDiagChunk));
+      d->blob_layer.push_back(layer); d->blob_bias.push_back(is_bias);
+    };
+    for (int i = 0; i < l.L; ++i) {
+      blob(l.w_off[i], l.dims[i + 1], l.dims[i], l.kp[i], i, 0);
+      blob(l.b_off[i], 1, l.dims[i + 1], l.dims[i + 1], i, 1);
+    }
+    const int Hh = l.dims[l.L];
+    if (l.NH == kNO) {
+      blob(l.hw_off, kNA, Hh, Hh, l.L, 0); blob(l.hb_off, 1, kNA, kNA, l.L, 1);
+      blob(l.hw_off + (size_t)kNA * Hh, kNP, Hh, Hh, l.L + 1, 0); blob(l.hb_off + kNA, 1, kNP, kNP, l.L + 1, 1);
+    } else { blob(l.hw_off, 1, Hh, Hh, l.L, 0); blob(l.hb_off, 1, 1, 1, l.L, 1); }
+  }
+  d->n_blobs = (int)d->segs.size();
+  for (int p = 0; p < 5; ++p)
+    for (int i = 1; i <= h->L; ++i) {
+      const NetLayout& l = layout_of(h, p >= 2);
+      DiagSeg s{};
+      s.type = DIAG_PANEL; s.net = p; s.is16 = h->fp16 ? 1 : 0; s.rows = h->B; s.cols = l.dims[i];
+      s.panel = h->fp16 ? (const void*)h->act16[p][i] : (const void*)h->act[p][i];
+      s.pitch = h->fp16 ? h->k16[p >= 2][i] : l.kp[i];
+      const int strip = h->fp16 ? 128 : 64;
+      if (s.cols % strip) return fail("diagnostics: panel width %d is not a multiple of %d", s.cols, strip);
+      add(s, s.cols / strip);
+    }
+  d->n_panels = 5 * h->L;
+  auto alloc = [&](void** p, size_t bytes) -> int { HIPCHK(hipMalloc(p, bytes)); HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream)); return 0; };
+  RC(alloc((void**)&d->segs_dev, d->segs.size() * sizeof(DiagSeg)));
+  RC(alloc((void**)&d->items_dev, items.size() * sizeof(DiagItem)));
+  RC(alloc((void**)&d->parts, (size_t)d->n_items * sizeof(DiagPart)));
+  RC(alloc((void**)&d->out, d->segs.size() * sizeof(DiagPart)));
+  RC(alloc((void**)&d->rows, sizeof(DiagRows)));
+  HIPCHK(hipMemcpyAsync(d->segs_dev, d->segs.data(), d->segs.size() * sizeof(DiagSeg), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(d->items_dev, items.data(), items.size() * sizeof(DiagItem), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));       // (items is on this stack)
+  return 0;
+}
+static void diag_moments(dqnhip_diag_moments& o, const DiagMomPart& p, int64_t count) {
+  o.count = count; o.n_zero = p.n_zero; o.n_nonfinite = p.n_nonfinite; o.sum_abs = p.sum_abs; o.sum_sq = p.sum_sq; o.max_abs = p.max_abs; o.reserved = 0.0f;
+}
+
+}  // namespace dqnhip_host
+extern "C" {
+
+int dqnhip_diag_collect(dqnhip_handle h, dqnhip_diag_report* out) {
+  if (!out) return fail("dqnhip_diag_collect: null report");
+  if (out->struct_size != (int32_t)sizeof(dqnhip_diag_report)) return fail("dqnhip_diag_report.struct_size %d != %zu (ABI mismatch)", out->struct_size, sizeof(dqnhip_diag_report));
+  if (!h) return fail("dqnhip_diag_collect: null handle");
+  if (h->next_phase != 0) return fail("dqnhip_diag_collect: diagnostics describe a finished update, and a phased update is in progress (next phase %d)", h->next_phase);
+  if (h->w_owner) return fail("dqnhip_diag_collect: diagnostics are not available on a learner that reads another learner's parameters "
+                              "(dqnhip_share_parameters: the arenas it steps are not all its own); collect on the owner");
+  if (h->dp_shard) return fail("dqnhip_diag_collect: diagnostics are not available with a sharded optimiser (DQNHIP_DP_SHARD_OPT: m and v of foreign slices are stale)");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!h->diag && diag_build(h)) { diag_free(h); return 1; }
+  DiagHost* d = h->diag;
+  const dqnhip_config& c = h->cfg;
+  DiagPrepArgs pa{h->st, d->rows, {c.actor_lr, c.critic_lr}, c.momentum, c.momentum2};
+  HIPCHK(launch(h->stream, k_diag_prep, dim3(1), dim3(64), 0, pa));
+  DiagArgs a{};
+  a.segs = d->segs_dev; a.items = d->items_dev; a.parts = d->parts; a.rows = d->rows; a.B = h->B; a.delta = c.delta;
+  a.q_t = h->q_t; a.y = h->y; a.q1 = h->q1; a.q2 = h->q2; a.term = h->mb_term; a.aout16 = h->aout16; a.dA16 = h->dA16;
+  if (h->per) { a.per_w = h->per->w; a.per_prob = h->per->prob; a.per_td = h->per->td_abs; }
+  HIPCHK(launch(h->stream, k_diag_reduce, dim3(kDiagRowItems + d->n_items), dim3(256), 0, a));
+  HIPCHK(launch(h->stream, k_diag_final, dim3((unsigned)d->segs.size()), dim3(256), 0, (const DiagSeg*)d->segs_dev, (const DiagPart*)d->parts, d->out));
+  std::vector<DiagPart> res(d->segs.size());
+  DiagRows rows{}; DevState s{};
+  HIPCHK(hipMemcpyAsync(res.data(), d->out, res.size() * sizeof(DiagPart), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&rows, d->rows, sizeof rows, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&s, h->st, sizeof s, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+
+  memset(out, 0, sizeof *out);
+  out->struct_size = (int32_t)sizeof *out;
+  out->n_blobs = d->n_blobs; out->n_panels = d->n_panels; out->has_per = h->per ? 1 : 0;
+  double sumsq[2] = {0.0, 0.0};
+  for (int b = 0; b < d->n_blobs; ++b) {
+    const DiagSeg& sg = d->segs[b]; const DiagPart& p = res[b];
+    dqnhip_diag_blob& o = out->blobs[b];
+    o.net = sg.net; o.layer = d->blob_layer[b]; o.is_bias = d->blob_bias[b];
+    const int64_t count = (int64_t)sg.rows * sg.cols;
+    diag_moments(o.w, p.mom[0], count); diag_moments(o.g, p.mom[1], count); diag_moments(o.lag, p.mom[2], count); diag_moments(o.step, p.mom[3], count);
+    memcpy(o.g_hist, p.hist, sizeof o.g_hist);
+    sumsq[sg.net] += p.mom[1].sum_sq;
+  }
+  for (int q = 0; q < d->n_panels; ++q) {
+    const DiagSeg& sg = d->segs[d->n_blobs + q]; const DiagPart& p = res[d->n_blobs + q];
+    dqnhip_diag_panel& o = out->panels[q];
+    o.pass = sg.net; o.layer = q % h->L + 1; o.rows = sg.rows; o.cols = sg.cols;
+    o.n_negative = p.n_negative; o.dead_units = p.dead;
+    diag_moments(o.a, p.mom[0], (int64_t)sg.rows * sg.cols);
+    memcpy(o.hist, p.hist, sizeof o.hist);
+  }
+  dqnhip_diag_row* rr[5] = {&out->q_target, &out->y, &out->q_train, &out->q_policy, &out->td};
+  for (int i = 0; i < 5; ++i) { rr[i]->min = rows.row[i].mn; rr[i]->max = rows.row[i].mx; rr[i]->sum = rows.row[i].sum; rr[i]->sum_sq = rows.row[i].sum_sq; rr[i]->n_nonfinite = rows.row[i].n_nonfinite; }
+  out->n_terminal = rows.n_terminal;
+  for (int j = 0; j < kNO; ++j) { out->actor_out[j].min = rows.act[j].mn; out->actor_out[j].max = rows.act[j].mx; out->actor_out[j].sum = rows.act[j].sum; out->actor_out[j].n_out_of_bounds = rows.act[j].n_oob; }
+  out->dq_da_sum_abs = rows.dqda_sum_abs; out->dq_da_max_abs = rows.dqda_max_abs;
+  out->per_w_min = rows.per_w_min; out->per_w_sum = rows.per_w_sum; out->per_prob_min = rows.per_prob_min; out->per_td_abs_max = rows.per_td_abs_max;
+  out->actor_iter = s.actor_iter; out->critic_iter = s.critic_iter; out->critic_loss = s.critic_loss; out->avg_q = s.avg_q;
+  for (int net = 0; net < 2; ++net) {
+    const double norm = std::sqrt(sumsq[net]), clip = (double)c.clip_gradients;
+    out->grad_norm[net] = norm;
+    out->clip_scale[net] = (c.clip_gradients >= 0.0f && norm > clip) ? clip / norm : 1.0;
+  }
+  if (h->fp16) {
+    out->fp16 = 1; out->loss_scale_mode = c.loss_scale_mode;
+    out->loss_scale_critic = h->ls_c; out->loss_scale_dqda = h->ls_q; out->loss_scale_actor = h->ls_a;
+    out->mult_critic = h->ls_dynamic ? s.ls_mult[1][0] : 1.0f; out->mult_actor = h->ls_dynamic ? s.ls_mult[0][0] : 1.0f;
+  }
   return 0;
 }
 

@@ -647,6 +647,57 @@ class DQN:
                 "launches_graph_first": p.launches_graph_first, "launches_in_graph": p.launches_in_graph,
                 "updates_per_graph": p.updates_per_graph, "collectives": p.collectives}
 
+    # -- update diagnostics (include/dqnhip.h: Caffe's debug_info, reduced on the device; opt-in) --------------
+    def diag_collect_raw(self):
+        """dqnhip_diag_collect -> the ctypes report (capi.DiagReport)."""
+        r = capi.DiagReport()
+        r.struct_size = C.sizeof(capi.DiagReport)
+        self._ck(self.lib.dqnhip_diag_collect(self.h, C.byref(r)))
+        return r
+
+    def diagnostics(self):
+        """What the last update left on the device, as a plain dict (include/dqnhip.h has every definition):
+        blobs   one dict per parameter blob in the dense Caffe order of get_params (actor, then critic): net, layer (the Caffe layer
+                name), is_bias, count and the moments w / g / lag / step (dicts: count, n_zero, n_nonfinite, sum_abs, sum_sq,
+                max_abs), g_hist (int32[64])
+        panels  one dict per stored activation panel: pass, layer (1 .. L), rows, cols, the moments a, hist, n_negative, dead_units
+        rows    q_target, y, q_train, q_policy, td (min, max, sum, sum_sq, n_nonfinite), n_terminal, actor_out (10 dicts), dq_da and,
+                on a prioritized learner, per
+        and the scalars: actor_iter, critic_iter, critic_loss, avg_q, grad_norm / clip_scale (by net), loss_scale (fp16 learner)."""
+        r = self.diag_collect_raw()
+        L = self.cfg.num_hidden
+
+        def mom(m):
+            return {"count": m.count, "n_zero": m.n_zero, "n_nonfinite": m.n_nonfinite, "sum_abs": m.sum_abs, "sum_sq": m.sum_sq,
+                    "max_abs": m.max_abs}
+
+        def name(b):
+            if b.layer < L:
+                return "ip%d_layer" % (b.layer + 1)
+            if b.net == CRITIC:
+                return "q_values_layer"
+            return "action_layer" if b.layer == L else "actionpara_layer"
+
+        blobs = [{"net": b.net, "layer": name(b), "is_bias": bool(b.is_bias), "count": b.w.count, "w": mom(b.w), "g": mom(b.g),
+                  "lag": mom(b.lag), "step": mom(b.step), "g_hist": np.array(b.g_hist, np.int32)} for b in r.blobs[:r.n_blobs]]
+        panels = [{"pass": p.pass_, "layer": p.layer, "rows": p.rows, "cols": p.cols, "a": mom(p.a), "hist": np.array(p.hist, np.int32),
+                   "n_negative": p.n_negative, "dead_units": p.dead_units} for p in r.panels[:r.n_panels]]
+        rows = {k: {"min": v.min, "max": v.max, "sum": v.sum, "sum_sq": v.sum_sq, "n_nonfinite": v.n_nonfinite}
+                for k, v in (("q_target", r.q_target), ("y", r.y), ("q_train", r.q_train), ("q_policy", r.q_policy), ("td", r.td))}
+        rows["n_terminal"] = r.n_terminal
+        rows["actor_out"] = [{"min": a.min, "max": a.max, "sum": a.sum, "n_out_of_bounds": a.n_out_of_bounds} for a in r.actor_out]
+        rows["dq_da"] = {"sum_abs": r.dq_da_sum_abs, "max_abs": r.dq_da_max_abs}
+        rows["per"] = ({"w_min": r.per_w_min, "w_sum": r.per_w_sum, "prob_min": r.per_prob_min, "td_abs_max": r.per_td_abs_max}
+                       if r.has_per else None)
+        out = {"blobs": blobs, "panels": panels, "rows": rows, "has_per": bool(r.has_per), "actor_iter": r.actor_iter,
+               "critic_iter": r.critic_iter, "critic_loss": r.critic_loss, "avg_q": r.avg_q,
+               "grad_norm": {ACTOR: r.grad_norm[0], CRITIC: r.grad_norm[1]}, "clip_scale": {ACTOR: r.clip_scale[0], CRITIC: r.clip_scale[1]},
+               "loss_scale": None}
+        if r.fp16:
+            out["loss_scale"] = {"mode": r.loss_scale_mode, "critic": r.loss_scale_critic, "dqda": r.loss_scale_dqda,
+                                 "actor": r.loss_scale_actor, "mult_critic": r.mult_critic, "mult_actor": r.mult_actor}
+        return out
+
     # -- prioritized replay (include/dqnhip.h: no reference counterpart, off unless enabled) -----------------
     def enable_prioritized_replay(self, alpha=None, beta0=None, beta_anneal_iters=None, eps=None, seed=None):
         """dqnhip_per_enable.  Arguments left None keep dqnhip_per_default_config's values: the customary ones of Schaul et al.

@@ -641,6 +641,90 @@ int dqnhip_set_kernel_timing(dqnhip_handle h, int32_t enable);
 int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
                              int64_t* launches, int32_t reset);
 
+/* ---- update diagnostics (opt-in) ----------------------------------------------------------------------------------------
+ * Replaces what Caffe's debug_info prints in the reference's debug builds (DQN::Initialize / CloneNet switch it on,
+ * src/dqn.cpp:623-626, 632-635, 1027-1029): the magnitude of every top blob after a forward, of every parameter gradient after a
+ * backward, of every parameter's data and update after the solver step.  ONE call reduces what the last update left on the
+ * device — exactly the buffers dqnhip_get_params / dqnhip_debug_read / dqnhip_per_debug_read would return at that moment, whatever
+ * update form ran last — to this fixed-size report, in three launches on the learner's stream (csrc/diag_kernels.hip.h: a
+ * streaming pass over w, w', g, m, v of both online nets, the 5 x L activation panels and the [B] rows).  A learner that never
+ * makes the call launches what it launched before the call existed; the call reads, and writes nothing but its own scratch
+ * (allocated on first use, freed by dqnhip_destroy).  Stream-ordered, blocks.  Non-finite content is counted, never an error.
+ * Every floating-point sum is a double accumulated in one fixed order (no floating-point atomics): two collections with nothing in
+ * between return byte-identical reports.
+ *
+ * Moments of a set of elements x: count; n_zero (+-0); n_nonfinite (NaN, +-Inf); over the FINITE elements sum_abs = sum |x| and
+ * sum_sq = sum x^2 in double (a float's square is exact in double) and max_abs (float; 0 when no element is finite).
+ * Exponent histogram (64 bins) of the finite non-zero elements: e = the biased exponent field of the float32 bits (denormals:
+ * e = 0), bin = min(max(e - 87, 0), 63) — bin k in 1..62 holds 2^(k-40) <= |x| < 2^(k-39), bin 0 everything below 2^-39, bin 63
+ * everything from 2^23 up; sum of bins + n_zero + n_nonfinite = count.  Pad words of the internal layout are counted nowhere.
+ *
+ * Blobs: dense Caffe order of dqnhip_get_params — the actor's ip1 .. ipL, action_layer, actionpara_layer (2L + 4 blobs), then the
+ * critic's ip1 .. ipL, q_values_layer (2L + 2), weight before bias.  `layer` = 0 .. L-1 for the tower, L (and L + 1: actionpara_layer)
+ * for the heads.  Per blob: moments of w; of g as stored (DQNHIP_KIND_G: unscaled on every learner) with its histogram; of
+ * lag = (double)w - (double)w' against the net's target (exact differences; max_abs rounded to float); of
+ * step = s * (m / (sqrtf(v) + delta)) in float32, s = lr * adam_correction(beta1, beta2, t), t the net's iteration as it stands — the
+ * value the last optimiser step subtracted from w, recomputed from the m, v it stored (Caffe's "[Update] .. diff"); 0 everywhere
+ * while the iteration is 0.  After a SKIPPED step (non-finite gradient norm) it is the step the stored history implies, not one
+ * that was taken.
+ * Panels: pass p = 0 actor_target(s'), 1 actor(s), 2 critic_target, 3 critic(s, a), 4 critic(s, mu(s)), layer i = 1 .. L, the
+ * stored post-ReLU values ("act<p>_<i>"; fp16 learner: each half widened exactly): moments, histogram, n_negative (elements < 0:
+ * on the leaky branch), dead_units (columns < 0 in every row).
+ * Rows: q_target, y, q_train, q_policy, td = q_train - y (float subtraction): min / max / sum / sum_sq over the finite elements
+ * (min = max = 0 when none is), n_nonfinite; n_terminal; per actor-output column min / max / sum over the finite values and
+ * n_out_of_bounds = values outside the inverting gradients' bounds ([-1, 1] for the 4 actions, [0, 100] for parameters 0 and 4,
+ * [-180, 180] for the angles; src/dqn.cpp:927-957; a NaN is outside); sum_abs / max_abs of the finite dq_da.  Prioritized learner
+ * (has_per): min / sum of the importance weights, min of prob, max of td_abs, over the finite values; else 0.
+ * grad_norm[net] = sqrt(sum over the net's blobs of g.sum_sq), clip_scale[net] = clip_gradients >= 0 && norm > clip ? clip / norm : 1
+ * (double, formed on the host from the report).  net index: DQNHIP_ACTOR, DQNHIP_CRITIC.
+ *
+ * v1 refuses: a phased update in progress; a learner that reads another learner's parameters (dqnhip_share_parameters: the arenas
+ * it steps are not all its own — the owner is fine); a DQNHIP_DP_SHARD_OPT learner (m, v of foreign slices are stale). */
+typedef struct dqnhip_diag_moments {
+  int64_t count, n_zero, n_nonfinite;
+  double sum_abs, sum_sq;
+  float max_abs, reserved;
+} dqnhip_diag_moments;
+#define DQNHIP_DIAG_BINS 64
+typedef struct dqnhip_diag_blob {
+  int32_t net, layer, is_bias, reserved;
+  dqnhip_diag_moments w, g, lag, step;
+  int32_t g_hist[DQNHIP_DIAG_BINS];
+} dqnhip_diag_blob;
+typedef struct dqnhip_diag_panel {
+  int32_t pass, layer, rows, cols;
+  int64_t n_negative;
+  int32_t dead_units, reserved;
+  dqnhip_diag_moments a;
+  int32_t hist[DQNHIP_DIAG_BINS];
+} dqnhip_diag_panel;
+typedef struct dqnhip_diag_row { float min, max; double sum, sum_sq; int64_t n_nonfinite; } dqnhip_diag_row;
+typedef struct dqnhip_diag_action { float min, max; double sum; int64_t n_out_of_bounds; } dqnhip_diag_action;
+#define DQNHIP_DIAG_MAX_BLOBS (2 * (2 * DQNHIP_MAX_HIDDEN + 4))
+#define DQNHIP_DIAG_MAX_PANELS (5 * DQNHIP_MAX_HIDDEN)
+typedef struct dqnhip_diag_report {
+  int32_t struct_size;       /* in: sizeof(dqnhip_diag_report) */
+  int32_t n_blobs, n_panels, has_per;
+  dqnhip_diag_blob blobs[DQNHIP_DIAG_MAX_BLOBS];
+  dqnhip_diag_panel panels[DQNHIP_DIAG_MAX_PANELS];     /* pass-major: panel (p, i) at p * L + i - 1 */
+  dqnhip_diag_row q_target, y, q_train, q_policy, td;
+  int64_t n_terminal;
+  dqnhip_diag_action actor_out[DQNHIP_ACTOR_OUT];
+  double dq_da_sum_abs;
+  float dq_da_max_abs;
+  float per_w_min;
+  double per_w_sum;
+  float per_prob_min, per_td_abs_max;
+  int32_t actor_iter, critic_iter;
+  float critic_loss, avg_q;                             /* the last update's pair, as dqnhip_read_stats returns it (no flag is read or cleared) */
+  double grad_norm[2], clip_scale[2];
+  int32_t fp16, loss_scale_mode;                        /* fp16 learner: the scales the histograms are read against, else 0 */
+  float loss_scale_critic, loss_scale_dqda, loss_scale_actor;    /* the three static scales */
+  float mult_critic, mult_actor;                        /* the live multipliers (1 in static mode) */
+  int32_t reserved;
+} dqnhip_diag_report;
+int dqnhip_diag_collect(dqnhip_handle h, dqnhip_diag_report* out);
+
 /* ---- data parallelism: exchange forms that are NOT part of the supported surface -----------------------------------------
  * Built in rounds 3-4, priced net-negative by this library's own model and never run on more than one rank (no box
  * with more than one GPU has been available): dqnhip_dp_init refuses them for dp_world > 1 unless DQNHIP_DP_UNVERIFIED_OK says the
