@@ -222,6 +222,10 @@ SIGNATURES = {
     "dqnhip_load_state": (C.c_int, [H, C.c_char_p]),
     "dqnhip_state_info": (C.c_int, [C.c_char_p, C.POINTER(StateInfo)]),
     "dqnhip_state_read_user": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dqnhip_save_state_async": (C.c_int, [H, C.c_char_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "dqnhip_save_state_wait": (C.c_int, [H]),
+    "dqnhip_save_state_poll": (C.c_int, [H, C.POINTER(C.c_int32)]),
+    "dqnhip_state_crc32_device": (C.c_int, [H, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint32)]),
 }
 
 class EnvConfig(C.Structure):

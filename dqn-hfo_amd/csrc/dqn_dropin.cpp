@@ -67,6 +67,11 @@ DEFINE_bool(native_state, false, "Snapshot() additionally writes <prefix>_iter_<
             "state, the ring's position, priorities, this object's random_engine and smoothed sums), and RestoreCriticSolver() loads the one "
             "that belongs to the restored iterations: resume is then bit-identical to never having stopped. The reference's files are "
             "written and read as without the flag.");
+DEFINE_bool(native_state_async, false, "-native_state: the learner state is written behind training (dqnhip_save_state_async: frozen on the device at the "
+            "snapshot, written by a writer thread). The save is joined - and older .learnerstate files removed - at the next learner-state "
+            "snapshot, at a restore and when the learner is destroyed; a failed save aborts there. Same file, byte for byte.");
+DEFINE_bool(native_state_only_memory, false, "-native_state: a snapshot that is asked for the replay memory writes no gzip .replaymemory; the learner-state "
+            "file is the memory's only copy and restores it on resume.");
 DEFINE_bool(device_sampling, false, "Sample minibatch indices on the device (counter-based) instead of the host std::mt19937.");
 DEFINE_bool(chained_updates, true, "UpdateActorCritic() tells the library which indices the NEXT call will draw (a copy of the engine runs ahead; "
             "dqnhip_update_chained): bursts of Update() get the launch schedule of a multi-update graph.  Same results, same RNG order.");
@@ -282,6 +287,8 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   c.device = FLAGS_hip_device + tid * FLAGS_hip_agent_device_stride;
   c.use_graph = FLAGS_hip_graph ? 1 : 0;
   c.seed = seed;
+  CHECK(!FLAGS_native_state_async || FLAGS_native_state) << "-native_state_async needs -native_state (it changes how the learner-state file is written)";
+  CHECK(!FLAGS_native_state_only_memory || FLAGS_native_state) << "-native_state_only_memory needs -native_state (the learner-state file is then the memory's only copy)";
   CHECK(FLAGS_precision == "fp32" || FLAGS_precision == "fp16") << "-precision must be fp32 or fp16";
   c.precision = FLAGS_precision == "fp16" ? DQNHIP_FP16 : DQNHIP_FP32;
   CHECK(FLAGS_act_precision == "fp32" || FLAGS_act_precision == "fp16") << "-act_precision must be fp32 or fp16";
@@ -357,7 +364,7 @@ void DQN::RearmReplicaSync(const char* what) {
   dp_sync_pending_ = true;
 }
 
-DQN::~DQN() { CollectDeferred(); DQNHIP_CK(dqnhip_destroy(h_)); }
+DQN::~DQN() { CollectDeferred(); JoinNativeState(); DQNHIP_CK(dqnhip_destroy(h_)); }
 
 // ---- -deferred_updates ------------------------------------------------------------------------------------------------------
 // The driver calls Update() in bursts and discards the result (src/dqn_main.cpp:340-343, 359-361; Update() is void, src/dqn.hpp:103):
@@ -452,8 +459,10 @@ void DQN::SnapshotReplayMemory(const std::string& f) { SubmitPending(); DQNHIP_C
 void DQN::Snapshot() { Snapshot(save_path_, FLAGS_remove_old_snapshots, FLAGS_snapshot_memory); }
 void DQN::Snapshot(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory) {
   SubmitPending();
-  if (snapshot_memory) LOG(INFO) << "Snapshotting memory to " << snapshot_prefix << "_iter_" << max_iter() << ".replaymemory";
-  DQNHIP_CK(dqnhip_snapshot(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, snapshot_memory));
+  // -native_state_only_memory: the learner-state file below carries the memory (a data-parallel learner writes none: it keeps the gzip file)
+  const bool gzip_memory = snapshot_memory && !(FLAGS_native_state_only_memory && !dp_);
+  if (gzip_memory) LOG(INFO) << "Snapshotting memory to " << snapshot_prefix << "_iter_" << max_iter() << ".replaymemory";
+  DQNHIP_CK(dqnhip_snapshot(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, gzip_memory));
   if (FLAGS_native_state) SaveNativeState(snapshot_prefix, remove_old, snapshot_memory);
   LOG(INFO) << "Snapshotting Finished!";
 }
@@ -474,13 +483,32 @@ void DQN::SaveNativeState(const std::string& snapshot_prefix, bool remove_old, b
   user << "dqn_dropin_state 1\n" << random_engine << "\n" << bits[0] << " " << bits[1] << "\n"
        << (snapshot_from_update_ ? max_iter() : last_snapshot_iter_) << "\n";
   const std::string u = user.str();
+  const std::string older = snapshot_prefix + "_iter_[0-9]+\\.learnerstate";
+  if (FLAGS_native_state_async) {
+    // the previous save is joined first; this one's older files go when IT is joined: a process killed while the writer runs still
+    // leaves the previous complete file
+    JoinNativeState();
+    DQNHIP_CK(dqnhip_save_state_async(h_, f.c_str(), snapshot_memory ? 0 : DQNHIP_STATE_NO_MEMORY, u.data(), u.size()));
+    native_in_flight_ = true;
+    native_remove_ = remove_old ? older : std::string(); native_remove_below_ = critic_iter() - 1;
+    return;
+  }
   DQNHIP_CK(dqnhip_save_state(h_, f.c_str(), snapshot_memory ? 0 : DQNHIP_STATE_NO_MEMORY, u.data(), u.size()));
-  if (remove_old) RemoveSnapshots(snapshot_prefix + "_iter_[0-9]+\\.learnerstate", critic_iter() - 1);      // the .replaymemory files' rule (src/dqn.cpp:612-618)
+  if (remove_old) RemoveSnapshots(older, critic_iter() - 1);      // the .replaymemory files' rule (src/dqn.cpp:612-618)
+}
+
+// -native_state_async: waits for the save in flight (a failure aborts, as a failed synchronous save does) and removes the files it superseded
+void DQN::JoinNativeState() {
+  if (!native_in_flight_) return;
+  native_in_flight_ = false;
+  DQNHIP_CK(dqnhip_save_state_wait(h_));
+  if (!native_remove_.empty()) RemoveSnapshots(native_remove_, native_remove_below_);
 }
 
 // f: <stem>_critic_iter_<N>.solverstate, just restored.  The learner state of the same snapshot is <stem>_iter_<max_iter()>.learnerstate
 // and says which iterations it was taken at: only a file of exactly the restored pair is loaded.
 void DQN::LoadNativeState(const std::string& f) {
+  JoinNativeState();
   const size_t pos = f.rfind("_critic_iter_");
   if (pos == std::string::npos) return;
   const std::string stem = f.substr(0, pos), file = stem + "_iter_" + std::to_string(max_iter()) + ".learnerstate";

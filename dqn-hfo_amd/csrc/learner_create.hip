@@ -260,6 +260,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   if (h->ring_owner) h->ring_owner->sharers -= 1;
   if (h->ring_ev) hipEventDestroy(h->ring_ev);
   hipSetDevice(h->cfg.device);
+  state_async_free(h);                  // (a save in flight finishes its file first)
   dp_destroy_impl(h, false);
   hipStreamSynchronize(h->stream);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }

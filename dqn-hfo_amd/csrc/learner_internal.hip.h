@@ -9,9 +9,10 @@
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
-//                       introspection, update diagnostics (dqnhip_diag_collect)
+//                       introspection, update diagnostics (dqnhip_diag_collect), the launches of the asynchronous state save
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
-//   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state; host only
+//   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state, and the host side of
+//                       dqnhip_save_state_async (its writer thread; the kernels are launched from learner_io.hip); host only
 //   snapshot.cpp        Caffe snapshot layout (no device code)
 //   state_codec.cpp     the learner-state file's container (header, table, CRCs), dqnhip_state_info / _read_user (no device code, no HIP)
 // This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
@@ -45,6 +46,7 @@
 #include "learner_args.hip.h"
 #include "gemm_plan.hip.h"        // the fp32 forms and their choosers (bwd_layer_is_pair)
 #include "hgemm_plan.hip.h"
+#include "state_image.h"        // plain structures of the asynchronous state save
 
 namespace dqnhip_host {
 using namespace dqnhip;
@@ -131,6 +133,7 @@ struct PerHost {
   long long syncs = 0;                  // k_per_sync launches so far
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
+struct StateAsync;                      // asynchronous learner-state save (learner_state.hip; the kernels: state_kernels.hip.h)
 
 }  // namespace dqnhip_host
 
@@ -279,6 +282,7 @@ struct dqnhip_learner {
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
   DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
+  StateAsync* sasync = nullptr;         // dqnhip_save_state_async: staging buffer, pinned ring, writer thread; allocated by the first such save
 };
 
 namespace dqnhip_host {
@@ -427,5 +431,12 @@ int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behin
 int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
 int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
 void diag_free(H* h);                                    // dqnhip_diag_collect's scratch
+// asynchronous learner-state save: the launchers of state_kernels.hip.h, on the learner's stream (learner_io.hip) ...
+int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev);
+int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a);
+int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a);
+// ... and its host side (learner_state.hip)
+int state_async_join(H* h, const char* what);            // waits for a save in flight; fails, as `what`, with its message if it failed
+void state_async_free(H* h);                             // dqnhip_destroy: joins, stops the writer thread, frees; never fails
 
 }  // namespace dqnhip_host

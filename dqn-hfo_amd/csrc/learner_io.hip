@@ -5,6 +5,7 @@
 #include "io_kernels.hip.h"
 #include "per_kernels.hip.h"
 #include "diag_kernels.hip.h"
+#include "state_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;
@@ -1108,3 +1109,50 @@ int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
 }
 
 }  // extern "C"
+
+// ---- asynchronous learner-state save: the launchers of state_kernels.hip.h (the host side: learner_state.hip) ----
+namespace dqnhip_host {
+
+int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev) {
+  const float* p_max = h->per ? &((const PerDev*)h->per->dev)->p_max : nullptr;
+  HIPCHK(launch(h->stream, k_state_pack_params, dim3(64, n_seg + 1), dim3(256), 0, segs_dev, n_seg, (const DevState*)h->st, p_max, rec_dev));
+  return 0;
+}
+int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a) {
+  if (a.cap < 1 || a.n_arr < 1 || a.n_arr > dqnhip_state::kRingArrays) return fail("state_pack_ring_launch: bad arguments");
+  HIPCHK(launch(h->stream, k_state_pack_ring, dim3((a.cap + dqnhip_state::kPackRows - 1) / dqnhip_state::kPackRows, a.n_arr), dim3(256), 0, a));
+  return 0;
+}
+int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a) {
+  if (a.n < 1 || a.n > dqnhip_state::kMaxCrcSections) return fail("state_crc_launch: bad arguments");
+  if (a.total_chunks == 0) return 0;
+  HIPCHK(launch(h->stream, k_state_crc, dim3((a.total_chunks + 255) / 256), dim3(256), 0, a));
+  return 0;
+}
+
+}  // namespace dqnhip_host
+
+extern "C" int dqnhip_state_crc32_device(dqnhip_handle h, const void* host_bytes, size_t bytes, int32_t misalign, uint32_t* crc) {
+  using namespace dqnhip_state;
+  if (!h || !crc || (!host_bytes && bytes)) return fail("dqnhip_state_crc32_device: null argument");
+  if (misalign < 0 || misalign > 15) return fail("dqnhip_state_crc32_device: misalign %d is outside 0 ... 15", misalign);
+  if (bytes > ((size_t)1 << 31)) return fail("dqnhip_state_crc32_device: %zu bytes are more than this door takes (2^31)", bytes);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t chunks = (bytes + kCrcChunk - 1) / kCrcChunk, out_off = round_up_z((size_t)misalign + bytes, 16);
+  RC(ensure_stage(h, out_off + chunks * sizeof(uint32_t) + 16));
+  uint8_t* base = (uint8_t*)h->stage_dev;
+  if (bytes) HIPCHK(hipMemcpyAsync(base + misalign, host_bytes, bytes, hipMemcpyHostToDevice, h->stream));
+  CrcArgs a{};
+  a.base = base; a.rec = nullptr; a.out = (uint32_t*)(base + out_off); a.n = 1; a.max_rows = 0; a.total_chunks = (uint32_t)chunks;
+  a.sec[0] = CrcSection{(uint64_t)misalign, (uint64_t)bytes, 0u, 0u};
+  RC(state_crc_launch(h, a));
+  std::vector<uint32_t> raws(chunks);
+  if (chunks) HIPCHK(hipMemcpyAsync(raws.data(), a.out, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint32_t op[32];
+  std::vector<uint32_t> tab(kCrcTableWords);
+  crc_zeros_op(op, kCrcChunk);
+  crc_op_table(tab.data(), op);
+  *crc = crc_fold_chunks(raws.data(), bytes, tab.data());
+  return 0;
+}

@@ -50,18 +50,19 @@ std::string tag_name(uint32_t tag) {
   return s;
 }
 
-int write_file(const char* filename, const dqnhip_state_info_t& info, const std::vector<Section>& sections, std::string* err) {
-  const std::string fn(filename), tmp = fn + ".tmp";
-  if (sections.size() > kMaxSections) return set(err, fn + ": too many sections");
-  const uint32_t n = (uint32_t)sections.size();
+namespace {
+
+// header + section table of a file whose sections are `e` (tag, crc, bytes), packed back to back behind the table
+std::vector<uint8_t> build_head(const dqnhip_state_info_t& info, const std::vector<StreamEntry>& e) {
+  const uint32_t n = (uint32_t)e.size();
   std::vector<uint8_t> head(kHeaderTotal + (size_t)n * kEntryBytes, 0);
   uint64_t off = head.size(), user_bytes = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    uint8_t* e = head.data() + kHeaderTotal + (size_t)i * kEntryBytes;
-    put<uint32_t>(e, 0, sections[i].tag); put<uint32_t>(e, 4, crc_of(sections[i].data, sections[i].bytes));
-    put<uint64_t>(e, 8, off); put<uint64_t>(e, 16, sections[i].bytes);
-    off += sections[i].bytes;
-    if (sections[i].tag == kTagUser) user_bytes = sections[i].bytes;
+    uint8_t* t = head.data() + kHeaderTotal + (size_t)i * kEntryBytes;
+    put<uint32_t>(t, 0, e[i].tag); put<uint32_t>(t, 4, e[i].crc);
+    put<uint64_t>(t, 8, off); put<uint64_t>(t, 16, e[i].bytes);
+    off += e[i].bytes;
+    if (e[i].tag == kTagUser) user_bytes = e[i].bytes;
   }
   uint8_t* h = head.data();
   memcpy(h + oMagic, kMagic, 8);
@@ -77,17 +78,61 @@ int write_file(const char* filename, const dqnhip_state_info_t& info, const std:
   put<uint64_t>(h, oUserBytes, user_bytes); put<uint64_t>(h, oFileBytes, off);
   put<uint32_t>(h, oTableCrc, crc_of(h + kHeaderTotal, (uint64_t)n * kEntryBytes));
   put<uint32_t>(h, oHeaderCrc, crc_of(h, oHeaderCrc));
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) return set(err, "cannot open " + tmp + " for writing: " + strerror(errno));
-  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
-  for (uint32_t i = 0; i < n && ok; ++i)
-    ok = sections[i].bytes == 0 || fwrite(sections[i].data, 1, sections[i].bytes, f) == sections[i].bytes;
-  ok = fflush(f) == 0 && ok;
-  ok = fsync(fileno(f)) == 0 && ok;                 // (the rename below must not overtake the data on its way to the disk)
-  ok = fclose(f) == 0 && ok;
-  if (!ok) { const std::string why = strerror(errno); remove(tmp.c_str()); return set(err, "short write to " + tmp + ": " + why); }
-  if (rename(tmp.c_str(), fn.c_str()) != 0) { const std::string why = strerror(errno); remove(tmp.c_str()); return set(err, "rename " + tmp + " -> " + fn + " failed: " + why); }
+  return head;
+}
+
+}  // namespace
+
+uint32_t crc32_of(const void* p, uint64_t n) { return crc_of(p, n); }
+
+int write_file(const char* filename, const dqnhip_state_info_t& info, const std::vector<Section>& sections, std::string* err) {
+  if (sections.size() > kMaxSections) return set(err, std::string(filename) + ": too many sections");
+  std::vector<StreamEntry> e;
+  for (const Section& s : sections) e.push_back({s.tag, crc_of(s.data, s.bytes), s.bytes});
+  StreamWriter w;
+  if (w.open(filename, info, e, err)) return 1;
+  for (const Section& s : sections)
+    if (w.append(s.data, s.bytes, err)) return 1;
+  return w.finish(err);
+}
+
+int StreamWriter::open(const char* filename, const dqnhip_state_info_t& info, const std::vector<StreamEntry>& entries, std::string* err) {
+  abort();
+  fn_ = filename; tmp_ = fn_ + ".tmp";
+  if (entries.size() > kMaxSections) return set(err, fn_ + ": too many sections");
+  const std::vector<uint8_t> head = build_head(info, entries);
+  left_ = 0;
+  for (const StreamEntry& e : entries) left_ += e.bytes;
+  f_ = fopen(tmp_.c_str(), "wb");
+  if (!f_) return set(err, "cannot open " + tmp_ + " for writing: " + strerror(errno));
+  if (fwrite(head.data(), 1, head.size(), f_) != head.size()) { const std::string why = strerror(errno); abort(); return set(err, "short write to " + tmp_ + ": " + why); }
   return 0;
+}
+
+int StreamWriter::append(const void* data, uint64_t bytes, std::string* err) {
+  if (!f_) return set(err, fn_ + ": append without an open file");
+  if (bytes > left_) { abort(); return set(err, fn_ + ": more payload bytes than the section table declares"); }
+  if (bytes && fwrite(data, 1, bytes, f_) != bytes) { const std::string why = strerror(errno); abort(); return set(err, "short write to " + tmp_ + ": " + why); }
+  left_ -= bytes;
+  return 0;
+}
+
+int StreamWriter::finish(std::string* err) {
+  if (!f_) return set(err, fn_ + ": finish without an open file");
+  if (left_) { abort(); return set(err, fn_ + ": fewer payload bytes than the section table declares"); }
+  bool ok = fflush(f_) == 0;
+  ok = fsync(fileno(f_)) == 0 && ok;                // (the rename below must not overtake the data on its way to the disk)
+  ok = fclose(f_) == 0 && ok;
+  f_ = nullptr;
+  if (!ok) { const std::string why = strerror(errno); remove(tmp_.c_str()); return set(err, "short write to " + tmp_ + ": " + why); }
+  if (rename(tmp_.c_str(), fn_.c_str()) != 0) { const std::string why = strerror(errno); remove(tmp_.c_str()); return set(err, "rename " + tmp_ + " -> " + fn_ + " failed: " + why); }
+  return 0;
+}
+
+void StreamWriter::abort() {
+  if (!f_) return;
+  fclose(f_); f_ = nullptr;
+  remove(tmp_.c_str());
 }
 
 int read_file(const char* filename, Parsed* out, bool keep, std::string* err) {

@@ -2,6 +2,7 @@
 // state_codec.cpp.  Host code only; not installed, not part of the C-ABI.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -43,6 +44,27 @@ std::string tag_name(uint32_t tag);
 // Writes header, table and the sections back to back into filename + ".tmp" and renames it over filename.  info: every field the
 // header stores except user_bytes and file_bytes, which are derived here.  On failure *err says why and filename is untouched.
 int write_file(const char* filename, const dqnhip_state_info_t& info, const std::vector<Section>& sections, std::string* err);
+
+// The same file, streamed: header and table first — every section's CRC and size are known before its bytes arrive — then the
+// payload in table order, in pieces of any size, then the flush and rename of write_file.  open/append/finish return 0 or set *err;
+// a failure (and a writer dropped before finish) removes the ".tmp" and leaves filename untouched.  write_file is built on it.
+struct StreamEntry { uint32_t tag, crc; uint64_t bytes; };
+class StreamWriter {
+ public:
+  StreamWriter() = default;
+  StreamWriter(const StreamWriter&) = delete;
+  StreamWriter& operator=(const StreamWriter&) = delete;
+  ~StreamWriter() { abort(); }
+  int open(const char* filename, const dqnhip_state_info_t& info, const std::vector<StreamEntry>& entries, std::string* err);
+  int append(const void* data, uint64_t bytes, std::string* err);
+  int finish(std::string* err);
+  void abort();
+ private:
+  std::string fn_, tmp_;
+  FILE* f_ = nullptr;
+  uint64_t left_ = 0;            // payload bytes the table declares and append has not seen yet
+};
+uint32_t crc32_of(const void* p, uint64_t n);      // zlib's, over any length
 
 struct Parsed {
   dqnhip_state_info_t info{};

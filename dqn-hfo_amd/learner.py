@@ -746,10 +746,30 @@ class DQN:
         return out.astype(np.int64) if name == "slot" else out
 
     # -- native learner-state file (include/dqnhip.h: exact resume, opt-in) ----------------------------------
-    def save_state(self, path, memory=True, user=b""):
-        """dqnhip_save_state: everything a bit-exact resume needs, in one file; `user` is an opaque section of the caller's."""
+    def save_state(self, path, memory=True, user=b"", wait=True):
+        """dqnhip_save_state: everything a bit-exact resume needs, in one file; `user` is an opaque section of the caller's.
+        wait=False: dqnhip_save_state_async — the same bytes, frozen on the device at this point of the stream and written by the
+        learner's writer thread while training goes on; save_state_wait() joins it and reports its status."""
         user = bytes(user)
-        self._ck(self.lib.dqnhip_save_state(self.h, os.fsencode(path), 0 if memory else capi.STATE_NO_MEMORY, user or None, len(user)))
+        fn = self.lib.dqnhip_save_state if wait else self.lib.dqnhip_save_state_async
+        self._ck(fn(self.h, os.fsencode(path), 0 if memory else capi.STATE_NO_MEMORY, user or None, len(user)))
+
+    def save_state_wait(self):
+        """dqnhip_save_state_wait: joins an asynchronous save in flight; raises if it failed."""
+        self._ck(self.lib.dqnhip_save_state_wait(self.h))
+
+    def save_state_done(self):
+        """dqnhip_save_state_poll: True when no asynchronous save is in flight.  Never blocks."""
+        done = C.c_int32()
+        self._ck(self.lib.dqnhip_save_state_poll(self.h, C.byref(done)))
+        return bool(done.value)
+
+    def state_crc32_device(self, data, misalign=0):
+        """dqnhip_state_crc32_device: the asynchronous save's checksum path on `data` (bytes); equals zlib.crc32(data)."""
+        data = bytes(data)
+        crc = C.c_uint32()
+        self._ck(self.lib.dqnhip_state_crc32_device(self.h, data or None, len(data), int(misalign), C.byref(crc)))
+        return crc.value
 
     def load_state(self, path):
         """dqnhip_load_state: validates the whole file first; a failure leaves the learner untouched."""

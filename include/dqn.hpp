@@ -168,6 +168,10 @@ class DQN {
   std::string native_stem_; bool native_has_memory_ = false;
   void SaveNativeState(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory);
   void LoadNativeState(const std::string& critic_solverstate);
+  // -native_state_async: SaveNativeState calls dqnhip_save_state_async; the save is joined (and the files it supersedes removed) at
+  // the next SaveNativeState, at LoadNativeState and in the destructor
+  bool native_in_flight_ = false; std::string native_remove_; int native_remove_below_ = 0;
+  void JoinNativeState();
   dqnhip_handle h_;
 };
 

@@ -842,6 +842,30 @@ int dqnhip_state_info(const char* filename, dqnhip_state_info_t* out);
 /* The caller's section: *n_out = its length (0: none); fails if it exceeds cap. */
 int dqnhip_state_read_user(const char* filename, void* buf, size_t cap, size_t* n_out);
 
+/* ---- the same file, written behind training (opt-in) ---------------------------------------------------------------------------
+ * dqnhip_save_state_async writes, byte for byte, the file dqnhip_save_state would have written at this point of the learner's
+ * stream, without waiting for the stream.  On the caller's thread: the argument checks and v1 refusals of dqnhip_save_state
+ * (reported by this call), the tree brought in step with the ring, then three launches on the learner's stream — the parameters
+ * into dense Caffe order plus a record of the DevState fields, the ring's window in logical order ((ring_head, ring_size) are read
+ * on the device), zlib's CRC-32 of every section in 1 KB chunks (csrc/state_kernels.hip.h) — into a device staging buffer, and
+ * an event.  `user` and the host-side values are copied; the call returns.  A writer thread (one per learner) waits for the
+ * event, folds the chunk CRCs, and streams the staging buffer through two pinned 8 MB chunks to filename + ".tmp", then renames.
+ * Whatever is enqueued after the call returns — updates, appends, acting, env steps, parameter writes, snapshots — is not in the
+ * image.  Not part of it: the host-side conveniences of the synchronous call (harvesting indexed updates, refreshing the host's
+ * (head, size) mirror).
+ * One save is in flight per learner: a second dqnhip_save_state_async, dqnhip_save_state, dqnhip_load_state and dqnhip_destroy
+ * first join it; if it failed, the joining call fails with its message (dqnhip_destroy still destroys and does not fail).
+ * Cost: from the first asynchronous save until dqnhip_destroy, device memory of the file's upper bound for this learner (the
+ * staging buffer) and 16 MB of pinned host memory.  If the staging buffer cannot be allocated the call fails and says so;
+ * dqnhip_save_state needs none. */
+int dqnhip_save_state_async(dqnhip_handle h, const char* filename, int32_t flags, const void* user, size_t user_bytes);
+int dqnhip_save_state_wait(dqnhip_handle h);                 /* joins; the save's status; 0 when none is in flight */
+int dqnhip_save_state_poll(dqnhip_handle h, int32_t* done);  /* never blocks; *done = 1: nothing is in flight */
+/* The save's checksum path on caller-supplied bytes: host_bytes are copied into device scratch `misalign` bytes (0 ... 15) past
+ * a 16-byte boundary, the chunk kernel and the combine step of the asynchronous save run, *crc = zlib's crc32 of the bytes.
+ * Stream-ordered, blocks.  For tests, and for anyone who wants to verify a buffer. */
+int dqnhip_state_crc32_device(dqnhip_handle h, const void* host_bytes, size_t bytes, int32_t misalign, uint32_t* crc);
+
 /* ---- batched env front-end (HFOGameState reward shaping, N workers) ----- */
 
 /* Replaces HFOGameState::update + reward (src/hfo_game.cpp:122-236) for n
