@@ -359,6 +359,15 @@ int sync_w16(H* h, hipStream_t st, int net) {
     cvt16_add(b, h->w[net] + l.w_off[i], l.kp[i], l.dims[i + 1], l.kp[i], h->w16[net][i], h->k16[kind][i], 1.0f);
     if (b.n == 8) { HIPCHK(cvt16_launch(b, st)); b = Cvt16Batch{}; }
   }
+  // ... and what lies between the matrices (the biases; behind the last tower layer's, the heads): no GEMM reads those from the mirror,
+  // but the optimiser pass writes the WHOLE arena's mirror, the target's only when the soft update is on — without this a target's mirror
+  // kept whatever it held there before a host-side change until the next soft update (debug buffer w16_<net>: the mirror is the
+  // master's image everywhere)
+  for (int i = 0; i < l.L; ++i) {
+    const size_t lo = l.b_off[i], hi = i + 1 < l.L ? l.w_off[i + 1] : l.arena;      // (whole 64-float lines: layout_init)
+    cvt16_add(b, h->w[net] + lo, (int)(hi - lo), 1, (int)(hi - lo), h->w16a[net] + lo, (int)(hi - lo), 1.0f);
+    if (b.n == 8) { HIPCHK(cvt16_launch(b, st)); b = Cvt16Batch{}; }
+  }
   HIPCHK(cvt16_launch(b, st));
   h->w16_dirty[net] = false;
   return 0;

@@ -857,7 +857,7 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   const float* src = nullptr; size_t n = B; bool pad16 = false; bool is_int = false;
   if (!strcmp(name, "indexed_graph_launches")) {
     if (count < 1) return fail("buffer too small for '%s'", name);
-    host[0] = (float)h->ix_nodes[0];
+    for (size_t k = 0; k < std::min(count, (size_t)kIxSizes); ++k) host[k] = (float)h->ix_nodes[k];      // [16, 8, 4, 2, 1 updates]
     return 0;
   }
   if (!strcmp(name, "q_target")) src = h->q_t;
@@ -884,6 +884,22 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
       HIPCHK(hipMemcpy(t16.data(), h->act16[p][i], t16.size() * sizeof(h16), hipMemcpyDeviceToHost));
       for (size_t e = 0; e < t16.size(); ++e) host[e] = (float)t16[e];
     } else HIPCHK(hipMemcpy(host, h->act[p][i], B * W * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  else if (!strncmp(name, "w16_", 4) && name[4] >= '0' && name[4] <= '3' && name[5] == 0) {
+    // "w16_<net>": the fp16 mirror of a net's weight arena (the copy the fp16 GEMMs read; the optimiser pass writes it beside the fp32
+    // master, host-side weight changes reach it with the next launch sequence: sync_dirty16), as stored, widened to float, in
+    // dqnhip_get_params' dense Caffe order
+    if (!h->fp16) return fail("debug buffer '%s': an fp32 learner keeps no fp16 weight mirror", name);
+    const int net = name[4] - '0';
+    const NetLayout& l = layout_of(h, net);
+    if (count < l.dense) return fail("buffer too small for '%s': %zu < %zu", name, count, l.dense);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<h16> t16(l.arena);
+    HIPCHK(hipMemcpy(t16.data(), h->w16a[net], t16.size() * sizeof(h16), hipMemcpyDeviceToHost));
+    std::vector<float> arena(l.arena);
+    for (size_t e = 0; e < t16.size(); ++e) arena[e] = (float)t16[e];
+    arena_to_dense(l, arena, host);
     return 0;
   }
   else if (!strcmp(name, "dq")) src = h->dq;

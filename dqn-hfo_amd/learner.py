@@ -617,6 +617,10 @@ class DQN:
             out = np.empty(B * width, np.float32)
             self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
             return out.reshape(B, width)
+        if name.startswith("w16_"):       # "w16_<net>": the fp16 weight mirror of a net, widened, dense Caffe order like get_params
+            out = np.empty(self.param_count(int(name[4:])), np.float32)
+            self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
+            return out
         if name in ("dz_c", "dz_a"):      # tower-top gradients [B][last hidden width] (fp16 learner: the scaled panel, widened)
             width = self.cfg.hidden[self.cfg.num_hidden - 1]
             out = np.empty(B * width, np.float32)

@@ -616,7 +616,8 @@ int dqnhip_remove_snapshots(const char* regexp, int32_t min_iter);
  * "q_policy" [B], "actor_out" [B,10] (mu(s)), "dq_da" [B,10] (post
  * inverting-gradients), "idx" [B] (as float), "terminal" [B];
  * "indexed_graph_launches" [1]: the kernel nodes of the sixteen-update graph dqnhip_update_indexed_n has captured (0: none
- * captured, or dropped since - sharing, set-up of data parallelism).
+ * captured, or dropped since - sharing, set-up of data parallelism); a buffer of 5 floats or more also gets those of the eight-,
+ * four-, two- and one-update graphs in [1] .. [4].
  * What the head layers hand on, for per-element tests between the phases of dqnhip_update_phase:
  * "dq" [B]: Step(1)'s loss diff (q - y) / B, valid after phase 0;
  * "actor_target_out" [B,10]: mu'(s'), valid after phase 0;
@@ -629,6 +630,9 @@ int dqnhip_remove_snapshots(const char* regexp, int32_t min_iter);
  *   never writes the buffer (DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD restores it).
  * Nothing else in an update overwrites these before the phase that wrote them returns; after a whole update they hold what
  * phase 1 left (dz_c: the seed).
+ * "w16_0" .. "w16_3" [dqnhip_param_count(net)]: fp16 learner only — the fp16 mirror of that net's weights (the copy the fp16
+ *   GEMMs read; the optimiser pass writes it beside the fp32 master), as stored, widened to float, in dqnhip_get_params' dense
+ *   order.  After any update or dqnhip_apply_update it equals (fp16)master element for element.
  * count = floats the caller's buffer holds; fails if too small. */
 int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
 

@@ -142,14 +142,19 @@ def test_apply_update_is_the_pass_inside_an_update(pkg, gpu):
 
 
 def test_apply_update_fp16_learner_keeps_its_mirrors(pkg, gpu):
-    """fp16 learner: the pass also writes the fp16 weight mirrors the GEMMs read — an update after an isolated
-    ApplyUpdate must see the stepped weights (checked through the greedy action of the stepped actor)."""
+    """fp16 learner: the pass also writes the fp16 weight mirrors the GEMMs read — after an isolated ApplyUpdate the mirror of the
+    stepped net and of its soft-updated target are float16(master) bit for bit (debug_read("w16_<net>")), and so are the two nets the
+    call did not touch (their mirrors were brought up to date from the host-side weights before the pass ran)."""
+    import adam_ref
     S, hidden = 58, (128, 128)
     d, o = _pair(pkg, S, hidden, precision="fp16")
     rng = np.random.default_rng(3)
     before = _load(pkg, d, o, rng, S, hidden, 0, 50.0, 0, 0)
     d.apply_update(0); o.apply_update(0)
     _check(pkg, d, o, 0, before, exact_scale=False, t=1)
+    assert not np.array_equal(d.get_params(2), before[1])          # soft_update_freq = 1: the target moved
+    for net in range(4):
+        adam_ref.check_mirror("apply_update(0)", "w16_%d" % net, d.debug_read("w16_%d" % net), d.get_params(net))
     st = rng.uniform(-1, 1, (8, S)).astype(np.float32)
     a = d.SelectActionGreedily(st)             # fp32 acting path on the stepped master weights
     np.testing.assert_allclose(a, o.actor_forward(st), atol=1e-3, rtol=1e-3)
