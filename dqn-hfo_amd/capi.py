@@ -22,7 +22,8 @@ PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor"
 LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
 FP32, FP16 = 0, 1                                   # DQNHIP_FP32 / DQNHIP_FP16: dqnhip_config.precision, dqnhip_set_act_precision
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
-KIND_W, KIND_M, KIND_V, KIND_G = 0, 1, 2, 3
+KIND_W, KIND_M, KIND_V, KIND_G = 0, 1, 2, 3       # (KIND_M / KIND_V: solver history 1 / 2)
+SOLVERS = ("Adam", "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta")      # DQNHIP_SOLVER_*, by value: Caffe's type strings
 
 
 class Config(C.Structure):
@@ -37,6 +38,7 @@ class Config(C.Structure):
         ("device", C.c_int32), ("dp_world", C.c_int32), ("dp_rank", C.c_int32), ("use_graph", C.c_int32),
         ("seed", C.c_uint64), ("stream", C.c_void_p), ("grad_arena", C.c_void_p),
         ("grad_arena_bytes", C.c_size_t), ("precision", C.c_int32), ("loss_scale", C.c_float),
+        ("solver_type", C.c_int32), ("rms_decay", C.c_float),
         ("tuning_flags", C.c_int32),
         ("loss_scale_mode", C.c_int32), ("loss_scale_growth_interval", C.c_int32),
         ("loss_scale_min_mult", C.c_float), ("loss_scale_max_mult", C.c_float),
@@ -53,7 +55,7 @@ class LossScaleState(C.Structure):
 class UpdatePlan(C.Structure):
     """struct dqnhip_update_plan (include/dqnhip.h)."""
     _fields_ = [("struct_size", C.c_int32), ("forms", C.c_int32), ("launches_single", C.c_int32), ("launches_graph_first", C.c_int32),
-                ("launches_in_graph", C.c_int32), ("updates_per_graph", C.c_int32), ("collectives", C.c_int32), ("reserved", C.c_int32)]
+                ("launches_in_graph", C.c_int32), ("updates_per_graph", C.c_int32), ("collectives", C.c_int32), ("solver_type", C.c_int32)]
 
 
 class PerConfig(C.Structure):
@@ -75,7 +77,7 @@ class StateInfo(C.Structure):
                 ("state_size", C.c_int32), ("num_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_HIDDEN), ("replay_capacity", C.c_int32),
                 ("memory_size", C.c_int32), ("actor_iter", C.c_int32), ("critic_iter", C.c_int32), ("has_memory", C.c_int32),
                 ("has_per", C.c_int32), ("has_loss_scale", C.c_int32), ("seed", C.c_uint64), ("update_counter", C.c_uint64),
-                ("user_bytes", C.c_uint64), ("file_bytes", C.c_uint64)]
+                ("user_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("solver_type", C.c_int32), ("rms_decay", C.c_float)]
 
 
 STATE_NO_MEMORY = 1      # DQNHIP_STATE_NO_MEMORY
@@ -133,6 +135,7 @@ H = C.c_void_p
 # name -> (restype, argtypes): every function include/dqnhip.h declares
 SIGNATURES = {
     "dqnhip_default_config": (None, [C.POINTER(Config), C.c_int32]),
+    "dqnhip_solver_name": (C.c_char_p, [C.c_int32]),
     "dqnhip_grad_arena_bytes": (C.c_size_t, [C.POINTER(Config)]),
     "dqnhip_last_error": (C.c_char_p, []),
     "dqnhip_create": (C.c_int, [C.POINTER(Config), C.POINTER(H)]),

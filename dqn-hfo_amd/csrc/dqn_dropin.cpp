@@ -283,7 +283,26 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
   // (the reference's default); anything else would silently train with a different schedule than the user asked for
   for (const caffe::SolverParameter* sp : {&actor_solver_param_, &critic_solver_param_})
     CHECK(sp->lr_policy().empty() || sp->lr_policy() == "fixed") << "only -lr_policy fixed is implemented (got '" << sp->lr_policy() << "')";
-  CHECK(actor_solver_param_.type() == "Adam" && critic_solver_param_.type() == "Adam") << "only the Adam solver is implemented (-solver Adam, the reference's default)";
+  // -solver (src/dqn_main.cpp:30 -> SolverParameter::set_type -> SolverRegistry::CreateSolver, src/dqn.cpp:628-629): Caffe's six type
+  // strings; the fused optimiser pass runs ONE rule, so the two solvers must name the same type (the driver sets both from the flag)
+  CHECK(actor_solver_param_.type() == critic_solver_param_.type()) << "actor and critic solvers must be of the same type (got '"
+      << actor_solver_param_.type() << "' and '" << critic_solver_param_.type() << "')";
+  CHECK(actor_solver_param_.rms_decay() == critic_solver_param_.rms_decay()) << "actor and critic solvers must share rms_decay";
+  c.solver_type = -1;
+  for (int s = 0; dqnhip_solver_name(s) != nullptr; ++s)
+    if (critic_solver_param_.type() == dqnhip_solver_name(s)) c.solver_type = s;
+  CHECK(c.solver_type >= 0) << "Unknown solver type: " << critic_solver_param_.type() << " (known types: Adam, SGD, Nesterov, AdaGrad, RMSProp, AdaDelta)";
+  c.rms_decay = critic_solver_param_.rms_decay();
+  // Caffe's solver constructors, with their wording (the library refuses the same; here it is the reference's abort)
+  if (c.solver_type == DQNHIP_SOLVER_ADAGRAD) CHECK_EQ(0, c.momentum) << "Momentum cannot be used with AdaGrad.";
+  if (c.solver_type == DQNHIP_SOLVER_RMSPROP) {
+    CHECK_EQ(0, c.momentum) << "Momentum cannot be used with RMSProp.";
+    CHECK_GE(c.rms_decay, 0) << "rms_decay should lie between 0 and 1.";
+    CHECK_LT(c.rms_decay, 1) << "rms_decay should lie between 0 and 1.";
+  }
+  if (c.solver_type != DQNHIP_SOLVER_ADAM) CHECK_LE(FLAGS_debug_info_iter, 0) << "-debug_info_iter needs -solver Adam (the diagnostics are defined through Adam's m and v)";
+  if (c.solver_type != DQNHIP_SOLVER_ADAM)
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-solver " << critic_solver_param_.type() << " is a single-learner option (-dp_world 1, no -dp_rendezvous)";
   c.device = FLAGS_hip_device + tid * FLAGS_hip_agent_device_stride;
   c.use_graph = FLAGS_hip_graph ? 1 : 0;
   c.seed = seed;

@@ -13,6 +13,7 @@
 #include "head_fwd_kernels.hip.h"
 #include "head_kernels.hip.h"
 #include "small_kernels.hip.h"
+#include "solver_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;
@@ -269,6 +270,27 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
   // k_adam_soft_l0, k_adam_soft_fwd1_gather and k_adam_soft_gather below are launched while a multi-update or chain graph is being
   // captured (cap_u >= 0) and never otherwise; a learner with kernel timing on does not capture, so their LaunchOn carries no events
   if (h->timing && h->cap_u >= 0) return fail("internal: adam_launch inside a graph capture with kernel timing on");
+  // A learner whose solver is not Adam reaches k_solver_soft<> / k_solver_soft_gather<> and nothing else (solver_kernels.hip.h): the
+  // same arguments (beta2's slot carries rms_decay: solver_hyper), the same grid rule, the same timing family; no first-layer riders
+  const int solver = h->cfg.solver_type;
+  if (solver != DQNHIP_SOLVER_ADAM) {
+    if (fl != nullptr || early_gather != nullptr || next_l0 != nullptr)
+      return fail("internal: adam_launch: the %s solver's optimiser launches carry no first-layer riders", dqnhip_solver_name(solver));
+    a.beta2 = h->cfg.rms_decay;
+    const LaunchOn on = timed(h, kFamAdam, st);
+    const int blocks = (int)std::min<size_t>((a.n4 + 255) / 256, (size_t)1536);
+    if (tick && h->cap_u >= 0 && h->cap_u + 1 < h->cap_n) {      // (early_l0(h) is false on this learner: the gather rides here, as in k_adam_soft_gather)
+      const GatherArgs g = gather_args(h, nullptr, h->cap_u + 1);
+      const int ablocks = std::min(blocks, std::max(1536 - g.blocks, 1280));
+      h->opt_launches[2] += 1;
+      HIPCHK(solver_launch(solver, on, ablocks, a, &g));
+    } else {
+      h->opt_launches[1] += 1;
+      HIPCHK(solver_launch(solver, on, blocks, a, nullptr));
+    }
+    return 0;
+  }
+  h->opt_launches[0] += 1;
   const LaunchOn on = timed(h, kFamAdam, st);
   // 1536 blocks = 6 per CU, all resident at once (68 VGPRs: 7 waves per SIMD): with the loads hoisted above the prologue
   // same-box A/B gives 18.4 us per launch against 19.3 at 2048 (a second, short round of blocks), 19.4 at 1792, 18.7 at
@@ -912,6 +934,8 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world) {
   h->epoch += 1;
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
   if (h->next_phase != 0) return fail("dqnhip_apply_update_sharded: a phased update is in progress (next phase %d)", h->next_phase);
+  if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
+    return fail("dqnhip_apply_update_sharded: the %s solver has no sharded form in this version (DESIGN.md 9); use dqnhip_apply_update", dqnhip_solver_name(h->cfg.solver_type));
   const NetLayout& l = layout_of(h, net);
   if (world < 1 || l.arena % ((size_t)4 * world)) return fail("apply_update_sharded: the arena (%zu floats) must be divisible by 4 x world = %d", l.arena, 4 * world);
   HIPCHK(hipSetDevice(h->cfg.device));

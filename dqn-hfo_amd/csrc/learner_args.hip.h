@@ -3,8 +3,10 @@
 // and embeds no device code.  Layers, includes pointing downwards only:
 //   arguments   gemm_common.hip.h (GEMM problems, LaunchOn / launch, tails, flags), this header, gemm_plan.hip.h (the fp32 family's
 //               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
-//   bodies      gemm_bodies.hip.h, update_bodies.hip.h: __device__ functions only
+//   bodies      gemm_bodies.hip.h, update_bodies.hip.h, solver_bodies.hip.h (the optimiser pass of the solvers other than Adam):
+//               __device__ functions only
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
+//               solver_kernels.hip.h (the optimiser launches of the solvers other than Adam; learner.hip),
 //               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), diag_kernels.hip.h (update diagnostics;
 //               learner_io.hip), env.hip.h: __global__ functions and their launchers, grouped by the unit that launches them
 // One include points upwards: head_fwd_kernels.hip.h holds the launcher head_forward<>, which takes the learner and reports through

@@ -80,6 +80,13 @@ void dqnhip_default_config(dqnhip_config* c, int32_t state_size) {
   c->loss_scale_growth_interval = 2000;                // the customary value of mixed-precision trainers; not measured here
   c->loss_scale_min_mult = 1.0f / 4096.0f;             // ls_q x 2^-12 = 1: no scaling left
   c->loss_scale_max_mult = 1.0f;                       // never above the built-in scales unless asked
+  c->solver_type = DQNHIP_SOLVER_ADAM;                 // FLAGS_solver, src/dqn_main.cpp:30
+  c->rms_decay = .99f;                                 // Caffe SolverParameter.rms_decay default
+}
+
+const char* dqnhip_solver_name(int32_t solver_type) {
+  static const char* const kNames[] = {"Adam", "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta"};
+  return solver_type >= 0 && solver_type <= DQNHIP_SOLVER_ADADELTA ? kNames[solver_type] : nullptr;
 }
 
 int dqnhip_get_config(dqnhip_handle h, dqnhip_config* out) {

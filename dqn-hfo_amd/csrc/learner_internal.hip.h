@@ -272,6 +272,7 @@ struct dqnhip_learner {
   int ix_busy[kIxBanks] = {0};
   int ix_next = 0;                      // the bank the next graph takes (round robin: the busy banks are the most recent ones, in order)
   hipGraphExec_t ix_graph[kIxBanks][kIxSizes] = {{nullptr}};   // [bank][16, 8, 4, 2, 1 updates]
+  long long opt_launches[3] = {0, 0, 0};   // optimiser launches enqueued or captured: k_adam_soft*, k_solver_soft<>, k_solver_soft_gather<> (dqnhip_debug_read "optimiser_launches")
   int ix_nodes[kIxSizes] = {0};         // kernel nodes of the captured graph of each size (dqnhip_debug_read "indexed_graph_launches")
   const int* cap_idx = nullptr;         // while an indexed graph is captured / an indexed update runs eagerly: the bank's index slots ...
   float* cap_stats = nullptr;           // ... and its stats slots (device aliases); tick_args / gather_args read them

@@ -855,6 +855,11 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t B = h->B;
   const float* src = nullptr; size_t n = B; bool pad16 = false; bool is_int = false;
+  if (!strcmp(name, "optimiser_launches")) {      // [k_adam_soft*, k_solver_soft<>, k_solver_soft_gather<>] enqueued or captured so far
+    if (count < 3) return fail("buffer too small for '%s'", name);
+    for (int k = 0; k < 3; ++k) host[k] = (float)h->opt_launches[k];
+    return 0;
+  }
   if (!strcmp(name, "indexed_graph_launches")) {
     if (count < 1) return fail("buffer too small for '%s'", name);
     for (size_t k = 0; k < std::min(count, (size_t)kIxSizes); ++k) host[k] = (float)h->ix_nodes[k];      // [16, 8, 4, 2, 1 updates]
@@ -1027,6 +1032,9 @@ int dqnhip_diag_collect(dqnhip_handle h, dqnhip_diag_report* out) {
   if (h->next_phase != 0) return fail("dqnhip_diag_collect: diagnostics describe a finished update, and a phased update is in progress (next phase %d)", h->next_phase);
   if (h->w_owner) return fail("dqnhip_diag_collect: diagnostics are not available on a learner that reads another learner's parameters "
                               "(dqnhip_share_parameters: the arenas it steps are not all its own); collect on the owner");
+  if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
+    return fail("dqnhip_diag_collect: diagnostics are not available with the %s solver (the step, lag and moment records are defined through Adam's m and v: DESIGN.md 9)",
+                dqnhip_solver_name(h->cfg.solver_type));
   if (h->dp_shard) return fail("dqnhip_diag_collect: diagnostics are not available with a sharded optimiser (DQNHIP_DP_SHARD_OPT: m and v of foreign slices are stale)");
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!h->diag && diag_build(h)) { diag_free(h); return 1; }

@@ -112,6 +112,16 @@ int validate(const dqnhip_config* c) {
     if (c->loss_scale_min_mult > 1.0f) return fail("loss_scale_min_mult %g > 1: the multipliers start at 1", (double)c->loss_scale_min_mult);
     if (c->loss_scale_max_mult < 1.0f) return fail("loss_scale_max_mult %g < 1: the multipliers start at 1", (double)c->loss_scale_max_mult);
   }
+  // Caffe's solver constructors (adagrad / rmsprop: CHECK_EQ(0, momentum); rmsprop: CHECK_GE(rms_decay, 0), CHECK_LT(rms_decay, 1))
+  const char* solver = dqnhip_solver_name(c->solver_type);
+  if (!solver) return fail("unknown solver_type %d (DQNHIP_SOLVER_ADAM .. DQNHIP_SOLVER_ADADELTA)", c->solver_type);
+  if (c->solver_type == DQNHIP_SOLVER_ADAGRAD && c->momentum != 0.0f) return fail("Momentum cannot be used with AdaGrad. (momentum = %g)", (double)c->momentum);
+  if (c->solver_type == DQNHIP_SOLVER_RMSPROP) {
+    if (c->momentum != 0.0f) return fail("Momentum cannot be used with RMSProp. (momentum = %g)", (double)c->momentum);
+    if (!(c->rms_decay >= 0.0f && c->rms_decay < 1.0f)) return fail("RMSProp: rms_decay must be in [0, 1) (got %g)", (double)c->rms_decay);
+  }
+  if (c->solver_type != DQNHIP_SOLVER_ADAM && c->dp_world > 1)
+    return fail("the %s solver needs dp_world = 1 (got %d): its data-parallel forms do not exist in this version", solver, c->dp_world);
   return 0;
 }
 
@@ -199,6 +209,9 @@ UpdatePlan plan_of(const H* h) {
   // (prioritized replay: an update's indices do not exist before its predecessor's write-back — no rider gathers ahead)
   p.early_l0 = !p.prioritized && h->Xa_s2[1] != nullptr && !(tf & DQNHIP_TUNE_LATE_GATHER) && p.critic_l0 && p.first_layers_merged && h->shared_fl[DQNHIP_ACTOR] == 0 &&
                la.kp[0] == 64 && l0_can_ride(la);
+  // the first-layer riders step their slice with Adam's expression (adam_apply4): the other solvers' optimiser launches carry none —
+  // the schedule DQNHIP_TUNE_SEPARATE_FIRST_LAYER | DQNHIP_TUNE_LATE_GATHER give an Adam learner
+  if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM) { p.critic_l0 = false; p.early_l0 = false; }
   return p;
 }
 // ... while a multi-update graph is being captured (cap_u: the position of the update in it)

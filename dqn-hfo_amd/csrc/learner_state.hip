@@ -56,6 +56,7 @@ struct StateJob {
   bool with_mem = false, has_per = false, has_ls = false;
   std::vector<uint8_t> user;
   HostSection host{};
+  bool has_solver = false; SolverSection solver{};      // a learner whose solver is not Adam
   PerSection per{};                      // p_max comes from the record
   dqnhip_state_info_t info{};            // the config's share; the record fills the rest
   int device = 0, cap = 0;
@@ -155,6 +156,7 @@ int write_job(StateAsync* a, std::string* err) {
   std::vector<Out> out;
   for (int net = 0; net < 4; ++net) out.push_back({kTagW[net], net, nullptr, 0});
   for (int net = 0; net < 2; ++net) { out.push_back({kTagM[net], 4 + 2 * net, nullptr, 0}); out.push_back({kTagV[net], 5 + 2 * net, nullptr, 0}); }
+  if (j.has_solver) out.push_back({kTagSolver, -1, &j.solver, sizeof j.solver});
   out.push_back({kTagDev, -1, &devs, sizeof devs});
   if (j.has_ls) out.push_back({kTagLossScale, -1, &ls, sizeof ls});
   out.push_back({kTagHost, -1, &j.host, sizeof j.host});
@@ -371,6 +373,8 @@ int dqnhip_save_state_async(dqnhip_handle h, const char* filename, int32_t flags
   j.filename = filename; j.flags = flags; j.with_mem = with_mem; j.has_per = has_per; j.has_ls = h->ls_dynamic;
   if (user_bytes) j.user.assign((const uint8_t*)user, (const uint8_t*)user + user_bytes);
   j.host = HostSection{h->sample_states_calls, h->cfg.seed};
+  j.has_solver = h->cfg.solver_type != DQNHIP_SOLVER_ADAM;
+  j.solver = SolverSection{h->cfg.solver_type, h->cfg.rms_decay, {0, 0}};
   if (has_per) {
     const dqnhip_per_config& pc = h->per->cfg;
     j.per = PerSection{pc.alpha, pc.beta0, pc.beta_anneal_iters, pc.eps, pc.seed, 0.0f, 0, (int64_t)h->per->syncs};
@@ -433,6 +437,9 @@ int dqnhip_save_state(dqnhip_handle h, const char* filename, int32_t flags, cons
     sec.push_back({kTagM[net], m.data(), m.size() * sizeof(float)});
     sec.push_back({kTagV[net], v.data(), v.size() * sizeof(float)});
   }
+  // a learner whose solver is not Adam says so; an Adam learner's file is what it was before the other solvers existed
+  const SolverSection solver{h->cfg.solver_type, h->cfg.rms_decay, {0, 0}};
+  if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM) sec.push_back({kTagSolver, &solver, sizeof solver});
   const DevSection dev{st.actor_iter, st.critic_iter, st.update_counter, st.critic_loss, st.avg_q, st.flags, st.skipped_steps};
   sec.push_back({kTagDev, &dev, sizeof dev});
   const LossScaleSection ls{{st.ls_mult[0][0], st.ls_mult[1][0]}, {st.ls_good[0], st.ls_good[1]}, {st.ls_backoffs[0], st.ls_backoffs[1]},
@@ -504,6 +511,9 @@ int dqnhip_load_state(dqnhip_handle h, const char* filename) {
     return fail("dqnhip_load_state: %s: the file's nets (state_size %d, hidden %s) are not this learner's (state_size %d, hidden %s)", filename,
                 in.state_size, a.c_str(), h->cfg.state_size, b.c_str());
   }
+  if (in.solver_type != h->cfg.solver_type)
+    return fail("dqnhip_load_state: %s: the file was written by a learner with the %s solver, this learner's solver is %s (the histories mean something else)", filename,
+                dqnhip_solver_name(in.solver_type), dqnhip_solver_name(h->cfg.solver_type));
   const bool with_mem = in.has_memory != 0;
   // a section of exactly `bytes` bytes
   auto need = [&](uint32_t tag, uint64_t bytes, const uint8_t** out) -> int {

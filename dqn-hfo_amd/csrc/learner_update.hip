@@ -253,7 +253,7 @@ int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
                (p.critic_l0 ? DQNHIP_PLAN_CRITIC_L0_RIDES : 0) | (p.first_layers_merged ? DQNHIP_PLAN_FIRST_LAYERS_MERGED : 0) |
                (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0) |
                (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0);
-  out->updates_per_graph = kMultiU;
+  out->updates_per_graph = kMultiU; out->solver_type = h->cfg.solver_type;
   // per net and update: one all-reduce (per-layer buckets: one per tower layer + the head slice; bf16 exchange: the tails travel in a
   // second call beside the actor's; sharded optimiser: reduce-scatter + the 4-float all-reduce + 2 (fp16 learner: 4) all-gathers)
   if (h->comm) out->collectives = h->dp_shard ? 2 * (2 + (h->fp16 ? 4 : 2)) : h->dp_per_layer ? 2 * (h->L + 1) : h->dp_half ? 3 : 2;

@@ -225,6 +225,9 @@ int load_net_proto(const std::string& bytes, const std::vector<ParamBlob>& tbl, 
   return matched > 0 ? 0 : fail(path + ": no layer of this net found");
 }
 
+// Caffe's solvers that keep two history blobs per parameter (AdamSolver::AdamPreSolve, AdaDeltaSolver::AdaDeltaPreSolve)
+bool two_histories(int solver_type) { return solver_type == DQNHIP_SOLVER_ADAM || solver_type == DQNHIP_SOLVER_ADADELTA; }
+
 // ---- file search helpers (src/dqn.cpp:80-121, 559-580) ------------------------------------------
 std::vector<std::string> files_matching_regexp(const std::string& regexp) {
   fs::path stem(regexp), dir(fs::current_path());
@@ -287,14 +290,19 @@ int dqnhip_solver_snapshot(dqnhip_handle h, int32_t net, const char* prefix, int
   if (dqnhip_save_caffemodel(h, net, (base + ".caffemodel").c_str())) return 1;
   std::vector<ParamBlob> tbl; size_t total = 0;
   if (blob_table(h, net, tbl, total)) return 1;
+  dqnhip_config cfg;
+  if (dqnhip_get_config(h, &cfg)) return 1;
+  const bool two = two_histories(cfg.solver_type);
   std::vector<float> m(total), v(total);
   if (dqnhip_get_params(h, net, DQNHIP_KIND_M, m.data(), total)) return 1;
-  if (dqnhip_get_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;
+  if (two && dqnhip_get_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;
   std::string o;
   put_int(o, 1, iter);
   put_bytes(o, 2, base + ".caffemodel");
-  for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, m.data() + b.offset, b.count));   // AdamSolver history: all m, then all v
-  for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, v.data() + b.offset, b.count));
+  // SGDSolver::PreSolve gives every solver one history blob per parameter; AdamSolver and AdaDeltaSolver append a second set:
+  // history 1 of every blob, then history 2 of every blob (Adam: all m, then all v)
+  for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, m.data() + b.offset, b.count));
+  if (two) for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, v.data() + b.offset, b.count));
   put_int(o, 4, 0);                                                                           // current_step
   if (!write_file(base + ".solverstate", o)) return fail("cannot write " + base + ".solverstate");
   if (iter_out) *iter_out = iter;
@@ -317,7 +325,12 @@ int dqnhip_solver_restore(dqnhip_handle h, int32_t net, const char* solverstate)
     else r.skip(wt);
     if (!r.ok) return fail(std::string(solverstate) + ": malformed SolverState");
   }
-  if (hist.size() != 2 * tbl.size()) return fail(std::string(solverstate) + ": Incorrect length of history blobs.");   // Caffe CHECK_EQ
+  dqnhip_config cfg;
+  if (dqnhip_get_config(h, &cfg)) return 1;
+  const bool two = two_histories(cfg.solver_type);
+  if (hist.size() != (two ? 2 : 1) * tbl.size())                                                                       // Caffe CHECK_EQ
+    return fail(std::string(solverstate) + ": Incorrect length of history blobs. (" + std::to_string(hist.size()) + " in the file, the " +
+                dqnhip_solver_name(cfg.solver_type) + " solver of this learner keeps " + std::to_string((two ? 2 : 1) * tbl.size()) + ")");
   if (!learned.empty()) {
     // Solver::Restore -> net_->CopyTrainedLayersFrom(learned_net); a relative or stale path is
     // retried next to the .solverstate (snapshots are renamed after writing, src/dqn.cpp:596-604)
@@ -332,13 +345,13 @@ int dqnhip_solver_restore(dqnhip_handle h, int32_t net, const char* solverstate)
   }
   std::vector<float> m(total), v(total);
   for (size_t i = 0; i < tbl.size(); ++i) {
-    if (hist[i].data.size() != tbl[i].count || hist[i + tbl.size()].data.size() != tbl[i].count)
+    if (hist[i].data.size() != tbl[i].count || (two && hist[i + tbl.size()].data.size() != tbl[i].count))
       return fail(std::string(solverstate) + ": history blob shape mismatch");
     memcpy(m.data() + tbl[i].offset, hist[i].data.data(), tbl[i].count * 4);
-    memcpy(v.data() + tbl[i].offset, hist[i + tbl.size()].data.data(), tbl[i].count * 4);
+    if (two) memcpy(v.data() + tbl[i].offset, hist[i + tbl.size()].data.data(), tbl[i].count * 4);
   }
   if (dqnhip_set_params(h, net, DQNHIP_KIND_M, m.data(), total)) return 1;
-  if (dqnhip_set_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;
+  if (two && dqnhip_set_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;      // (a single-history solver's second arena stays zero)
   int32_t ia = 0, ic = 0;
   if (dqnhip_get_iters(h, &ia, &ic)) return 1;
   if (net == DQNHIP_ACTOR) ia = iter; else ic = iter;

@@ -8,6 +8,7 @@
 #include <zlib.h>
 
 #include <cerrno>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 
@@ -135,6 +136,17 @@ void StreamWriter::abort() {
   remove(tmp_.c_str());
 }
 
+// the SOLV section -> the info's solver fields (a file without one is an Adam learner's: both stay 0)
+static int solver_of(const uint8_t* p, uint64_t bytes, dqnhip_state_info_t* in, const std::string& fn, std::string* err) {
+  SolverSection s;
+  if (bytes != sizeof s) return set(err, fn + ": section SOLV holds " + std::to_string(bytes) + " bytes, expected " + std::to_string(sizeof s));
+  memcpy(&s, p, sizeof s);
+  if (s.solver_type <= DQNHIP_SOLVER_ADAM || s.solver_type > DQNHIP_SOLVER_ADADELTA)
+    return set(err, fn + ": section SOLV names solver " + std::to_string(s.solver_type) + " (an Adam learner writes no SOLV section; the others are 1 .. 5)");
+  in->solver_type = s.solver_type; in->rms_decay = s.rms_decay;
+  return 0;
+}
+
 int read_file(const char* filename, Parsed* out, bool keep, std::string* err) {
   const std::string fn(filename);
   FILE* f = fopen(filename, "rb");
@@ -196,6 +208,8 @@ int read_file(const char* filename, Parsed* out, bool keep, std::string* err) {
     if (rest && fread(out->file.data() + kHeaderTotal + table_bytes, 1, rest, f) != rest) return set(err, fn + ": truncated (short read)");
     for (const Entry& e : out->table)
       if (crc_of(out->file.data() + e.offset, e.bytes) != e.crc) return set(err, fn + ": section " + tag_name(e.tag) + " CRC mismatch");
+    if (const Entry* sv = out->find(kTagSolver))
+      if (solver_of(out->file.data() + sv->offset, sv->bytes, &in, fn, err)) return 1;
   } else {
     std::vector<uint8_t> buf(1 << 20);
     for (const Entry& e : out->table) {                     // (contiguous, in table order: one pass)
@@ -206,6 +220,7 @@ int read_file(const char* filename, Parsed* out, bool keep, std::string* err) {
         c = (uint32_t)crc32(c, buf.data(), (uInt)k); left -= k;
       }
       if (c != e.crc) return set(err, fn + ": section " + tag_name(e.tag) + " CRC mismatch");
+      if (e.tag == kTagSolver && solver_of(buf.data(), e.bytes, &in, fn, err)) return 1;      // (16 bytes: the one piece just read)
     }
   }
   const Entry* u = out->find(kTagUser);
@@ -221,11 +236,16 @@ extern "C" {
 
 int dqnhip_state_info(const char* filename, dqnhip_state_info_t* out) {
   if (!filename || !out) return dqnhip_internal_set_error("dqnhip_state_info: null argument");
-  if (out->struct_size != (int32_t)sizeof(dqnhip_state_info_t))
+  // the struct as it is, or as it was before solver_type / rms_decay were appended (a caller compiled against that header: it gets
+  // the fields it knows, under its own struct_size)
+  const int32_t asked = out->struct_size;
+  const int32_t before_solver = (int32_t)offsetof(dqnhip_state_info_t, solver_type);
+  if (asked != (int32_t)sizeof(dqnhip_state_info_t) && asked != before_solver)
     return dqnhip_internal_set_error(("dqnhip_state_info_t.struct_size " + std::to_string(out->struct_size) + " != " + std::to_string(sizeof(dqnhip_state_info_t)) + " (ABI mismatch)").c_str());
   Parsed p; std::string err;
   if (read_file(filename, &p, false, &err)) return dqnhip_internal_set_error(err.c_str());
-  *out = p.info;
+  memcpy(out, &p.info, (size_t)asked);
+  out->struct_size = asked;
   return 0;
 }
 

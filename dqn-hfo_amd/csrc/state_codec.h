@@ -17,7 +17,7 @@ constexpr uint32_t kMaxSections = 64;
 constexpr uint32_t tag4(char a, char b, char c, char d) {
   return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
 }
-// parameter sections: dense Caffe order (dqnhip_get_params), float32.  WGT<net>, ADM<net> (Adam m), ADV<net> (Adam v)
+// parameter sections: dense Caffe order (dqnhip_get_params), float32.  WGT<net>, ADM<net> (history 1: Adam's m), ADV<net> (history 2: Adam's v)
 constexpr uint32_t kTagW[4] = {tag4('W', 'G', 'T', '0'), tag4('W', 'G', 'T', '1'), tag4('W', 'G', 'T', '2'), tag4('W', 'G', 'T', '3')};
 constexpr uint32_t kTagM[2] = {tag4('A', 'D', 'M', '0'), tag4('A', 'D', 'M', '1')};
 constexpr uint32_t kTagV[2] = {tag4('A', 'D', 'V', '0'), tag4('A', 'D', 'V', '1')};
@@ -25,14 +25,17 @@ constexpr uint32_t kTagDev = tag4('D', 'E', 'V', 'S'), kTagLossScale = tag4('L',
 constexpr uint32_t kTagRing = tag4('R', 'I', 'N', 'G'), kTagStates = tag4('R', 'S', 'T', 'A'), kTagNext = tag4('R', 'N', 'X', 'T'),
                    kTagAct = tag4('R', 'A', 'C', 'T'), kTagReward = tag4('R', 'R', 'E', 'W'), kTagMc = tag4('R', 'M', 'C', 'T'),
                    kTagTerm = tag4('R', 'T', 'R', 'M');
+constexpr uint32_t kTagSolver = tag4('S', 'O', 'L', 'V');      // written by a learner whose solver is not Adam, right behind ADV1
 constexpr uint32_t kTagPerCfg = tag4('P', 'E', 'R', 'C'), kTagPerLeaves = tag4('P', 'E', 'R', 'L'), kTagUser = tag4('U', 'S', 'E', 'R');
 
 // the fixed-size sections, as they lie in the file (little endian, no padding inside)
 struct DevSection { int32_t actor_iter, critic_iter; uint64_t update_counter; float critic_loss, avg_q; int32_t flags, skipped_steps; };
 struct LossScaleSection { float mult[2]; int32_t good[2], backoffs[2], growths[2]; };      // [actor, critic]
 struct HostSection { uint64_t sample_states_calls, seed; };
+struct SolverSection { int32_t solver_type; float rms_decay; int32_t reserved[2]; };
 struct RingSection { int32_t ring_head, ring_size; };
 struct PerSection { float alpha, beta0; int32_t beta_anneal_iters; float eps; uint64_t seed; float p_max; int32_t reserved; int64_t syncs; };
+static_assert(sizeof(SolverSection) == 16, "SOLV is 16 bytes");
 static_assert(sizeof(DevSection) == 32 && sizeof(LossScaleSection) == 32 && sizeof(HostSection) == 16 && sizeof(RingSection) == 8 &&
               sizeof(PerSection) == 40, "the sections have no padding");
 

@@ -86,7 +86,7 @@ class DQN:
                  device=0, dp_world=1, dp_rank=0, use_graph=False, stream=None, grad_arena=None,
                  grad_arena_bytes=0, tid=0, save_path="state/dqn", precision="fp32", loss_scale=0.0, tuning=0,
                  loss_scale_mode="static", loss_scale_growth_interval=None, loss_scale_min_mult=None, loss_scale_max_mult=None,
-                 act_precision="fp32"):
+                 act_precision="fp32", solver="Adam", rms_decay=0.99, delta=None):
         self.lib = capi.load()
         cfg = capi.Config()
         self.lib.dqnhip_default_config(C.byref(cfg), state_size)
@@ -115,6 +115,12 @@ class DQN:
             cfg.loss_scale_min_mult = loss_scale_min_mult
         if loss_scale_max_mult is not None:
             cfg.loss_scale_max_mult = loss_scale_max_mult
+        # Caffe's solver type string (the reference driver's -solver); AdaGrad and RMSProp need momentum=0, as in Caffe
+        if solver not in capi.SOLVERS:
+            raise DQNFatal("Unknown solver type: %s (known types: %s)" % (solver, ", ".join(capi.SOLVERS)))
+        cfg.solver_type, cfg.rms_decay = capi.SOLVERS.index(solver), rms_decay
+        if delta is not None:
+            cfg.delta = delta
         self.cfg = cfg
         self.h = capi.H()
         self._ck(self.lib.dqnhip_create(C.byref(cfg), C.byref(self.h)))
@@ -150,6 +156,11 @@ class DQN:
         for i, hsz in enumerate(hidden):
             cfg.hidden[i] = hsz
         return lib.dqnhip_grad_arena_bytes(C.byref(cfg))
+
+    @property
+    def solver(self):
+        """Caffe's type string of this learner's solver (dqnhip_solver_name)."""
+        return self.lib.dqnhip_solver_name(self.cfg.solver_type).decode()
 
     def _ck(self, rc):
         if rc != 0:
@@ -626,6 +637,10 @@ class DQN:
             out = np.empty(B * width, np.float32)
             self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
             return out.reshape(B, width)
+        if name == "optimiser_launches":      # host counters [k_adam_soft*, k_solver_soft<>, k_solver_soft_gather<>], enqueued or captured
+            out = np.zeros(3, np.float32)
+            self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
+            return out.astype(np.int64)
         wide = name in ("actor_out", "dq_da", "actor_target_out", "dxc")
         out = np.empty(B * (10 if wide else 1), np.float32)
         self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
@@ -649,7 +664,7 @@ class DQN:
         self._ck(self.lib.dqnhip_get_update_plan(self.h, C.byref(p)))
         return {"forms": [n for i, n in enumerate(capi.PLAN_FORMS) if p.forms >> i & 1], "launches_single": p.launches_single,
                 "launches_graph_first": p.launches_graph_first, "launches_in_graph": p.launches_in_graph,
-                "updates_per_graph": p.updates_per_graph, "collectives": p.collectives}
+                "updates_per_graph": p.updates_per_graph, "collectives": p.collectives, "solver": capi.SOLVERS[p.solver_type]}
 
     # -- update diagnostics (include/dqnhip.h: Caffe's debug_info, reduced on the device; opt-in) --------------
     def diag_collect_raw(self):

@@ -53,13 +53,38 @@ enum dqnhip_net {
   DQNHIP_CRITIC_TARGET = 3  /* critic_target_net_  src/dqn.hpp:192 */
 };
 
-/* which per-parameter array: data, or Adam history (Caffe SolverState
- * history = [m_0..m_P-1, v_0..v_P-1]), or last gradient */
+/* which per-parameter array: data, or solver history (Caffe SolverState
+ * history = [h1_0..h1_P-1, h2_0..h2_P-1]), or last gradient.
+ * KIND_M is history 1 (Adam's m; the momentum / accumulated-square history of the other solvers), KIND_V is history 2
+ * (Adam's v, AdaDelta's update history; all zero and never touched under SGD, Nesterov, AdaGrad and RMSProp). */
 enum dqnhip_param_kind {
   DQNHIP_KIND_W = 0,
-  DQNHIP_KIND_M = 1,
-  DQNHIP_KIND_V = 2,
+  DQNHIP_KIND_M = 1,        /* history 1 */
+  DQNHIP_KIND_V = 2,        /* history 2 */
   DQNHIP_KIND_G = 3
+};
+
+/* dqnhip_config.solver_type: Caffe's solvers (SolverParameter.type, the reference driver's -solver flag: src/dqn_main.cpp:30,
+ * src/dqn.cpp:628-629).  0 — what a zero-filled field means — is Adam, the reference's default.  One type for both nets.
+ * With gs = g * clip_scale (SGDSolver::ClipGradients), lr = actor_lr / critic_lr, mom = momentum, d = delta, rho = rms_decay,
+ * float32 in this order (no bias correction, no use of the iteration):
+ *   SGD       h1 = fmaf(lr, gs, mom*h0);  w1 = w0 - h1
+ *   Nesterov  h1 = fmaf(lr, gs, mom*h0);  u = fmaf(1 + mom, h1, -(mom*h0));  w1 = w0 - u
+ *   AdaGrad   h1 = fmaf(gs, gs, h0);  w1 = w0 - lr * (gs / (sqrtf(h1) + d))                      needs momentum == 0
+ *   RMSProp   h1 = fmaf(1 - rho, gs*gs, rho*h0);  w1 = w0 - lr * (gs / (sqrtf(h1) + d))          needs momentum == 0, 0 <= rho < 1
+ *   AdaDelta  h1 = fmaf(1 - mom, gs*gs, mom*h0);  u = gs * sqrtf((h2_0 + d) / (h1 + d));
+ *             h2_1 = fmaf(1 - mom, u*u, mom*h2_0);  w1 = w0 - lr*u
+ * The soft target update, the skipped step on a non-finite norm and loss scaling are the Adam learner's.
+ * v1 limits of the five: no data parallelism (dp_world > 1, dqnhip_dp_init*, dqnhip_apply_update_sharded), no dqnhip_diag_collect,
+ * no first-layer riders in the optimiser launches (the schedule is the one DQNHIP_TUNE_SEPARATE_FIRST_LAYER |
+ * DQNHIP_TUNE_LATE_GATHER give an Adam learner). */
+enum dqnhip_solver {
+  DQNHIP_SOLVER_ADAM = 0,
+  DQNHIP_SOLVER_SGD = 1,
+  DQNHIP_SOLVER_NESTEROV = 2,
+  DQNHIP_SOLVER_ADAGRAD = 3,
+  DQNHIP_SOLVER_RMSPROP = 4,
+  DQNHIP_SOLVER_ADADELTA = 5
 };
 
 /* Learner configuration.  Defaults in comments are the reference's.
@@ -85,9 +110,11 @@ typedef struct dqnhip_config {
   double tau;                /* FLAGS_tau   (.001); applied as float          */
   float actor_lr;            /* FLAGS_actor_lr  (1e-5)                        */
   float critic_lr;           /* FLAGS_critic_lr (1e-3)                        */
-  float momentum;            /* Adam beta1, FLAGS_momentum  (.95)             */
-  float momentum2;           /* Adam beta2, FLAGS_momentum2 (.999)            */
-  float delta;               /* Adam eps, Caffe SolverParameter.delta (1e-8)  */
+  float momentum;            /* FLAGS_momentum (.95): Adam beta1; SGD / Nesterov momentum; AdaDelta decay;
+                                must be 0 for AdaGrad and RMSProp               */
+  float momentum2;           /* FLAGS_momentum2 (.999): Adam beta2; read by no other solver */
+  float delta;               /* Caffe SolverParameter.delta (1e-8): Adam eps; AdaGrad / RMSProp: added to the root;
+                                AdaDelta: inside both roots; SGD / Nesterov: not read */
   float clip_gradients;      /* FLAGS_clip_grad (10); < 0 disables            */
   int32_t device;            /* HIP device ordinal                            */
   int32_t dp_world;          /* data-parallel world size (1 = single GPU)     */
@@ -111,6 +138,11 @@ typedef struct dqnhip_config {
                                 norm non-finite: the step is skipped and the next
                                 dqnhip_read_stats fails ("Gradient norm not finite") —
                                 unless loss_scale_mode is dynamic.                     */
+  int32_t solver_type;       /* FLAGS_solver: DQNHIP_SOLVER_* (0 = Adam, the default, and what a zero-filled field means) */
+  float rms_decay;           /* RMSProp's decay, Caffe SolverParameter.rms_decay (.99); read by no other solver.
+                                Every field above these two keeps the offset it had before they existed — a caller compiled
+                                against that header and run on this library (which fills the struct through
+                                dqnhip_default_config) still sets what it means to set; from here on the offsets grew by 8. */
   int32_t tuning_flags;      /* DQNHIP_TUNE_* bits: A/B switches that select an alternative
                                 SCHEDULE of the same arithmetic (0 = the measured winners).
                                 The library reads no environment variable; every bit has a
@@ -176,6 +208,9 @@ typedef struct dqnhip_learner* dqnhip_handle;
 /* Fill *cfg with the reference defaults (B=32, tower 1024-512-256-128, replay
  * 500k, gamma .99, beta .5, tau .001, Adam .95/.999, lr 1e-5/1e-3, clip 10). */
 void dqnhip_default_config(dqnhip_config* cfg, int32_t state_size);
+
+/* Caffe's type string of a DQNHIP_SOLVER_* value ("Adam", "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta"); NULL: no such solver. */
+const char* dqnhip_solver_name(int32_t solver_type);
 
 /* Bytes the caller must provide in cfg->grad_arena (0 on invalid config). */
 size_t dqnhip_grad_arena_bytes(const dqnhip_config* cfg);
@@ -332,7 +367,7 @@ typedef struct dqnhip_update_plan {
   int32_t launches_in_graph;    /* ... of every later update of such a graph */
   int32_t updates_per_graph;    /* 16 */
   int32_t collectives;          /* RCCL calls per update once a communicator is up (not counted in launches_*), else 0 */
-  int32_t reserved;
+  int32_t solver_type;          /* DQNHIP_SOLVER_* of the learner (0 = Adam; this word was reserved, always 0, before the other solvers existed) */
 } dqnhip_update_plan;
 /* Fails while a phased update is in progress or kernel timing is on; launches_* are 0 for a sharded optimiser (its
  * sequence contains collectives and is not captured here). */
@@ -618,6 +653,8 @@ int dqnhip_remove_snapshots(const char* regexp, int32_t min_iter);
  * "indexed_graph_launches" [1]: the kernel nodes of the sixteen-update graph dqnhip_update_indexed_n has captured (0: none
  * captured, or dropped since - sharing, set-up of data parallelism); a buffer of 5 floats or more also gets those of the eight-,
  * four-, two- and one-update graphs in [1] .. [4].
+ * "optimiser_launches" [3]: host counters of the optimiser launches this learner has enqueued or captured (the captures of
+ * dqnhip_get_update_plan included): Adam's kernels (k_adam_soft*), k_solver_soft<>, k_solver_soft_gather<>.
  * What the head layers hand on, for per-element tests between the phases of dqnhip_update_phase:
  * "dq" [B]: Step(1)'s loss diff (q - y) / B, valid after phase 0;
  * "actor_target_out" [B,10]: mu'(s'), valid after phase 0;
@@ -827,6 +864,10 @@ int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t
  * slot (ring_head + i) % capacity, the tree restored to the saved learner's bits at every level (a prioritized learner also adopts
  * the file's beta0, beta_anneal_iters, eps and sampler seed), captured graphs dropped.
  *
+ * Solver: a learner whose solver is not Adam writes a 16-byte SOLV section (solver_type, rms_decay) behind the history sections, an
+ * Adam learner writes none (its file is what it was before the other solvers existed); dqnhip_load_state refuses a file whose solver
+ * is not the learner's, in either direction, before it touches the learner.  ADM<net> / ADV<net> carry history 1 / history 2.
+ *
  * v1 refuses, in both calls: a learner in any sharing relationship (parameters or replay memory, either role), dp_world > 1 or a
  * live communicator, a phased update in progress, kernel timing on.  Env front-end handles attached to a learner that loads see
  * what they see after dqnhip_load_replay_memory: the ring changed under them, their open episodes continue on it. */
@@ -836,10 +877,12 @@ int dqnhip_save_state(dqnhip_handle h, const char* filename, int32_t flags,
 int dqnhip_load_state(dqnhip_handle h, const char* filename);
 /* host only, needs no GPU */
 typedef struct dqnhip_state_info {
-  int32_t struct_size;       /* in: sizeof(dqnhip_state_info_t) */
+  int32_t struct_size;       /* in: sizeof(dqnhip_state_info_t) (or its size before solver_type / rms_decay were appended: that much is filled) */
   int32_t version, flags, precision, minibatch, state_size, num_hidden, hidden[DQNHIP_MAX_HIDDEN], replay_capacity, memory_size,
       actor_iter, critic_iter, has_memory, has_per, has_loss_scale;
   uint64_t seed, update_counter, user_bytes, file_bytes;
+  int32_t solver_type;       /* DQNHIP_SOLVER_* of the learner that wrote the file (0 = Adam: a file without a SOLV section) */
+  float rms_decay;           /* ... and its rms_decay (0 in an Adam learner's file: it is not stored there) */
 } dqnhip_state_info_t;       /* (the type carries _t: in C a typedef and a function cannot share a name) */
 /* Validates the whole file (every CRC) as dqnhip_load_state does, and reports the header. */
 int dqnhip_state_info(const char* filename, dqnhip_state_info_t* out);

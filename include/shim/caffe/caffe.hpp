@@ -109,6 +109,7 @@ class SolverParameter {
   DQNHIP_SHIM_FIELD(float, momentum, 0.0f)
   DQNHIP_SHIM_FIELD(float, momentum2, 0.999f)          // caffe.proto defaults
   DQNHIP_SHIM_FIELD(float, delta, 1e-8f)
+  DQNHIP_SHIM_FIELD(float, rms_decay, 0.99f)           // (RMSProp)
   DQNHIP_SHIM_FIELD(float, clip_gradients, -1.0f)
 #undef DQNHIP_SHIM_FIELD
  private:
