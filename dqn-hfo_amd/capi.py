@@ -198,6 +198,9 @@ SIGNATURES = {
     "dqnhip_solver_snapshot": (C.c_int, [H, C.c_int32, C.c_char_p, ip]),
     "dqnhip_solver_restore": (C.c_int, [H, C.c_int32, C.c_char_p]),
     "dqnhip_snapshot": (C.c_int, [H, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32]),
+    "dqnhip_snapshot_async": (C.c_int, [H, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dqnhip_snapshot_wait": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "dqnhip_snapshot_poll": (C.c_int, [H, C.POINTER(C.c_int32)]),
     "dqnhip_find_latest_snapshot": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "dqnhip_find_hiscore": (C.c_int, [C.c_char_p, ip]),
     "dqnhip_remove_files_matching_regexp": (C.c_int, [C.c_char_p]),

@@ -70,6 +70,12 @@ DEFINE_bool(native_state, false, "Snapshot() additionally writes <prefix>_iter_<
 DEFINE_bool(native_state_async, false, "-native_state: the learner state is written behind training (dqnhip_save_state_async: frozen on the device at the "
             "snapshot, written by a writer thread). The save is joined - and older .learnerstate files removed - at the next learner-state "
             "snapshot, at a restore and when the learner is destroyed; a failed save aborts there. Same file, byte for byte.");
+DEFINE_bool(snapshot_async, false, "Snapshot() writes the Caffe snapshot's files behind training (dqnhip_snapshot_async: frozen on the device at the snapshot, "
+            "built and compressed by the learner's writer thread and -snapshot_async_threads compressor threads; same names, same protobuf bytes, "
+            "same decompressed replay memory). The snapshot is joined - \"Snapshotting Finished!\" - before the next snapshot, before a restore or "
+            "load and when the learner is destroyed; a failed snapshot aborts there. Where the library refuses (shared or data-parallel "
+            "learners), the snapshot is taken synchronously.");
+DEFINE_int32(snapshot_async_threads, 0, "-snapshot_async: compressor threads for the replay memory (0: the library's default, 8).");
 DEFINE_bool(native_state_only_memory, false, "-native_state: a snapshot that is asked for the replay memory writes no gzip .replaymemory; the learner-state "
             "file is the memory's only copy and restores it on resume.");
 DEFINE_bool(device_sampling, false, "Sample minibatch indices on the device (counter-based) instead of the host std::mt19937.");
@@ -383,7 +389,7 @@ void DQN::RearmReplicaSync(const char* what) {
   dp_sync_pending_ = true;
 }
 
-DQN::~DQN() { CollectDeferred(); JoinNativeState(); DQNHIP_CK(dqnhip_destroy(h_)); }
+DQN::~DQN() { CollectDeferred(); JoinSnapshot(); JoinNativeState(); DQNHIP_CK(dqnhip_destroy(h_)); }
 
 // ---- -deferred_updates ------------------------------------------------------------------------------------------------------
 // The driver calls Update() in bursts and discards the result (src/dqn_main.cpp:340-343, 359-361; Update() is void, src/dqn.hpp:103):
@@ -451,15 +457,16 @@ void DQN::Benchmark(int iterations) {
   LOG(INFO) << "*** Benchmark ends ***";
 }
 
-void DQN::RestoreActorSolver(const std::string& f) { CollectDeferred(); RearmReplicaSync("RestoreActorSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_ACTOR, f.c_str())); last_snapshot_iter_ = max_iter(); }
+void DQN::RestoreActorSolver(const std::string& f) { CollectDeferred(); JoinSnapshot(); RearmReplicaSync("RestoreActorSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_ACTOR, f.c_str())); last_snapshot_iter_ = max_iter(); }
 void DQN::RestoreCriticSolver(const std::string& f) {
-  CollectDeferred(); RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter();
+  CollectDeferred(); JoinSnapshot(); RearmReplicaSync("RestoreCriticSolver"); DQNHIP_CK(dqnhip_solver_restore(h_, DQNHIP_CRITIC, f.c_str())); last_snapshot_iter_ = max_iter();
   if (FLAGS_native_state) LoadNativeState(f);      // (the later of the driver's two restore calls, src/dqn_main.cpp:268-275)
 }
-void DQN::LoadActorWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadActorWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_ACTOR, f.c_str())); }
-void DQN::LoadCriticWeights(const std::string& f) { CollectDeferred(); RearmReplicaSync("LoadCriticWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_CRITIC, f.c_str())); }
+void DQN::LoadActorWeights(const std::string& f) { CollectDeferred(); JoinSnapshot(); RearmReplicaSync("LoadActorWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_ACTOR, f.c_str())); }
+void DQN::LoadCriticWeights(const std::string& f) { CollectDeferred(); JoinSnapshot(); RearmReplicaSync("LoadCriticWeights"); DQNHIP_CK(dqnhip_load_caffemodel(h_, DQNHIP_CRITIC, f.c_str())); }
 void DQN::LoadReplayMemory(const std::string& f) {
   SubmitPending();
+  JoinSnapshot();
   if (FLAGS_native_state && native_has_memory_) {
     // <stem>_iter_<N>.replaymemory of the prefix the learner state came from: loading it would put logical 0 back at slot 0 and reset the priorities
     const std::string head = native_stem_ + "_iter_", tail = ".replaymemory";
@@ -473,16 +480,33 @@ void DQN::LoadReplayMemory(const std::string& f) {
   DQNHIP_CK(dqnhip_load_replay_memory(h_, f.c_str()));
   LOG(INFO) << "replay_mem_size = " << memory_size();
 }
-void DQN::SnapshotReplayMemory(const std::string& f) { SubmitPending(); DQNHIP_CK(dqnhip_snapshot_replay_memory(h_, f.c_str())); }
+void DQN::SnapshotReplayMemory(const std::string& f) { SubmitPending(); JoinSnapshot(); DQNHIP_CK(dqnhip_snapshot_replay_memory(h_, f.c_str())); }
 
 void DQN::Snapshot() { Snapshot(save_path_, FLAGS_remove_old_snapshots, FLAGS_snapshot_memory); }
 void DQN::Snapshot(const std::string& snapshot_prefix, bool remove_old, bool snapshot_memory) {
   SubmitPending();
+  JoinSnapshot();                                    // (-snapshot_async: the previous snapshot's "Snapshotting Finished!" comes before this one's lines)
   // -native_state_only_memory: the learner-state file below carries the memory (a data-parallel learner writes none: it keeps the gzip file)
   const bool gzip_memory = snapshot_memory && !(FLAGS_native_state_only_memory && !dp_);
   if (gzip_memory) LOG(INFO) << "Snapshotting memory to " << snapshot_prefix << "_iter_" << max_iter() << ".replaymemory";
+  if (FLAGS_snapshot_async) {
+    if (dqnhip_snapshot_async(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, gzip_memory, FLAGS_snapshot_async_threads) == 0) {
+      snapshot_in_flight_ = true;                    // ("Snapshotting Finished!" is printed when the snapshot is joined)
+      if (FLAGS_native_state) SaveNativeState(snapshot_prefix, remove_old, snapshot_memory);
+      return;
+    }
+    LOG(WARNING) << "[Agent" << tid_ << "] -snapshot_async: " << dqnhip_last_error() << "; this snapshot is taken synchronously";
+  }
   DQNHIP_CK(dqnhip_snapshot(h_, save_path_.c_str(), snapshot_prefix.c_str(), remove_old, gzip_memory));
   if (FLAGS_native_state) SaveNativeState(snapshot_prefix, remove_old, snapshot_memory);
+  LOG(INFO) << "Snapshotting Finished!";
+}
+
+// -snapshot_async: waits for the snapshot in flight (a failure aborts, as a failed synchronous snapshot does)
+void DQN::JoinSnapshot() {
+  if (!snapshot_in_flight_) return;
+  snapshot_in_flight_ = false;
+  DQNHIP_CK(dqnhip_snapshot_wait(h_, nullptr, nullptr));
   LOG(INFO) << "Snapshotting Finished!";
 }
 

@@ -9,12 +9,15 @@
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
-//                       introspection, update diagnostics (dqnhip_diag_collect), the launches of the asynchronous state save
+//                       introspection, update diagnostics (dqnhip_diag_collect), the launches of the asynchronous state save and of the
+//                       asynchronous Caffe snapshot (snapshot_kernels.hip.h)
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state, and the host side of
-//                       dqnhip_save_state_async (its writer thread; the kernels are launched from learner_io.hip); host only
-//   snapshot.cpp        Caffe snapshot layout (no device code)
+//                       dqnhip_save_state_async and dqnhip_snapshot_async (the writer thread they share; the kernels are launched
+//                       from learner_io.hip); host only
+//   snapshot.cpp        Caffe snapshot layout (no device code); snapshot_codec.h: its builders on host pointers, for the writer thread
 //   state_codec.cpp     the learner-state file's container (header, table, CRCs), dqnhip_state_info / _read_user (no device code, no HIP)
+//   gzip_parallel.cpp   one gzip member from chunks deflated by a pool of threads: the asynchronous snapshot's .replaymemory (no HIP)
 // This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
 // of the kernels it launches and embeds exactly those (tests/test_kernel_inventory.py), the host-only units embed no device code.
 // A launch attribute (hipFuncSetAttribute) of a kernel with internal linkage holds for the calling unit's copy only: it is set in
@@ -133,7 +136,7 @@ struct PerHost {
   long long syncs = 0;                  // k_per_sync launches so far
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
-struct StateAsync;                      // asynchronous learner-state save (learner_state.hip; the kernels: state_kernels.hip.h)
+struct StateAsync;                      // asynchronous learner-state save and Caffe snapshot (learner_state.hip; the kernels: state_kernels.hip.h, snapshot_kernels.hip.h)
 
 }  // namespace dqnhip_host
 
@@ -283,7 +286,7 @@ struct dqnhip_learner {
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
   DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
-  StateAsync* sasync = nullptr;         // dqnhip_save_state_async: staging buffer, pinned ring, writer thread; allocated by the first such save
+  StateAsync* sasync = nullptr;         // dqnhip_save_state_async / dqnhip_snapshot_async: the writer thread, the pinned ring and each kind's staging buffer, allocated at first use
 };
 
 namespace dqnhip_host {
@@ -438,6 +441,9 @@ int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a);
 int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a);
 // ... and its host side (learner_state.hip)
 int state_async_join(H* h, const char* what);            // waits for a save in flight; fails, as `what`, with its message if it failed
-void state_async_free(H* h);                             // dqnhip_destroy: joins, stops the writer thread, frees; never fails
+void state_async_free(H* h);                             // dqnhip_destroy: joins both kinds of job, stops the writer thread, frees; never fails
+// asynchronous Caffe snapshot (dqnhip_snapshot_async): the launcher of snapshot_kernels.hip.h (learner_io.hip), the join (learner_state.hip)
+int snap_pack_replay_launch(H* h, uint8_t* stream_dev);
+int snapshot_async_join(H* h, const char* what);         // waits for a snapshot in flight; fails, as `what`, with its message if it failed
 
 }  // namespace dqnhip_host

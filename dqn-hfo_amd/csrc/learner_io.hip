@@ -6,6 +6,7 @@
 #include "per_kernels.hip.h"
 #include "diag_kernels.hip.h"
 #include "state_kernels.hip.h"
+#include "snapshot_kernels.hip.h"
 
 using namespace dqnhip;
 using namespace dqnhip_host;
@@ -344,6 +345,7 @@ int dqnhip_reduce_gradients_local(dqnhip_handle* hs, int32_t n, int32_t net) {
 // ---- .replaymemory files (src/dqn.cpp:1146-1226) --------------------------------------------
 int dqnhip_snapshot_replay_memory(dqnhip_handle h, const char* filename) {
   if (!h || !filename) return fail("null argument");
+  RC(snapshot_async_join(h, "dqnhip_snapshot_replay_memory"));
   HIPCHK(hipSetDevice(h->cfg.device));
   // one RingUse for the whole file: with a shared ring another agent's AddTransitions must not
   // move the head between chunks (the file would hold shifted / duplicated transitions)
@@ -378,6 +380,7 @@ int dqnhip_snapshot_replay_memory(dqnhip_handle h, const char* filename) {
 
 int dqnhip_load_replay_memory(dqnhip_handle h, const char* filename) {
   if (!h || !filename) return fail("null argument");
+  RC(snapshot_async_join(h, "dqnhip_load_replay_memory"));
   RO(h)->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   gzFile f = gzopen(filename, "rb");
@@ -1151,6 +1154,22 @@ int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a) {
   if (a.n < 1 || a.n > dqnhip_state::kMaxCrcSections) return fail("state_crc_launch: bad arguments");
   if (a.total_chunks == 0) return 0;
   HIPCHK(launch(h->stream, k_state_crc, dim3((a.total_chunks + 255) / 256), dim3(256), 0, a));
+  return 0;
+}
+// asynchronous Caffe snapshot (snapshot_kernels.hip.h): the ring's window as the `.replaymemory` stream at `stream_dev`, which has
+// room for the stream of a full ring and, behind that (rounded up to a dword), the guard band this call fills and nothing else writes.
+// The stream's first record (stream_dev + 4) lies on a 16-byte boundary.  64 records per workgroup measured fastest
+// (profiles/snapshot_async_ab.md); fewer where the state is so long that 64 rows do not fit the LDS a launch gets without asking
+int snap_pack_replay_launch(H* h, uint8_t* stream_dev) {
+  const uint64_t max_dwords = dqnhip_snap::stream_dwords(h->S, (uint64_t)h->ring.cap);
+  const size_t row_bytes = (size_t)dqnhip_snap::snap_lds_row_words(h->S) * sizeof(uint32_t);
+  int K = 64;
+  while (K > 16 && K * row_bytes > 48 * 1024) K /= 2;
+  if (K * row_bytes > 48 * 1024) return fail("the asynchronous snapshot's pack kernel stages 16 records of %zu bytes in LDS: too long a state (S = %d)", row_bytes, h->S);
+  if ((uintptr_t)(stream_dev + 4) % 16 != 0 || h->ring.cap < 1) return fail("snap_pack_replay_launch: bad arguments");
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(stream_dev + 4 * max_dwords), (int)dqnhip_snap::kGuardWord, dqnhip_snap::kGuardWords, h->stream));
+  HIPCHK(launch(h->stream, k_snap_pack_replay, dim3((unsigned)((h->ring.cap + K - 1) / K)), dim3(256), K * row_bytes, h->ring, (const DevState*)h->st,
+                (uint32_t*)stream_dev, max_dwords, K));
   return 0;
 }
 

@@ -4,10 +4,16 @@
 // dqnhip_save_state_async: the same file behind training.  The caller's thread enqueues the pack and the chunk CRCs on the learner's
 // stream (state_kernels.hip.h, launched from learner_io.hip) and hands a job to the learner's writer thread, which waits for the
 // event, folds the CRCs, and streams the staging buffer to the file through two pinned chunks.
+// dqnhip_snapshot_async: the Caffe snapshot's files behind training, a second kind of job for the same writer thread.  The caller's
+// thread enqueues the parameter pack, the `.replaymemory` stream (snapshot_kernels.hip.h) and its CRC into a staging buffer of the
+// snapshot's own; the writer builds the protobuf files with snapshot.cpp's builders and hands the stream to GzipParallelWriter.
 #include <condition_variable>
 #include <memory>
 
 #include "learner_internal.hip.h"
+#include "gzip_parallel.h"
+#include "snapshot_codec.h"
+#include "snapshot_stream.h"
 #include "state_codec.h"
 
 using namespace dqnhip_state;
@@ -62,12 +68,41 @@ struct StateJob {
   int device = 0, cap = 0;
 };
 
-struct StateAsync {
-  // device side, allocated by the first asynchronous save and kept until dqnhip_destroy
+// what one asynchronous snapshot needs besides its staging buffer
+struct SnapJob {
+  std::string save_path, prefix;
+  bool remove_old = false, with_mem = false, two = false;   // two: the solver keeps a second history set
+  int workers = 8;
+  dqnhip_config cfg{};
+  int device = 0, cap = 0, S = 0;
+};
+constexpr int kSnapPar = 6;              // W actor, W critic, history 1 / 2 of the actor, history 1 / 2 of the critic
+struct SnapAsync {
+  // device side, allocated by the first asynchronous snapshot and kept until dqnhip_destroy: the snapshot's own staging buffer
   uint8_t* stage = nullptr; size_t stage_bytes = 0;
+  hipEvent_t ev = nullptr;
+  // its map: the record, the segment table, the chunk CRCs of the records, the dense parameters, the stream (its records start on a
+  // 16-byte boundary: the count sits in the 4 bytes before one), the guard band behind the stream's upper bound
+  size_t off_rec = 0, off_segs = 0, off_crc = 0, off_par[kSnapPar] = {0}, off_stream = 0, off_guard = 0;
+  size_t par_bytes[kSnapPar] = {0};
+  int n_seg = 0;
+  std::vector<PackSeg> segs;
+  SnapJob job;
+  int32_t actor_iter = 0, critic_iter = 0;       // of the last job that wrote its files
+};
+
+enum JobKind { kJobState = 0, kJobSnapshot = 1, kJobKinds = 2 };
+const char* const kJobWhat[kJobKinds] = {"save", "snapshot"};
+
+struct StateAsync {
+  // the learner-state save's device side, allocated by the first asynchronous save and kept until dqnhip_destroy (null: this learner
+  // has only snapshotted asynchronously)
+  uint8_t* stage = nullptr; size_t stage_bytes = 0;
+  hipEvent_t ev = nullptr;
+  // what both kinds of job share, allocated with the writer thread by whichever comes first
   uint8_t* pinned = nullptr;
   hipStream_t copy_stream = nullptr;
-  hipEvent_t ev = nullptr;
+  SnapAsync* snap = nullptr;             // dqnhip_snapshot_async's side, allocated by the first asynchronous snapshot
   // the staging buffer's map (byte offsets, every section on a 16-byte boundary)
   size_t off_rec = 0, off_segs = 0, off_crc = 0, off_par[8] = {0}, off_ring[kRingArrays] = {0};
   size_t par_bytes[8] = {0};
@@ -80,9 +115,11 @@ struct StateAsync {
   std::thread th;
   std::mutex mu;
   std::condition_variable cv;
-  bool pending = false, busy = false, quit = false;   // pending: a job waits for the thread; busy: a save is in flight
+  std::deque<int> queue;                 // the kinds of the jobs that wait for the thread, first in first out
+  bool busy[kJobKinds] = {false, false}; // a job of this kind is in flight (waiting or being written): at most one of each
+  bool quit = false;
   StateJob job;
-  bool failed = false; std::string err;  // of the last finished save, until a join reports it
+  bool failed[kJobKinds] = {false, false}; std::string err[kJobKinds];   // of the last finished job of each kind, until a join reports it
 };
 
 }  // namespace dqnhip_host
@@ -92,27 +129,28 @@ namespace {
 std::string hip_msg(const char* what, hipError_t e) { return std::string(what) + " failed: " + hipGetErrorString(e); }
 #define WCHK(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { *err = hip_msg(#expr, e__); return 1; } } while (0)
 
-// bytes [off, off + bytes) of the staging buffer -> dst (host memory of any kind), through the pinned ring
-int fetch_dev(StateAsync* a, size_t off, size_t bytes, void* dst, std::string* err) {
+// `bytes` bytes of a staging buffer at src -> dst (host memory of any kind), through the pinned ring
+int fetch_dev(StateAsync* a, const uint8_t* src, size_t bytes, void* dst, std::string* err) {
   for (size_t done = 0; done < bytes;) {
     const size_t k = std::min(bytes - done, kPinnedChunk);
-    WCHK(hipMemcpyAsync(a->pinned, a->stage + off + done, k, hipMemcpyDeviceToHost, a->copy_stream));
+    WCHK(hipMemcpyAsync(a->pinned, src + done, k, hipMemcpyDeviceToHost, a->copy_stream));
     WCHK(hipStreamSynchronize(a->copy_stream));
     memcpy((char*)dst + done, a->pinned, k);
     done += k;
   }
   return 0;
 }
-// ... -> the file: the copy of chunk k + 1 runs while chunk k is written
-int stream_dev(StateAsync* a, size_t off, size_t bytes, StreamWriter* w, std::string* err) {
+// ... -> the file (StreamWriter, GzipParallelWriter): the copy of chunk k + 1 runs while chunk k is written
+template <class Writer>
+int stream_dev(StateAsync* a, const uint8_t* src, size_t bytes, Writer* w, std::string* err) {
   if (!bytes) return 0;
   int b = 0;
   size_t k = std::min(bytes, kPinnedChunk);
-  WCHK(hipMemcpyAsync(a->pinned, a->stage + off, k, hipMemcpyDeviceToHost, a->copy_stream));
+  WCHK(hipMemcpyAsync(a->pinned, src, k, hipMemcpyDeviceToHost, a->copy_stream));
   for (size_t done = 0; done < bytes;) {
     WCHK(hipStreamSynchronize(a->copy_stream));
     const size_t next = done + k, k_next = std::min(bytes - next, kPinnedChunk);
-    if (k_next) WCHK(hipMemcpyAsync(a->pinned + (size_t)(b ^ 1) * kPinnedChunk, a->stage + off + next, k_next, hipMemcpyDeviceToHost, a->copy_stream));
+    if (k_next) WCHK(hipMemcpyAsync(a->pinned + (size_t)(b ^ 1) * kPinnedChunk, src + next, k_next, hipMemcpyDeviceToHost, a->copy_stream));
     if (w->append(a->pinned + (size_t)b * kPinnedChunk, k, err)) return 1;
     done = next; k = k_next; b ^= 1;
   }
@@ -127,7 +165,7 @@ int write_job(StateAsync* a, std::string* err) {
   // (the copy stream already waits for the save's event — dqnhip_save_state_async enqueued that wait: every copy below is behind the
   // pack and the CRC, and this thread touches neither the learner's stream nor an event recorded on it, which may be capturing by now)
   StateRec rec{};
-  if (fetch_dev(a, a->off_rec, sizeof rec, &rec, err)) return 1;
+  if (fetch_dev(a, a->stage + a->off_rec, sizeof rec, &rec, err)) return 1;
   const int head = rec.ring_head, size = rec.ring_size;
   if (j.with_mem && (head < 0 || head >= j.cap || size < 0 || size > j.cap)) {
     *err = "the ring's (head, size) = (" + std::to_string(head) + ", " + std::to_string(size) + ") is outside its capacity " + std::to_string(j.cap);
@@ -142,7 +180,7 @@ int write_job(StateAsync* a, std::string* err) {
     const uint64_t bytes = c.row_bytes ? (uint64_t)size * c.row_bytes : c.fixed_bytes;
     const size_t chunks = (size_t)((bytes + kCrcChunk - 1) / kCrcChunk);
     raws.resize(chunks);
-    if (fetch_dev(a, a->off_crc + (size_t)c.chunk0 * sizeof(uint32_t), chunks * sizeof(uint32_t), raws.data(), err)) return 1;
+    if (fetch_dev(a, a->stage + a->off_crc + (size_t)c.chunk0 * sizeof(uint32_t), chunks * sizeof(uint32_t), raws.data(), err)) return 1;
     dev.push_back({(size_t)c.off, bytes, crc_fold_chunks(raws.data(), bytes, a->chunk_tab)});
   }
   // the host-built sections
@@ -178,10 +216,69 @@ int write_job(StateAsync* a, std::string* err) {
   StreamWriter w;
   if (w.open(j.filename.c_str(), info, entries, err)) return 1;
   for (const Out& o : out) {
-    if (o.dev_ix >= 0) { if (stream_dev(a, dev[o.dev_ix].off, (size_t)dev[o.dev_ix].bytes, &w, err)) return 1; }
+    if (o.dev_ix >= 0) { if (stream_dev(a, a->stage + dev[o.dev_ix].off, (size_t)dev[o.dev_ix].bytes, &w, err)) return 1; }
     else if (w.append(o.host, o.bytes, err)) return 1;
   }
   return w.finish(err);
+}
+
+// The writer thread's share of one asynchronous snapshot, under the same rule: the snapshot's staging buffer, its job and its
+// launch's CrcArgs are all it reads.  Order and names are dqnhip_snapshot's; every file appears under a name only when it is complete.
+int snap_write_job(StateAsync* a, std::string* err) {
+  SnapAsync* sn = a->snap;
+  const SnapJob& j = sn->job;
+  WCHK(hipSetDevice(j.device));
+  StateRec rec{};
+  if (fetch_dev(a, sn->stage + sn->off_rec, sizeof rec, &rec, err)) return 1;
+  const int head = rec.ring_head, size = rec.ring_size;
+  if (j.with_mem) {
+    if (head < 0 || head >= j.cap || size < 0 || size > j.cap) {
+      *err = "the ring's (head, size) = (" + std::to_string(head) + ", " + std::to_string(size) + ") is outside its capacity " + std::to_string(j.cap);
+      return 1;
+    }
+    uint32_t guard[dqnhip_snap::kGuardWords];
+    if (fetch_dev(a, sn->stage + sn->off_guard, sizeof guard, guard, err)) return 1;
+    for (int i = 0; i < dqnhip_snap::kGuardWords; ++i)
+      if (guard[i] != dqnhip_snap::kGuardWord) { *err = "guard word " + std::to_string(i) + " behind the replay-memory stream was overwritten; no file was written"; return 1; }
+  }
+  // ---- the four protobuf files, from the staged dense arrays ----
+  std::vector<float> par[kSnapPar];
+  for (int i = 0; i < kSnapPar; ++i) {
+    par[i].resize(sn->par_bytes[i] / sizeof(float));
+    if (fetch_dev(a, sn->stage + sn->off_par[i], sn->par_bytes[i], par[i].data(), err)) return 1;
+  }
+  const int iters[2] = {rec.actor_iter, rec.critic_iter};
+  static const char* const kNet[2] = {"_actor", "_critic"};
+  std::string to[2];
+  for (int net = 0; net < 2; ++net) {
+    const std::string from = j.save_path + kNet[net] + "_iter_" + std::to_string(iters[net]);      // Solver::SnapshotFilename
+    to[net] = j.prefix + kNet[net] + "_iter_" + std::to_string(iters[net]);
+    if (dqnhip_snap::publish_file(from + ".caffemodel", dqnhip_snap::caffemodel_bytes(j.cfg, net, par[net].data()), err)) return 1;
+    const float* h2 = j.two ? par[3 + 2 * net].data() : nullptr;
+    if (dqnhip_snap::publish_file(from + ".solverstate", dqnhip_snap::solverstate_bytes(j.cfg, net, iters[net], from + ".caffemodel", par[2 + 2 * net].data(), h2), err)) return 1;
+  }
+  for (int net = 0; net < 2; ++net) {
+    const std::string from = j.save_path + kNet[net] + "_iter_" + std::to_string(iters[net]);
+    if (dqnhip_snap::move_file(from + ".caffemodel", to[net] + ".caffemodel", err) || dqnhip_snap::move_file(from + ".solverstate", to[net] + ".solverstate", err)) return 1;
+  }
+  // ---- the replay memory: one gzip member, the trailer's CRC from the device ----
+  if (j.with_mem) {
+    const uint64_t rec_bytes = (uint64_t)size * dqnhip_snap::record_bytes(j.S);
+    std::vector<uint32_t> raws((size_t)((rec_bytes + kCrcChunk - 1) / kCrcChunk));
+    if (fetch_dev(a, sn->stage + sn->off_crc, raws.size() * sizeof(uint32_t), raws.data(), err)) return 1;
+    // k_state_crc checksums the records; the count in front is four bytes the host knows: crc(A || B) = Z_|B|(crc(A)) ^ crc(B),
+    // zlib's crc32_combine
+    const int32_t count = size;
+    const uint32_t crc = (uint32_t)crc32_combine(crc32_of(&count, sizeof count), crc_fold_chunks(raws.data(), rec_bytes, a->chunk_tab), (z_off_t)rec_bytes);
+    const std::string mem = j.prefix + "_iter_" + std::to_string(std::max(iters[0], iters[1])) + ".replaymemory";
+    GzipParallelWriter w;
+    if (w.open(mem.c_str(), j.workers, GzipParallelWriter::kDefaultChunk, err)) return 1;
+    if (stream_dev(a, sn->stage + sn->off_stream, (size_t)(4 + rec_bytes), &w, err)) return 1;
+    if (w.finish(crc, err)) return 1;
+  }
+  if (j.remove_old) dqnhip_snap::remove_old_snapshots(j.prefix, iters[0], iters[1]);      // only now: all of this job's files are in place
+  sn->actor_iter = iters[0]; sn->critic_iter = iters[1];
+  return 0;
 }
 
 void writer_main(StateAsync* a) {
@@ -190,15 +287,16 @@ void writer_main(StateAsync* a) {
   (void)hipThreadExchangeStreamCaptureMode(&mode);
   std::unique_lock<std::mutex> lk(a->mu);
   for (;;) {
-    a->cv.wait(lk, [a] { return a->pending || a->quit; });
-    if (!a->pending) return;             // quit, and nothing left to write
-    a->pending = false;
+    a->cv.wait(lk, [a] { return !a->queue.empty() || a->quit; });
+    if (a->queue.empty()) return;        // quit, and nothing left to write
+    const int kind = a->queue.front();
+    a->queue.pop_front();
     lk.unlock();
     std::string err;
-    const int rc = write_job(a, &err);
+    const int rc = kind == kJobState ? write_job(a, &err) : snap_write_job(a, &err);
     lk.lock();
-    a->failed = rc != 0; a->err = err;
-    a->busy = false;
+    a->failed[kind] = rc != 0; a->err[kind] = err;
+    a->busy[kind] = false;
     a->cv.notify_all();
   }
 }
@@ -226,11 +324,28 @@ int arena_segs(const NetLayout& l, const float* base, float* dst, std::vector<Pa
   return d == l.dense ? 0 : fail("dqnhip_save_state_async: the dense image of a net has %zu floats, expected %zu", d, l.dense);
 }
 
-// first use: the staging buffer's map, the four HIP objects, the segment table, the writer thread
-int state_async_init(H* h) {
+// first use of either kind of job: what they share — the pinned ring, the copy stream, the combine table, the writer thread
+int writer_init(H* h) {
   if (h->sasync) return 0;
   std::unique_ptr<StateAsync> up(new StateAsync);
   StateAsync* a = up.get();
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipHostMalloc((void**)&a->pinned, 2 * kPinnedChunk, hipHostMallocDefault));
+  const hipError_t e = hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking);
+  if (e != hipSuccess) { hipHostFree(a->pinned); return fail("hipStreamCreateWithFlags failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__); }
+  uint32_t op[32];
+  crc_zeros_op(op, kCrcChunk);
+  crc_op_table(a->chunk_tab, op);
+  a->th = std::thread(writer_main, a);
+  h->sasync = up.release();
+  return 0;
+}
+
+// first asynchronous save: the staging buffer's map, the buffer, its event, the segment table
+int state_async_init(H* h) {
+  RC(writer_init(h));
+  StateAsync* a = h->sasync;
+  if (a->stage) return 0;
   const size_t cap = (size_t)h->ring.cap;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off = round_up_z(off + bytes, 16); return at; };
@@ -256,67 +371,136 @@ int state_async_init(H* h) {
     return fail("dqnhip_save_state_async: cannot allocate the device staging buffer of %zu bytes (%s); the learner is untouched and "
                 "dqnhip_save_state, which needs none, still works", a->stage_bytes, hipGetErrorString(e));
   }
-  a->stage = (uint8_t*)p;
+  uint8_t* stage = (uint8_t*)p;
+  hipEvent_t ev = nullptr;
   auto bail = [&](int rc) {
-    if (a->ev) hipEventDestroy(a->ev);
-    if (a->copy_stream) hipStreamDestroy(a->copy_stream);
-    if (a->pinned) hipHostFree(a->pinned);
-    hipFree(a->stage);
+    if (ev) hipEventDestroy(ev);
+    hipFree(stage);
+    a->segs.clear();
     return rc;
   };
 #define ICHK(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return bail(fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__)); } while (0)
-  ICHK(hipHostMalloc((void**)&a->pinned, 2 * kPinnedChunk, hipHostMallocDefault));
-  ICHK(hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking));
-  ICHK(hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
+  ICHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   // the segment table: W of the four nets, then (m, v) of the two online nets — the order of the parameter sections
   const float* arenas[8] = {h->w[0], h->w[1], h->w[2], h->w[3], h->m[0], h->v[0], h->m[1], h->v[1]};
   for (int i = 0; i < 8; ++i) {
     const int net = i < 4 ? i : (i - 4) / 2;
-    if (arena_segs(layout_of(h, net), arenas[i], (float*)(a->stage + a->off_par[i]), &a->segs)) return bail(1);
+    if (arena_segs(layout_of(h, net), arenas[i], (float*)(stage + a->off_par[i]), &a->segs)) return bail(1);
   }
   a->n_seg = (int)a->segs.size();
   if (a->n_seg > max_segs) return bail(fail("dqnhip_save_state_async: %d parameter pieces, room for %d", a->n_seg, max_segs));
-  ICHK(hipMemcpyAsync(a->stage + a->off_segs, a->segs.data(), a->segs.size() * sizeof(PackSeg), hipMemcpyHostToDevice, h->stream));
+  ICHK(hipMemcpyAsync(stage + a->off_segs, a->segs.data(), a->segs.size() * sizeof(PackSeg), hipMemcpyHostToDevice, h->stream));
   ICHK(hipStreamSynchronize(h->stream));
 #undef ICHK
-  uint32_t op[32];
-  crc_zeros_op(op, kCrcChunk);
-  crc_op_table(a->chunk_tab, op);
-  a->th = std::thread(writer_main, a);
-  h->sasync = up.release();
+  a->stage = stage; a->ev = ev;
   return 0;
+}
+
+// first asynchronous snapshot: the same for the snapshot's own staging buffer — the two kinds of job can be in flight together
+int snap_async_init(H* h) {
+  RC(writer_init(h));
+  StateAsync* a = h->sasync;
+  if (a->snap) return 0;
+  std::unique_ptr<SnapAsync> up(new SnapAsync);
+  SnapAsync* sn = up.get();
+  const bool two = h->cfg.solver_type == DQNHIP_SOLVER_ADAM || h->cfg.solver_type == DQNHIP_SOLVER_ADADELTA;
+  const uint64_t cap = (uint64_t)h->ring.cap, R = dqnhip_snap::record_bytes(h->S);
+  const uint64_t chunks = (cap * R + kCrcChunk - 1) / kCrcChunk;
+  if (chunks > 0x7fffffffull) return fail("dqnhip_snapshot_async: this learner's replay memory is too large for the chunk table");
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off = round_up_z(off + bytes, 16); return at; };
+  sn->off_rec = take(sizeof(StateRec));
+  // W of actor and critic, then (history 1, history 2) of each; a single-history solver has no second set
+  for (int i = 0; i < kSnapPar; ++i) {
+    const int net = i < 2 ? i : (i - 2) / 2;
+    const bool second = i >= 2 && (i - 2) % 2 == 1;
+    sn->par_bytes[i] = second && !two ? 0 : layout_of(h, net).dense * sizeof(float);
+    // the builders of snapshot.cpp index these arrays by their own blob table: the two must describe the same dense array
+    if (dqnhip_snap::dense_count(h->cfg, net) != (size_t)layout_of(h, net).dense)
+      return fail("dqnhip_snapshot_async: the snapshot codec counts %zu dense parameters in net %d, the learner %zu", dqnhip_snap::dense_count(h->cfg, net), net,
+                  (size_t)layout_of(h, net).dense);
+  }
+  const int max_segs = kSnapPar * (2 * kMaxL + 4);
+  sn->off_segs = take((size_t)max_segs * sizeof(PackSeg));
+  sn->off_crc = take((size_t)chunks * sizeof(uint32_t));
+  for (int i = 0; i < kSnapPar; ++i) sn->off_par[i] = take(sn->par_bytes[i]);
+  const size_t max_dwords = (size_t)dqnhip_snap::stream_dwords(h->S, cap);
+  sn->off_stream = take(16) + 12;                  // the count's four bytes end on a 16-byte boundary: k_snap_pack_replay stores whole 16-byte pieces of records, their CRC reads whole lines
+  off = sn->off_stream + 4 * max_dwords;
+  sn->off_guard = off;
+  off += dqnhip_snap::kGuardWords * sizeof(uint32_t);
+  sn->stage_bytes = round_up_z(off, 16);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, sn->stage_bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail("dqnhip_snapshot_async: the asynchronous snapshot cannot allocate its device staging buffer of %zu bytes (%s); the learner is "
+                "untouched and dqnhip_snapshot, which needs none, still works", sn->stage_bytes, hipGetErrorString(e));
+  }
+  sn->stage = (uint8_t*)p;
+  auto bail = [&](int rc) {
+    if (sn->ev) hipEventDestroy(sn->ev);
+    hipFree(sn->stage);
+    return rc;
+  };
+#define ICHK(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return bail(fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__)); } while (0)
+  ICHK(hipEventCreateWithFlags(&sn->ev, hipEventDisableTiming));
+  const float* arenas[kSnapPar] = {h->w[0], h->w[1], h->m[0], h->v[0], h->m[1], h->v[1]};
+  for (int i = 0; i < kSnapPar; ++i) {
+    if (!sn->par_bytes[i]) continue;
+    const int net = i < 2 ? i : (i - 2) / 2;
+    if (arena_segs(layout_of(h, net), arenas[i], (float*)(sn->stage + sn->off_par[i]), &sn->segs)) return bail(1);
+  }
+  sn->n_seg = (int)sn->segs.size();
+  if (sn->n_seg > max_segs) return bail(fail("dqnhip_snapshot_async: %d parameter pieces, room for %d", sn->n_seg, max_segs));
+  ICHK(hipMemcpyAsync(sn->stage + sn->off_segs, sn->segs.data(), sn->segs.size() * sizeof(PackSeg), hipMemcpyHostToDevice, h->stream));
+  ICHK(hipStreamSynchronize(h->stream));
+#undef ICHK
+  a->snap = up.release();
+  return 0;
+}
+
+// waits for the job of `kind` in flight; its failure, once, as `what`'s
+int job_join(H* h, int kind, const char* what) {
+  StateAsync* a = h->sasync;
+  if (!a) return 0;
+  std::unique_lock<std::mutex> lk(a->mu);
+  a->cv.wait(lk, [a, kind] { return !a->busy[kind]; });
+  if (!a->failed[kind]) return 0;
+  a->failed[kind] = false;
+  if (kind == kJobState) return fail("%s: the asynchronous save of %s failed: %s", what, a->job.filename.c_str(), a->err[kind].c_str());
+  return fail("%s: the asynchronous snapshot to %s failed: %s", what, a->snap->job.prefix.c_str(), a->err[kind].c_str());
 }
 
 }  // namespace
 
 namespace dqnhip_host {
 
-int state_async_join(H* h, const char* what) {
-  StateAsync* a = h->sasync;
-  if (!a) return 0;
-  std::unique_lock<std::mutex> lk(a->mu);
-  a->cv.wait(lk, [a] { return !a->busy; });
-  if (!a->failed) return 0;
-  a->failed = false;
-  return fail("%s: the asynchronous save of %s failed: %s", what, a->job.filename.c_str(), a->err.c_str());
-}
+int state_async_join(H* h, const char* what) { return job_join(h, kJobState, what); }
+int snapshot_async_join(H* h, const char* what) { return job_join(h, kJobSnapshot, what); }
 
 void state_async_free(H* h) {
   StateAsync* a = h->sasync;
   if (!a) return;
   {
     std::unique_lock<std::mutex> lk(a->mu);
-    a->cv.wait(lk, [a] { return !a->busy; });
+    a->cv.wait(lk, [a] { return !a->busy[kJobState] && !a->busy[kJobSnapshot]; });
     a->quit = true;
     a->cv.notify_all();
   }
   a->th.join();
-  hipEventDestroy(a->ev); hipStreamDestroy(a->copy_stream); hipHostFree(a->pinned); hipFree(a->stage);
+  if (a->snap) { hipEventDestroy(a->snap->ev); hipFree(a->snap->stage); delete a->snap; }
+  if (a->stage) { hipEventDestroy(a->ev); hipFree(a->stage); }
+  hipStreamDestroy(a->copy_stream); hipHostFree(a->pinned);
   delete a;
   h->sasync = nullptr;
 }
 
 }  // namespace dqnhip_host
+
+// what snapshot.cpp (a client of the C-ABI, without the learner's definition) needs of the above
+extern "C" int dqnhip_internal_snapshot_join(dqnhip_handle h, const char* what) { return h ? snapshot_async_join(h, what) : 0; }
 
 extern "C" {
 
@@ -387,8 +571,8 @@ int dqnhip_save_state_async(dqnhip_handle h, const char* filename, int32_t flags
   info.has_memory = with_mem; info.has_per = has_per; info.has_loss_scale = h->ls_dynamic;
   info.seed = h->cfg.seed;
   j.device = h->cfg.device; j.cap = h->ring.cap;
-  a->failed = false; a->err.clear();
-  a->pending = true; a->busy = true;
+  a->failed[kJobState] = false; a->err[kJobState].clear();
+  a->queue.push_back(kJobState); a->busy[kJobState] = true;
   a->cv.notify_all();
   return 0;
 }
@@ -403,7 +587,63 @@ int dqnhip_save_state_poll(dqnhip_handle h, int32_t* done) {
   StateAsync* a = h->sasync;
   if (!a) { *done = 1; return 0; }
   std::lock_guard<std::mutex> lk(a->mu);
-  *done = a->busy ? 0 : 1;
+  *done = a->busy[kJobState] ? 0 : 1;
+  return 0;
+}
+
+int dqnhip_snapshot_async(dqnhip_handle h, const char* save_path, const char* snapshot_prefix, int32_t remove_old, int32_t snapshot_memory,
+                          int32_t compress_threads) {
+  if (!h || !save_path || !snapshot_prefix) return fail("dqnhip_snapshot_async: null argument");
+  if (compress_threads < 0 || compress_threads > 64) return fail("dqnhip_snapshot_async: compress_threads %d is outside 0 ... 64 (0: the default, 8)", compress_threads);
+  RC(state_refuse(h, "dqnhip_snapshot_async: the asynchronous snapshot"));
+  RC(snapshot_async_join(h, "dqnhip_snapshot_async"));      // one snapshot in flight per learner
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RC(snap_async_init(h));
+  StateAsync* a = h->sasync;
+  SnapAsync* sn = a->snap;
+  // ---- the learner's stream: parameters and record, the stream, its checksum, event ----
+  RC(state_pack_params_launch(h, (const PackSeg*)(sn->stage + sn->off_segs), sn->n_seg, (StateRec*)(sn->stage + sn->off_rec)));
+  CrcArgs c{};
+  if (snapshot_memory) {
+    RC(snap_pack_replay_launch(h, sn->stage + sn->off_stream));
+    c.base = sn->stage; c.rec = (const StateRec*)(sn->stage + sn->off_rec); c.out = (uint32_t*)(sn->stage + sn->off_crc);
+    c.max_rows = h->ring.cap; c.n = 1;
+    const uint32_t R = (uint32_t)dqnhip_snap::record_bytes(h->S);
+    c.sec[0] = CrcSection{sn->off_stream + 4, 0, R, 0u};       // the records; the count in front of them is the host's to add
+    c.total_chunks = (uint32_t)(((uint64_t)h->ring.cap * R + kCrcChunk - 1) / kCrcChunk);
+    RC(state_crc_launch(h, c));
+  }
+  HIPCHK(hipEventRecord(sn->ev, h->stream));
+  HIPCHK(hipStreamWaitEvent(a->copy_stream, sn->ev, 0));   // the writer's copies are ordered behind the image by its own stream
+  // ---- the job ----
+  std::unique_lock<std::mutex> lk(a->mu);
+  SnapJob& j = sn->job;
+  j = SnapJob{};
+  j.save_path = save_path; j.prefix = snapshot_prefix; j.remove_old = remove_old != 0; j.with_mem = snapshot_memory != 0;
+  j.two = h->cfg.solver_type == DQNHIP_SOLVER_ADAM || h->cfg.solver_type == DQNHIP_SOLVER_ADADELTA;
+  j.workers = compress_threads ? compress_threads : 8;       // (never derived from the machine's CPU count: a container may grant fewer)
+  j.cfg = h->cfg; j.device = h->cfg.device; j.cap = h->ring.cap; j.S = h->S;
+  a->failed[kJobSnapshot] = false; a->err[kJobSnapshot].clear();
+  a->queue.push_back(kJobSnapshot); a->busy[kJobSnapshot] = true;
+  a->cv.notify_all();
+  return 0;
+}
+
+int dqnhip_snapshot_wait(dqnhip_handle h, int32_t* actor_iter, int32_t* critic_iter) {
+  if (!h) return fail("dqnhip_snapshot_wait: null argument");
+  RC(snapshot_async_join(h, "dqnhip_snapshot_wait"));
+  const SnapAsync* sn = h->sasync ? h->sasync->snap : nullptr;
+  if (actor_iter) *actor_iter = sn ? sn->actor_iter : 0;
+  if (critic_iter) *critic_iter = sn ? sn->critic_iter : 0;
+  return 0;
+}
+
+int dqnhip_snapshot_poll(dqnhip_handle h, int32_t* done) {
+  if (!h || !done) return fail("dqnhip_snapshot_poll: null argument");
+  StateAsync* a = h->sasync;
+  if (!a) { *done = 1; return 0; }
+  std::lock_guard<std::mutex> lk(a->mu);
+  *done = a->busy[kJobSnapshot] ? 0 : 1;
   return 0;
 }
 
@@ -497,6 +737,7 @@ int dqnhip_load_state(dqnhip_handle h, const char* filename) {
   if (!h || !filename) return fail("dqnhip_load_state: null argument");
   RC(state_refuse(h, (std::string("dqnhip_load_state: ") + filename).c_str()));
   RC(state_async_join(h, "dqnhip_load_state"));
+  RC(snapshot_async_join(h, "dqnhip_load_state"));
   // ---- everything that can fail for the file's sake, before the learner is touched ----
   Parsed p; std::string err;
   if (read_file(filename, &p, true, &err)) return fail("dqnhip_load_state: %s", err.c_str());

@@ -3,6 +3,7 @@
 // libprotobuf in the image), snapshot naming, old-snapshot removal, FindLatestSnapshot.
 // A pure client of the C-ABI in include/dqnhip.h: no device code here.
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstring>
 #include <filesystem>
@@ -12,11 +13,16 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "../../include/dqnhip.h"
+#include "snapshot_codec.h"
 
 namespace fs = std::filesystem;
 
 extern "C" int dqnhip_internal_set_error(const char* msg);
+// joins an asynchronous snapshot in flight (learner_state.hip); fails, as `what`, with its message if it failed
+extern "C" int dqnhip_internal_snapshot_join(dqnhip_handle h, const char* what);
 
 namespace {
 
@@ -96,9 +102,7 @@ bool write_file(const std::string& path, const std::string& data) {
 // ---- the learner's parameter blobs, in Caffe learnable_params order --------------------------
 struct ParamBlob { std::string layer; std::vector<int64_t> shape; size_t offset, count; };
 
-int blob_table(dqnhip_handle h, int net, std::vector<ParamBlob>& out, size_t& total) {
-  dqnhip_config c;
-  if (dqnhip_get_config(h, &c)) return 1;
+void blob_table_of(const dqnhip_config& c, int net, std::vector<ParamBlob>& out, size_t& total) {
   const bool actor = net == DQNHIP_ACTOR;
   int k = actor ? c.state_size : c.state_size + DQNHIP_ACTOR_OUT;
   size_t off = 0;
@@ -110,6 +114,11 @@ int blob_table(dqnhip_handle h, int net, std::vector<ParamBlob>& out, size_t& to
   if (actor) { add("action_layer", DQNHIP_ACTION_SIZE, k); add("actionpara_layer", DQNHIP_ACTION_PARAM_SIZE, k); }          // :426-427
   else add("q_values_layer", 1, k);                                                                                         // src/dqn.hpp:43
   total = off;
+}
+int blob_table(dqnhip_handle h, int net, std::vector<ParamBlob>& out, size_t& total) {
+  dqnhip_config c;
+  if (dqnhip_get_config(h, &c)) return 1;
+  blob_table_of(c, net, out, total);
   return 0;
 }
 
@@ -132,20 +141,20 @@ struct LayerSpec {
   int blob0 = -1;                           // index into the ParamBlob table of this layer's weight blob (-1: no blobs)
 };
 
-std::string layer_proto(const LayerSpec& l, const std::vector<ParamBlob>& tbl, const std::vector<float>& w) {
+std::string layer_proto(const LayerSpec& l, const std::vector<ParamBlob>& tbl, const float* w) {
   std::string o;
   put_bytes(o, 1, l.name);
   put_bytes(o, 2, l.type);
   for (auto& b : l.bottom) put_bytes(o, 3, b);
   for (auto& t : l.top) put_bytes(o, 4, t);
   if (l.blob0 >= 0)
-    for (int k = 0; k < 2; ++k) put_bytes(o, 7, blob_proto(tbl[l.blob0 + k].shape, w.data() + tbl[l.blob0 + k].offset, tbl[l.blob0 + k].count));
+    for (int k = 0; k < 2; ++k) put_bytes(o, 7, blob_proto(tbl[l.blob0 + k].shape, w + tbl[l.blob0 + k].offset, tbl[l.blob0 + k].count));
   put_int(o, 10, 0);                        // phase: TRAIN
   o += l.params;
   return o;
 }
 
-std::string net_proto(const std::vector<ParamBlob>& tbl, const std::vector<float>& w, bool actor, const dqnhip_config& c) {
+std::string net_proto(const std::vector<ParamBlob>& tbl, const float* w, bool actor, const dqnhip_config& c) {
   auto memory_data = [&](const std::string& name, const std::string& top, const std::string& dummy, int batch, int channels, int height) {
     LayerSpec l; l.name = name; l.type = "MemoryData"; l.top = {top, dummy};
     std::string p; put_int(p, 1, batch); put_int(p, 2, channels); put_int(p, 3, height); put_int(p, 4, 1);
@@ -249,7 +258,68 @@ std::string esc(const std::string& s) {            // the reference concatenates
   return s;
 }
 
+// caffe.SolverState{iter = 1, learned_net = 2, history = 3, current_step = 4}.  SGDSolver::PreSolve gives every solver one history
+// blob per parameter; AdamSolver and AdaDeltaSolver append a second set: history 1 of every blob, then history 2 of every blob
+// (Adam: all m, then all v).  h2 is read by a two-history solver only.
+std::string solverstate_proto(const std::vector<ParamBlob>& tbl, int iter, const std::string& learned_net, const float* h1, const float* h2, bool two) {
+  std::string o;
+  put_int(o, 1, iter);
+  put_bytes(o, 2, learned_net);
+  for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, h1 + b.offset, b.count));
+  if (two) for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, h2 + b.offset, b.count));
+  put_int(o, 4, 0);                                                                           // current_step
+  return o;
+}
+
 }  // namespace
+
+// ---- the builders on host pointers: what the asynchronous snapshot's writer thread (learner_state.hip) calls ----
+namespace dqnhip_snap {
+
+size_t dense_count(const dqnhip_config& c, int net) {
+  std::vector<ParamBlob> tbl; size_t total = 0;
+  blob_table_of(c, net, tbl, total);
+  return total;
+}
+std::string caffemodel_bytes(const dqnhip_config& c, int net, const float* w) {
+  std::vector<ParamBlob> tbl; size_t total = 0;
+  blob_table_of(c, net, tbl, total);
+  return net_proto(tbl, w, net == DQNHIP_ACTOR, c);
+}
+std::string solverstate_bytes(const dqnhip_config& c, int net, int iter, const std::string& learned_net, const float* h1, const float* h2) {
+  std::vector<ParamBlob> tbl; size_t total = 0;
+  blob_table_of(c, net, tbl, total);
+  return solverstate_proto(tbl, iter, learned_net, h1, h2, two_histories(c.solver_type));
+}
+int publish_file(const std::string& path, const std::string& data, std::string* err) {
+  const std::string tmp = path + ".tmp";
+  FILE* f = fopen(tmp.c_str(), "wb");
+  if (!f) { *err = "cannot open " + tmp + " for writing: " + strerror(errno); return 1; }
+  int bad = 0;                                      // errno of the first call that failed
+  if (fwrite(data.data(), 1, data.size(), f) != data.size()) bad = errno ? errno : EIO;
+  if (fflush(f) != 0 && !bad) bad = errno;
+  if (fsync(fileno(f)) != 0 && !bad) bad = errno;   // (the rename must not overtake the data on its way to the disk)
+  if (fclose(f) != 0 && !bad) bad = errno;
+  if (bad) { *err = "short write to " + tmp + ": " + strerror(bad); remove(tmp.c_str()); return 1; }
+  if (rename(tmp.c_str(), path.c_str()) != 0) { const std::string why = strerror(errno); remove(tmp.c_str()); *err = "rename " + tmp + " -> " + path + " failed: " + why; return 1; }
+  return 0;
+}
+int move_file(const std::string& a, const std::string& b, std::string* err) {
+  std::error_code ec;
+  if (!fs::is_regular_file(a, ec)) { *err = "missing " + a; return 1; }                 // CHECK(is_regular_file), :593-601
+  if (a != b) fs::rename(a, b, ec);
+  if (ec) { *err = "rename " + a + " -> " + b + " failed"; return 1; }
+  return 0;
+}
+void remove_old_snapshots(const std::string& pre, int actor_iter, int critic_iter) {   // :612-618
+  try {
+    remove_snapshots(esc(pre) + "_actor_iter_[0-9]+\\.(caffemodel|solverstate)", actor_iter - 1);
+    remove_snapshots(esc(pre) + "_critic_iter_[0-9]+\\.(caffemodel|solverstate)", critic_iter - 1);
+    remove_snapshots(esc(pre) + "_iter_[0-9]+\\.replaymemory", critic_iter - 1);
+  } catch (const std::exception&) { }               // (a prefix that is no regular expression removes nothing)
+}
+
+}  // namespace dqnhip_snap
 
 extern "C" {
 
@@ -262,13 +332,14 @@ int dqnhip_save_caffemodel(dqnhip_handle h, int32_t net, const char* filename) {
   if (dqnhip_get_params(h, net, DQNHIP_KIND_W, w.data(), total)) return 1;
   dqnhip_config cfg;
   if (dqnhip_get_config(h, &cfg)) return 1;
-  if (!write_file(filename, net_proto(tbl, w, net == DQNHIP_ACTOR, cfg))) return fail(std::string("cannot write ") + filename);
+  if (!write_file(filename, net_proto(tbl, w.data(), net == DQNHIP_ACTOR, cfg))) return fail(std::string("cannot write ") + filename);
   return 0;
 }
 
 int dqnhip_load_caffemodel(dqnhip_handle h, int32_t net, const char* filename) {
   if (!h || !filename) return fail("null argument");
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
+  if (dqnhip_internal_snapshot_join(h, "dqnhip_load_caffemodel")) return 1;
   std::string bytes;
   if (!read_file(filename, bytes)) return fail(std::string("Invalid file: ") + filename);      // CHECK(is_regular_file), :526,534
   std::vector<ParamBlob> tbl; size_t total = 0;
@@ -283,6 +354,7 @@ int dqnhip_load_caffemodel(dqnhip_handle h, int32_t net, const char* filename) {
 int dqnhip_solver_snapshot(dqnhip_handle h, int32_t net, const char* prefix, int32_t* iter_out) {
   if (!h || !prefix) return fail("null argument");
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
+  if (dqnhip_internal_snapshot_join(h, "dqnhip_solver_snapshot")) return 1;
   int32_t ia = 0, ic = 0;
   if (dqnhip_get_iters(h, &ia, &ic)) return 1;
   const int iter = net == DQNHIP_ACTOR ? ia : ic;
@@ -296,15 +368,7 @@ int dqnhip_solver_snapshot(dqnhip_handle h, int32_t net, const char* prefix, int
   std::vector<float> m(total), v(total);
   if (dqnhip_get_params(h, net, DQNHIP_KIND_M, m.data(), total)) return 1;
   if (two && dqnhip_get_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;
-  std::string o;
-  put_int(o, 1, iter);
-  put_bytes(o, 2, base + ".caffemodel");
-  // SGDSolver::PreSolve gives every solver one history blob per parameter; AdamSolver and AdaDeltaSolver append a second set:
-  // history 1 of every blob, then history 2 of every blob (Adam: all m, then all v)
-  for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, m.data() + b.offset, b.count));
-  if (two) for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, v.data() + b.offset, b.count));
-  put_int(o, 4, 0);                                                                           // current_step
-  if (!write_file(base + ".solverstate", o)) return fail("cannot write " + base + ".solverstate");
+  if (!write_file(base + ".solverstate", solverstate_proto(tbl, iter, base + ".caffemodel", m.data(), v.data(), two))) return fail("cannot write " + base + ".solverstate");
   if (iter_out) *iter_out = iter;
   return 0;
 }
@@ -312,6 +376,7 @@ int dqnhip_solver_snapshot(dqnhip_handle h, int32_t net, const char* prefix, int
 int dqnhip_solver_restore(dqnhip_handle h, int32_t net, const char* solverstate) {
   if (!h || !solverstate) return fail("null argument");
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
+  if (dqnhip_internal_snapshot_join(h, "dqnhip_solver_restore")) return 1;
   std::string bytes;
   if (!read_file(solverstate, bytes)) return fail(std::string("Invalid file: ") + solverstate);   // :542,551
   std::vector<ParamBlob> tbl; size_t total = 0;
@@ -362,6 +427,7 @@ int dqnhip_solver_restore(dqnhip_handle h, int32_t net, const char* solverstate)
 int dqnhip_snapshot(dqnhip_handle h, const char* save_path, const char* snapshot_prefix, int32_t remove_old,
                     int32_t snapshot_memory) {
   if (!h || !save_path || !snapshot_prefix) return fail("null argument");
+  if (dqnhip_internal_snapshot_join(h, "dqnhip_snapshot")) return 1;
   const std::string sp(save_path), pre(snapshot_prefix);
   int32_t actor_iter = 0, critic_iter = 0;
   if (dqnhip_solver_snapshot(h, DQNHIP_ACTOR, (sp + "_actor").c_str(), &actor_iter)) return 1;    // snapshot_prefix of the solvers, src/dqn_main.cpp:247-248
@@ -381,11 +447,7 @@ int dqnhip_snapshot(dqnhip_handle h, const char* save_path, const char* snapshot
     if (dqnhip_snapshot_replay_memory(h, mem.c_str())) return 1;
     if (!fs::is_regular_file(mem, ec)) return fail("missing " + mem);
   }
-  if (remove_old) {                                                                                // :612-618
-    remove_snapshots(esc(pre) + "_actor_iter_[0-9]+\\.(caffemodel|solverstate)", actor_iter - 1);
-    remove_snapshots(esc(pre) + "_critic_iter_[0-9]+\\.(caffemodel|solverstate)", critic_iter - 1);
-    remove_snapshots(esc(pre) + "_iter_[0-9]+\\.replaymemory", critic_iter - 1);
-  }
+  if (remove_old) dqnhip_snap::remove_old_snapshots(pre, actor_iter, critic_iter);
   return 0;
 }
 

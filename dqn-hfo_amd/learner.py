@@ -272,16 +272,36 @@ class DQN:
         return s, a, r, mc, nx, t
 
     # -- snapshot / restore (src/dqn.cpp:525-620) ---------------------------------------------------
-    def Snapshot(self, snapshot_prefix=None, remove_old=None, snapshot_memory=None):
+    def Snapshot(self, snapshot_prefix=None, remove_old=None, snapshot_memory=None, wait=True, compress_threads=0):
         """DQN::Snapshot(): `<prefix>_{actor,critic}_iter_N.{caffemodel,solverstate}` (+
         `<prefix>_iter_N.replaymemory`) in Caffe's binary protobuf layout.  With no arguments:
-        Snapshot(save_path_, FLAGS_remove_old_snapshots=True, FLAGS_snapshot_memory=True)."""
+        Snapshot(save_path_, FLAGS_remove_old_snapshots=True, FLAGS_snapshot_memory=True).
+        wait=False: dqnhip_snapshot_async — the same files under the same names, frozen on the device at this point of the stream and
+        written by the learner's writer thread (the replay memory deflated by `compress_threads` threads, 0: 8) while training goes
+        on; snapshot_wait() joins it and reports its status."""
         prefix = self.save_path_ if snapshot_prefix is None else snapshot_prefix
         remove_old = True if remove_old is None and snapshot_prefix is None else bool(remove_old)
         snapshot_memory = True if snapshot_memory is None else bool(snapshot_memory)
-        self._ck(self.lib.dqnhip_snapshot(self.h, os.fsencode(self.save_path_), os.fsencode(prefix),
-                                          int(remove_old), int(snapshot_memory)))
+        if wait:
+            self._ck(self.lib.dqnhip_snapshot(self.h, os.fsencode(self.save_path_), os.fsencode(prefix),
+                                              int(remove_old), int(snapshot_memory)))
+        else:
+            self._ck(self.lib.dqnhip_snapshot_async(self.h, os.fsencode(self.save_path_), os.fsencode(prefix),
+                                                    int(remove_old), int(snapshot_memory), int(compress_threads)))
         self.last_snapshot_iter_ = self.max_iter()
+
+    def snapshot_wait(self):
+        """dqnhip_snapshot_wait: joins an asynchronous snapshot in flight; raises if it failed.  -> (actor_iter, critic_iter) its files
+        are named by ((0, 0) when this learner never snapshotted asynchronously)."""
+        ia, ic = C.c_int32(), C.c_int32()
+        self._ck(self.lib.dqnhip_snapshot_wait(self.h, C.byref(ia), C.byref(ic)))
+        return ia.value, ic.value
+
+    def snapshot_done(self):
+        """dqnhip_snapshot_poll: True when no asynchronous snapshot is in flight.  Never blocks."""
+        done = C.c_int32()
+        self._ck(self.lib.dqnhip_snapshot_poll(self.h, C.byref(done)))
+        return bool(done.value)
 
     def RestoreActorSolver(self, actor_solver):
         self._ck(self.lib.dqnhip_solver_restore(self.h, ACTOR, os.fsencode(actor_solver)))

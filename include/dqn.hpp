@@ -172,6 +172,10 @@ class DQN {
   // the next SaveNativeState, at LoadNativeState and in the destructor
   bool native_in_flight_ = false; std::string native_remove_; int native_remove_below_ = 0;
   void JoinNativeState();
+  // -snapshot_async: Snapshot() calls dqnhip_snapshot_async; the snapshot is joined ("Snapshotting Finished!") before the next
+  // snapshot, before any Restore* / Load* and in the destructor
+  bool snapshot_in_flight_ = false;
+  void JoinSnapshot();
   dqnhip_handle h_;
 };
 

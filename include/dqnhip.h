@@ -628,6 +628,32 @@ int dqnhip_solver_restore(dqnhip_handle h, int32_t net, const char* solverstate)
  * older snapshots of the same prefix */
 int dqnhip_snapshot(dqnhip_handle h, const char* save_path, const char* snapshot_prefix,
                     int32_t remove_old, int32_t snapshot_memory);
+/* ---- the same files, written behind training (opt-in) ---------------------------------------------------------------------------
+ * dqnhip_snapshot_async writes the files dqnhip_snapshot would have written at this point of the learner's stream, under the same
+ * names, without waiting for the stream: the four protobuf files byte for byte, the `.replaymemory` as one gzip member whose
+ * decompressed bytes are the synchronous file's (its chunks are deflated independently by `compress_threads` threads, 0: 8; the
+ * compressed size differs by a few bytes per MiB).  On the caller's thread: the checks and v1 refusals (a learner in a sharing
+ * relationship, dp_world > 1 or a live communicator, a phased update in progress, kernel timing on), then the launches on the
+ * learner's stream — actor / critic weights and histories into dense Caffe order plus a record of the iteration counters and the
+ * ring's (head, size), the replay memory as the uncompressed stream (i32 n, n records of 4 S + 49 bytes in logical order), the
+ * stream's CRC-32 for the gzip trailer — into a device staging buffer of the snapshot's own, and one event.  The learner's writer
+ * thread, which it shares with dqnhip_save_state_async (jobs are taken first in first out, at most one of each kind in flight),
+ * waits for the event on a stream of its own, builds the files and publishes each as <name>.tmp, fsync, rename — a killed process
+ * leaves no partial file under a name dqnhip_find_latest_snapshot matches.  With remove_old the older files go only after all of
+ * this snapshot's files are in place.  The file names carry the iteration counters of the image, not the host's at a later moment.
+ * Whatever is enqueued after the call returns is not in the image.
+ * A second dqnhip_snapshot_async, dqnhip_snapshot, dqnhip_solver_snapshot, dqnhip_snapshot_replay_memory, dqnhip_solver_restore,
+ * dqnhip_load_caffemodel, dqnhip_load_replay_memory, dqnhip_load_state and dqnhip_destroy first join the one in flight; if it
+ * failed, the joining call fails with its message (dqnhip_destroy still destroys and does not fail).
+ * Cost: from the first asynchronous snapshot until dqnhip_destroy, device memory of the stream's upper bound for the capacity plus
+ * the six dense parameter arrays (about 360 MB at 1 M transitions of 58 floats), and the writer's 16 MB of pinned host memory; while
+ * a job runs, compress_threads x (1 MiB in + its deflate bound out) of host memory.  If the staging buffer cannot be allocated the
+ * call fails and says so; dqnhip_snapshot needs none. */
+int dqnhip_snapshot_async(dqnhip_handle h, const char* save_path, const char* snapshot_prefix, int32_t remove_old, int32_t snapshot_memory,
+                          int32_t compress_threads);
+int dqnhip_snapshot_wait(dqnhip_handle h, int32_t* actor_iter, int32_t* critic_iter);   /* joins; the job's status and the iterations its
+                                                                                          files are named by (either may be NULL); 0 when none */
+int dqnhip_snapshot_poll(dqnhip_handle h, int32_t* done);                               /* never blocks; *done = 1: nothing is in flight */
 /* FindLatestSnapshot (src/dqn.cpp:122-144): newest <prefix>_{actor,critic}_iter_N.solverstate
  * and <prefix>_iter_N.replaymemory; each buffer receives "" when none is found */
 int dqnhip_find_latest_snapshot(const char* snapshot_prefix, char* actor, char* critic, char* memory,
