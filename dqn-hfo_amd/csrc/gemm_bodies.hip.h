@@ -23,6 +23,28 @@ __host__ __device__ __forceinline__ void tile_of_counts(int tiles_p, int tiles_q
   tile_q = j - d * tiles_q;
   tile_p = xmap ? d * 8 + (b & 7) : d;
 }
+// The same map without the division, for the kernels that take packed arguments: the host knows tiles_q, pack_args stores
+// magic = tile_magic(tiles_q) = ceil(2^31 / tiles_q) in the problem's hot record, and j / tiles_q = mulhi(2 j + 1, magic) — two
+// scalar instructions where the division was a convert, a reciprocal, two lane reads and two correction steps in the vector unit,
+// one dependent chain in front of every launch's first load.
+// Why it is exact: magic = (2^31 + e) / tiles_q with 0 <= e < tiles_q, so (2 j + 1) magic / 2^32 = (j + 1/2) / tiles_q +
+// (2 j + 1) e / (tiles_q 2^32).  floor((j + 1/2) / tiles_q) = j / tiles_q, and (j + 1/2) / tiles_q lies at least 1 / (2 tiles_q)
+// below the next integer, so the floor is unchanged while (2 j + 1) e < 2^31, i.e. for every j < 2^30 / tiles_q.
+// (tiles_q = 1: magic = 2^31, mulhi(2 j + 1, 2^31) = j.)  What pack_args lets through is far inside that, and is the range that
+// tests/cpp/tile_decode_host.cpp sweeps whole against tile_of_counts: at most kTileDecodeMaxQ row tiles and kTileDecodeMaxTiles
+// tiles per problem (the product's largest launch: 256 x 64 tiles, 4096 rows of a 1024-wide layer in 16 x 16 tiles).
+constexpr int kTileDecodeMaxQ = 1024, kTileDecodeMaxTiles = 1 << 18;
+__host__ __device__ __forceinline__ uint32_t tile_magic(int tiles_q) { return (uint32_t)((0x80000000ull + (uint32_t)tiles_q - 1) / (uint32_t)tiles_q); }
+__host__ __device__ __forceinline__ bool tile_magic_covers(int tiles_p, int tiles_q) {
+  return tiles_p >= 1 && tiles_q >= 1 && tiles_q <= kTileDecodeMaxQ && (int64_t)tiles_p * tiles_q <= kTileDecodeMaxTiles;
+}
+__host__ __device__ __forceinline__ void tile_decode(int tiles_p, int tiles_q, uint32_t magic, int b, int& tile_p, int& tile_q) {
+  const bool xmap = (tiles_p & 7) == 0;
+  const int j = xmap ? b >> 3 : b;
+  const int d = (int)(((uint64_t)(2u * (uint32_t)j + 1u) * magic) >> 32);
+  tile_q = j - d * tiles_q;
+  tile_p = xmap ? d * 8 + (b & 7) : d;
+}
 __device__ __forceinline__ void tile_of_problem(const GemmProblem& pr, int b, int& tile_p, int& tile_q) {
   tile_of_counts(pr.tiles_p, pr.tiles_q, b, tile_p, tile_q);
 }
@@ -37,21 +59,6 @@ __device__ __forceinline__ void tile_of_block(const GemmBatch& batch, int& pi, i
 }
 
 // ---- the packed form (GemmArgs, gemm_common.hip.h) ----
-// f(0) .. f(N - 1) are read at constant kernarg offsets — one round of scalar loads, whatever pi turns out to be — and the
-// (workgroup-uniform) pi chooses among the values with scalar selects.
-template <int N, typename F>
-__device__ __forceinline__ auto pick(int pi, F f) -> decltype(f(0)) {
-  const auto v0 = f(0);
-  if constexpr (N == 1) return v0;
-  else {
-    const auto v1 = f(1), v2 = f(N > 2 ? 2 : 0), v3 = f(N > 3 ? 3 : 0);
-    auto v = v0;
-    v = (pi == 1) ? v1 : v;
-    if constexpr (N > 2) v = (pi == 2) ? v2 : v;
-    if constexpr (N > 3) v = (pi == 3) ? v3 : v;
-    return v;
-  }
-}
 // The GemmProblem a body takes, assembled in registers.  `cold` may be indexed by pi: its loads are the epilogue's.
 __device__ __forceinline__ GemmProblem make_problem(const float* P, const float* Q, float* C, int ldp, int ldq, int ldc, int Pdim, int Qdim, int Kred,
                                                     int mode, const GemmCold& c, int tiles_p, int tiles_q, int tile_base) {
@@ -64,7 +71,8 @@ __device__ __forceinline__ GemmProblem make_problem(const float* P, const float*
   return pr;
 }
 // One wait for a launch's scalar arguments.  The (empty) statement reads one value of every 16-byte piece of the header and of the
-// hot records (and up to two values of a rider struct, x0 / x1) and hands back the block index, from which everything else is
+// hot records, what the choice of a record and the tile decode read of them besides (Pdim, tq_magic), and up to two values of a
+// rider struct (x0 / x1), and hands back the block index, from which everything else is
 // computed: the compiler has to request all of them before it and cannot compute anything behind its back in between — left alone
 // it requests the header, waits, does the tile arithmetic, requests the records, waits again.
 template <int N>
@@ -76,7 +84,8 @@ __device__ __forceinline__ int request_args(const GemmArgs<N>& a, HotArgs<N>& r,
   for (int i = 0; i < N; ++i) r.hot[i] = a.hot[i];
   const GemmHot &h0 = r.hot[0], &h1 = r.hot[N > 1 ? 1 : 0], &h2 = r.hot[N > 2 ? 2 : 0], &h3 = r.hot[N > 3 ? 3 : 0];
   asm volatile("" : "+s"(b) : "s"(r.hd.tile_base[1]), "s"(r.hd.tiles_p[0]), "s"(r.hd.tiles_q[0]), "s"(x0), "s"(x1),
-               "s"(h0.P), "s"(h0.ldp), "s"(h0.C), "s"(h1.P), "s"(h1.ldp), "s"(h1.C), "s"(h2.P), "s"(h2.ldp), "s"(h2.C), "s"(h3.P), "s"(h3.ldp), "s"(h3.C));
+               "s"(h0.P), "s"(h0.ldp), "s"(h0.C), "s"(h1.P), "s"(h1.ldp), "s"(h1.C), "s"(h2.P), "s"(h2.ldp), "s"(h2.C), "s"(h3.P), "s"(h3.ldp), "s"(h3.C),
+               "s"(h0.Pdim), "s"(h1.Pdim), "s"(h2.Pdim), "s"(h3.Pdim), "s"(h0.tq_magic), "s"(h1.tq_magic), "s"(h2.tq_magic), "s"(h3.tq_magic));
   return b;
 }
 // problem I of a kernel whose problems are a compile-time fact (gemm_bwd_seq, gemm_wgrad_tail, k_dgrad_qtrain): no select at all
@@ -86,25 +95,46 @@ __device__ __forceinline__ GemmProblem problem_at(const GemmArgs<N>& a, const Ho
   const GemmHot& h = r.hot[I];
   return make_problem(h.P, h.Q, h.C, h.ldp, h.ldq, h.ldc, h.Pdim, h.Qdim, h.Kred, h.mode, a.cold[I], r.hd.tiles_p[I], r.hd.tiles_q[I], r.hd.tile_base[I]);
 }
+// ... and tile b of that problem (b counts from the problem's first tile)
+template <int I, int N>
+__device__ __forceinline__ void tile_of_record(const HotArgs<N>& r, int b, int& tile_p, int& tile_q) {
+  static_assert(I < N, "record not carried");
+  tile_decode(r.hd.tiles_p[I], r.hd.tiles_q[I], r.hot[I].tq_magic, b, tile_p, tile_q);
+}
 // GEMM tile b (request_args' return value) of a grouped launch: its problem and tile coordinates from the header alone, the hot
-// fields by select
+// fields of that problem's record
 template <int N>
 __device__ __forceinline__ GemmProblem problem_of_tile(const GemmArgs<N>& a, const HotArgs<N>& r, const int b, int& tile_p, int& tile_q) {
   const GemmHeader& hd = r.hd;
+  // A tile of problem 0 — every tile of a one-problem launch, which most launches of an update are (tile_base[1] = INT_MAX) —
+  // takes record 0 as it is, a tile of problem 1 record 1 as it is, and only the tiles of problems 2 and 3 choose, with ONE select
+  // per field.  The problem search and the three-deep selects over every field used to be some sixty scalar instructions between
+  // the arguments' arrival and every workgroup's first operand load; now they are uniform branches that a workgroup of an early
+  // problem does not enter.  (The empty statements keep the compiler from turning the branches back into selects.)
   int pi = 0;
-#pragma unroll
-  for (int i = 1; i < N; ++i)
-    if (b >= hd.tile_base[i]) pi = i;
-  const int tiles_p = pick<N>(pi, [&](int i) { return hd.tiles_p[i]; });
-  const int tiles_q = pick<N>(pi, [&](int i) { return hd.tiles_q[i]; });
-  const int tile_base = pick<N>(pi, [&](int i) { return hd.tile_base[i]; });
-  tile_of_counts(tiles_p, tiles_q, b - tile_base, tile_p, tile_q);
-  return make_problem(pick<N>(pi, [&](int i) { return r.hot[i].P; }), pick<N>(pi, [&](int i) { return r.hot[i].Q; }),
-                      pick<N>(pi, [&](int i) { return r.hot[i].C; }), pick<N>(pi, [&](int i) { return r.hot[i].ldp; }),
-                      pick<N>(pi, [&](int i) { return r.hot[i].ldq; }), pick<N>(pi, [&](int i) { return r.hot[i].ldc; }),
-                      pick<N>(pi, [&](int i) { return r.hot[i].Pdim; }), pick<N>(pi, [&](int i) { return r.hot[i].Qdim; }),
-                      pick<N>(pi, [&](int i) { return r.hot[i].Kred; }), pick<N>(pi, [&](int i) { return r.hot[i].mode; }),
-                      a.cold[N == 1 ? 0 : pi], tiles_p, tiles_q, tile_base);
+  int tiles_p = hd.tiles_p[0], tiles_q = hd.tiles_q[0], tile_base = hd.tile_base[0];
+  GemmHot h = r.hot[0];
+  if (N > 1 && b >= hd.tile_base[N > 1 ? 1 : 0]) {
+    pi = 1;
+    tiles_p = hd.tiles_p[N > 1 ? 1 : 0]; tiles_q = hd.tiles_q[N > 1 ? 1 : 0]; tile_base = hd.tile_base[N > 1 ? 1 : 0];
+    h = r.hot[N > 1 ? 1 : 0];
+    if (N > 2 && b >= hd.tile_base[N > 2 ? 2 : 0]) {
+      constexpr int I2 = N > 2 ? 2 : 0, I3 = N > 3 ? 3 : I2;
+      const bool last = N > 3 && b >= hd.tile_base[I3];
+      const GemmHot &h2 = r.hot[I2], &h3 = r.hot[I3];
+      pi = last ? I3 : I2;
+      tiles_p = last ? hd.tiles_p[I3] : hd.tiles_p[I2]; tiles_q = last ? hd.tiles_q[I3] : hd.tiles_q[I2];
+      tile_base = last ? hd.tile_base[I3] : hd.tile_base[I2];
+      h.P = last ? h3.P : h2.P; h.Q = last ? h3.Q : h2.Q; h.C = last ? h3.C : h2.C;
+      h.ldp = last ? h3.ldp : h2.ldp; h.ldq = last ? h3.ldq : h2.ldq; h.ldc = last ? h3.ldc : h2.ldc;
+      h.Pdim = last ? h3.Pdim : h2.Pdim; h.Qdim = last ? h3.Qdim : h2.Qdim; h.Kred = last ? h3.Kred : h2.Kred;
+      h.mode = last ? h3.mode : h2.mode; h.tq_magic = last ? h3.tq_magic : h2.tq_magic;
+      asm volatile("" : "+s"(pi));
+    }
+    asm volatile("" : "+s"(pi));
+  }
+  tile_decode(tiles_p, tiles_q, h.tq_magic, b - tile_base, tile_p, tile_q);
+  return make_problem(h.P, h.Q, h.C, h.ldp, h.ldq, h.ldc, h.Pdim, h.Qdim, h.Kred, h.mode, a.cold[N == 1 ? 0 : pi], tiles_p, tiles_q, tile_base);
 }
 template <int N>
 __device__ __forceinline__ GemmProblem problem_of_block(const GemmArgs<N>& a, int& tile_p, int& tile_q) {
@@ -166,12 +196,15 @@ __device__ __forceinline__ void fwd_direct_body(const GemmProblem& pr, int tile_
   const int p0 = tile_p * 16 * TP, q0 = tile_q * 16 * TQ;
   const int Kw = pr.Kred >> 2;              // this wave's share of the reduction
   const int nkb = Kw >> 4;                  // 16-wide k blocks
-  const float* pp[TP];
-  const float* qp[TQ];
+  // (addresses as in fwd_lds_body: a wave-uniform base per 16-row block, one 32-bit lane offset per operand — row li, k chunk lg)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const char* pp[TP];
+  const char* qp[TQ];
+  const uint32_t lofp = ((uint32_t)li * (uint32_t)pr.ldp + (uint32_t)lg * 4u) * 4u, lofq = ((uint32_t)li * (uint32_t)pr.ldq + (uint32_t)lg * 4u) * 4u;
 #pragma unroll
-  for (int c = 0; c < TP; ++c) pp[c] = pr.P + (size_t)(p0 + c * 16 + li) * pr.ldp + wave * Kw + lg * 4;
+  for (int c = 0; c < TP; ++c) pp[c] = c == 0 ? reinterpret_cast<const char*>(pr.P + (size_t)p0 * pr.ldp + wave_u * Kw) : pp[c > 0 ? c - 1 : 0] + (size_t)64 * pr.ldp;
 #pragma unroll
-  for (int a = 0; a < TQ; ++a) qp[a] = pr.Q + (size_t)(q0 + a * 16 + li) * pr.ldq + wave * Kw + lg * 4;
+  for (int a = 0; a < TQ; ++a) qp[a] = a == 0 ? reinterpret_cast<const char*>(pr.Q + (size_t)q0 * pr.ldq + wave_u * Kw) : qp[a > 0 ? a - 1 : 0] + (size_t)64 * pr.ldq;
 
   f32x4 acc[NACC];
 #pragma unroll
@@ -181,9 +214,9 @@ __device__ __forceinline__ void fwd_direct_body(const GemmProblem& pr, int tile_
 #define FWD_LOAD(slot, kb)                                                              \
   {                                                                                     \
     _Pragma("unroll") for (int c = 0; c < TP; ++c)                                      \
-        rp[slot][c] = *reinterpret_cast<const f32x4*>(pp[c] + ((kb) << 4));            \
+        rp[slot][c] = *reinterpret_cast<const f32x4*>(pp[c] + ((kb) << 6) + lofp);     \
     _Pragma("unroll") for (int a = 0; a < TQ; ++a)                                      \
-        rq[slot][a] = *reinterpret_cast<const f32x4*>(qp[a] + ((kb) << 4));            \
+        rq[slot][a] = *reinterpret_cast<const f32x4*>(qp[a] + ((kb) << 6) + lofq);     \
   }
 #define FWD_COMPUTE(slot)                                                               \
   {                                                                                     \
@@ -490,9 +523,13 @@ __device__ __forceinline__ void wgrad_direct_body(const GemmProblem& pr, int til
   const int p0 = tile_p * 64 * TPB, q0 = tile_q * 64 * TQB;
   const int Kw = pr.Kred >> 2;
   const int nst = Kw >> 2;                 // steps of 4 rows
-  const float* pp = pr.P + (size_t)(wave * Kw + lg) * pr.ldp + p0 + li * 4;
-  const float* qp = pr.Q + (size_t)(wave * Kw + lg) * pr.ldq + q0 + li * 4;
-  const size_t ldp = pr.ldp, ldq = pr.ldq;
+  // (addresses as in fwd_lds_body: a wave-uniform base — this wave's rows, the tile's columns — and one 32-bit lane offset per
+  // operand: row lg, columns 4 li; the steps advance the scalar base)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const char* pp = reinterpret_cast<const char*>(pr.P + (size_t)(wave_u * Kw) * pr.ldp + p0);
+  const char* qp = reinterpret_cast<const char*>(pr.Q + (size_t)(wave_u * Kw) * pr.ldq + q0);
+  const uint32_t lofp = ((uint32_t)lg * (uint32_t)pr.ldp + (uint32_t)li * 4u) * 4u, lofq = ((uint32_t)lg * (uint32_t)pr.ldq + (uint32_t)li * 4u) * 4u;
+  const size_t ldp = (size_t)pr.ldp * 4, ldq = (size_t)pr.ldq * 4;        // bytes
   const bool want_db = (pr.db != nullptr) && (tile_p == 0);
 
   f32x4 acc[NACC];   // index (((d*4 + qc)*TPB + b)*4 + pc)
@@ -508,9 +545,9 @@ __device__ __forceinline__ void wgrad_direct_body(const GemmProblem& pr, int til
 #define WG_LOAD(slot, st)                                                               \
   {                                                                                     \
     _Pragma("unroll") for (int b = 0; b < TPB; ++b)                                     \
-        rp[slot][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)((st) << 2) * ldp + b * 64); \
+        rp[slot][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)((st) << 2) * ldp + b * 256 + lofp); \
     _Pragma("unroll") for (int d = 0; d < TQB; ++d)                                     \
-        rq[slot][d] = *reinterpret_cast<const f32x4*>(qp + (size_t)((st) << 2) * ldq + d * 64); \
+        rq[slot][d] = *reinterpret_cast<const f32x4*>(qp + (size_t)((st) << 2) * ldq + d * 256 + lofq); \
   }
 #define WG_COMPUTE(slot)                                                                \
   {                                                                                     \
@@ -616,9 +653,12 @@ __device__ __forceinline__ void wgrad_narrow_body(const GemmProblem& pr, int til
   const int p0 = tile_p * 64 * TPB, q0 = tile_q * 16;
   const int Kw = pr.Kred >> 2;
   const int nst = Kw >> 2;
-  const float* pp = pr.P + (size_t)(wave * Kw + lg) * pr.ldp + p0 + li * 4;
-  const float* qp = pr.Q + (size_t)(wave * Kw + lg) * pr.ldq + q0 + li;
-  const size_t ldp = pr.ldp, ldq = pr.ldq;
+  // (addresses as in wgrad_direct_body; the dY operand one column per lane)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const char* pp = reinterpret_cast<const char*>(pr.P + (size_t)(wave_u * Kw) * pr.ldp + p0);
+  const char* qp = reinterpret_cast<const char*>(pr.Q + (size_t)(wave_u * Kw) * pr.ldq + q0);
+  const uint32_t lofp = ((uint32_t)lg * (uint32_t)pr.ldp + (uint32_t)li * 4u) * 4u, lofq = ((uint32_t)lg * (uint32_t)pr.ldq + (uint32_t)li) * 4u;
+  const size_t ldp = (size_t)pr.ldp * 4, ldq = (size_t)pr.ldq * 4;        // bytes
   const bool want_db = (pr.db != nullptr) && (tile_p == 0);
   f32x4 acc[NACC];
 #pragma unroll
@@ -629,8 +669,8 @@ __device__ __forceinline__ void wgrad_narrow_body(const GemmProblem& pr, int til
 #define WN_LOAD(slot, st)                                                               \
   {                                                                                     \
     _Pragma("unroll") for (int b = 0; b < TPB; ++b)                                     \
-        rp[slot][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)((st) << 2) * ldp + b * 64); \
-    rq[slot] = qp[(size_t)((st) << 2) * ldq];                                           \
+        rp[slot][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)((st) << 2) * ldp + b * 256 + lofp); \
+    rq[slot] = *reinterpret_cast<const float*>(qp + (size_t)((st) << 2) * ldq + lofq);  \
   }
 #define WN_COMPUTE(slot)                                                                \
   {                                                                                     \
@@ -724,14 +764,21 @@ __device__ __forceinline__ void fwd_lds_body(const GemmProblem& pr, int tile_p, 
   const int p0 = tile_p * 16 * TP, q0 = tile_q * 16 * TQ;
   const int Kw = pr.Kred >> 2;
   const int T = Kw >> 5;                         // steps of 32 k
-  float* wsm = smem + wave * WSTR;
-  const float* gp[NB];
-  size_t ld8[NB];
+  // Operand addresses: per 16-row block ONE wave-uniform base (scalar registers: tile row, this wave's k range) and per operand
+  // ONE per-lane 32-bit byte offset (row lr, chunk lc) — the loads take the scalar-base form; a 64-bit multiply-add and shift-add
+  // per block pointer in the vector unit used to stand between the arguments' arrival and the first load.  (The lane offset is
+  // at most 7 rows and 128 bytes: gemm_form_accepts bounds the leading dimensions, kMaxLeadingDim.)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const char* gp[NB];
+  size_t ld8[NB];                                              // 8 rows on, in bytes
+  uint32_t lof[NB];
+  const uint32_t lofp = ((uint32_t)lr * (uint32_t)pr.ldp + (uint32_t)lc * 4u) * 4u, lofq = ((uint32_t)lr * (uint32_t)pr.ldq + (uint32_t)lc * 4u) * 4u;
 #pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    if (b < TP) { gp[b] = pr.P + (size_t)(p0 + b * 16 + lr) * pr.ldp + wave * Kw + lc * 4; ld8[b] = (size_t)8 * pr.ldp; }
-    else { gp[b] = pr.Q + (size_t)(q0 + (b - TP) * 16 + lr) * pr.ldq + wave * Kw + lc * 4; ld8[b] = (size_t)8 * pr.ldq; }
+  for (int b = 0; b < NB; ++b) {               // (later blocks: the block before + 16 rows, a scalar add)
+    if (b < TP) { gp[b] = b == 0 ? reinterpret_cast<const char*>(pr.P + (size_t)p0 * pr.ldp + wave_u * Kw) : gp[b > 0 ? b - 1 : 0] + (size_t)64 * pr.ldp; ld8[b] = (size_t)32 * pr.ldp; lof[b] = lofp; }
+    else { gp[b] = b == TP ? reinterpret_cast<const char*>(pr.Q + (size_t)q0 * pr.ldq + wave_u * Kw) : gp[b > 0 ? b - 1 : 0] + (size_t)64 * pr.ldq; ld8[b] = (size_t)32 * pr.ldq; lof[b] = lofq; }
   }
+  float* wsm = smem + wave * WSTR;
   const int woff = lr * 32 + ((lc ^ lr) << 2);                 // + h*256 + b*512
   int roff[2];
 #pragma unroll
@@ -744,8 +791,8 @@ __device__ __forceinline__ void fwd_lds_body(const GemmProblem& pr, int tile_p, 
 
 #define L_GLOAD(G, t)                                                                   \
   { _Pragma("unroll") for (int b = 0; b < NB; ++b) {                                    \
-      G[b][0] = *reinterpret_cast<const f32x4*>(gp[b] + ((t) << 5));                   \
-      G[b][1] = *reinterpret_cast<const f32x4*>(gp[b] + ld8[b] + ((t) << 5)); } }
+      G[b][0] = *reinterpret_cast<const f32x4*>(gp[b] + ((t) << 7) + lof[b]);          \
+      G[b][1] = *reinterpret_cast<const f32x4*>(gp[b] + ld8[b] + ((t) << 7) + lof[b]); } }
 #define L_SWRITE(slot, G)                                                               \
   { _Pragma("unroll") for (int b = 0; b < NB; ++b) {                                    \
       *reinterpret_cast<f32x4*>(wsm + ((slot) % NSLOT) * SLOT + b * 512 + woff) = G[b][0];        \
@@ -900,12 +947,19 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
   const int Kw = pr.Kred >> 2;
   const int T = Kw >> 5;
   float* wsm = smem + wave * WAVE_FLOATS;
-  const float* pp = pr.P + (size_t)(wave * Kw + lg * 4) * pr.ldp + p0 + li * 4;
-  const size_t ldp = pr.ldp;
-  const float* gq[TQ];
+  // (addresses as in fwd_lds_body: wave-uniform bases and 32-bit lane offsets.  dY: row lr, chunk lc of a 16-row block.  W: the
+  // lane's row 4 lg + s2 of a 16-row k block, columns 4 li — one lane offset per s2, so that a step needs two scalar bases, not eight)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const char* pp = reinterpret_cast<const char*>(pr.P + (size_t)(wave_u * Kw) * pr.ldp + p0);
+  const size_t ldp = (size_t)pr.ldp * 4;                                   // bytes
+  uint32_t lofp[4];
 #pragma unroll
-  for (int a = 0; a < TQ; ++a) gq[a] = pr.Q + (size_t)(q0 + a * 16 + lr) * pr.ldq + wave * Kw + lc * 4;
-  const size_t ldq8 = (size_t)8 * pr.ldq;
+  for (int s2 = 0; s2 < 4; ++s2) lofp[s2] = ((uint32_t)(lg * 4 + s2) * (uint32_t)pr.ldp + (uint32_t)li * 4u) * 4u;
+  const char* gq[TQ];
+#pragma unroll
+  for (int a = 0; a < TQ; ++a) gq[a] = a == 0 ? reinterpret_cast<const char*>(pr.Q + (size_t)q0 * pr.ldq + wave_u * Kw) : gq[a > 0 ? a - 1 : 0] + (size_t)64 * pr.ldq;
+  const uint32_t lofq = ((uint32_t)lr * (uint32_t)pr.ldq + (uint32_t)lc * 4u) * 4u;
+  const size_t ldq8 = (size_t)32 * pr.ldq;                                 // 8 rows on, in bytes
   const int woff = lr * 32 + ((lc ^ lr) << 2);
   int roff[2];
 #pragma unroll
@@ -920,13 +974,13 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
 
 #define D_GLOADQ(G, t)                                                                  \
   { _Pragma("unroll") for (int a = 0; a < TQ; ++a) {                                    \
-      G[a][0] = *reinterpret_cast<const f32x4*>(gq[a] + ((t) << 5));                   \
-      G[a][1] = *reinterpret_cast<const f32x4*>(gq[a] + ldq8 + ((t) << 5)); } }
+      G[a][0] = *reinterpret_cast<const f32x4*>(gq[a] + ((t) << 7) + lofq);            \
+      G[a][1] = *reinterpret_cast<const f32x4*>(gq[a] + ldq8 + ((t) << 7) + lofq); } }
 #define D_GLOADP(PP, t)                                                                 \
   { _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                    \
     _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                    \
     _Pragma("unroll") for (int b = 0; b < TPB; ++b)                                     \
-        PP[kb][s2][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)(((t) << 5) + (kb << 4) + s2) * ldp + b * 64); }
+        PP[kb][s2][b] = *reinterpret_cast<const f32x4*>(pp + (size_t)(((t) << 5) + (kb << 4)) * ldp + b * 256 + lofp[s2]); }
 #define D_SWRITE(slot, G)                                                               \
   { _Pragma("unroll") for (int a = 0; a < TQ; ++a) {                                    \
       *reinterpret_cast<f32x4*>(wsm + (slot) * SLOT + a * 512 + woff) = G[a][0];        \

@@ -52,6 +52,10 @@ struct GemmProblem {
   int tiles_p, tiles_q, tile_base;
 };
 
+// The bodies address an operand as a wave-uniform 64-bit base plus ONE 32-bit byte offset per lane: at most 15 rows and 60 floats
+// into the operand, (15 ld + 60) * 4 + 16 <= 2^32.  gemm_form_accepts and pack_args refuse a larger leading dimension (the
+// product's are the tower widths, at most a few thousand); tests/cpp/tile_decode_host.cpp checks both sides of the bound.
+constexpr int kMaxLeadingDim = 1 << 26;
 constexpr int kMaxGroup = 4;
 struct GemmBatch {
   GemmProblem prob[kMaxGroup];
@@ -63,9 +67,9 @@ struct GemmBatch {
 // GemmBatch stays the host-side description; its launcher packs it (pack_args, gemm_direct.hip.h) into a GemmArgs laid out by when
 // a wave needs each field.  A wave's first operand load used to wait for five dependent scalar loads of the 640-byte GemmBatch
 // (tile_base, then tiles_p / tiles_q of prob[pi], ... then P / Q of prob[pi]); with this layout everything the first load needs is
-// requested at constant kernarg offsets in ONE round: the header (first 64 bytes) and the hot record of every problem, selected
-// with scalar selects.  The cold record (epilogue fields) is indexed by pi, so its request goes out after that round and nothing
-// waits for it before the operand loads are in flight.
+// requested at constant kernarg offsets in ONE round: the header (first 64 bytes) and the hot record of every problem; a uniform
+// branch on the block index then takes the record of the workgroup's problem (problem_of_tile).  The cold record (epilogue fields)
+// is indexed by pi, so its request goes out after that round and nothing waits for it before the operand loads are in flight.
 struct alignas(64) GemmHeader {
   int tile_base[kMaxGroup];    // entries >= n: INT_MAX (so the problem search needs no `n`)
   int tiles_p[kMaxGroup], tiles_q[kMaxGroup];
@@ -77,7 +81,9 @@ struct alignas(64) GemmHot {   // one 64-byte line; what every body's first load
   float* C;
   int mode;                    // (mixed-mode launches choose their body by it)
   int Pdim, Qdim;
-  int pad[3];
+  uint32_t tq_magic;           // ceil(2^31 / tiles_q): the tile decode's division as one multiply (tile_decode, gemm_bodies.hip.h); with
+                               // the record, not in the header: four problems need four and the header has two spare words
+  int pad[2];
 };
 struct GemmCold {
   const float* bias; const float* mask; float* db; float* partial;

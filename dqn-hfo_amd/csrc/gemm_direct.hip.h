@@ -130,13 +130,13 @@ __device__ __forceinline__ void bwd_seq_block(const GemmArgs<2>& args, const int
   // in flight do not pay for the registers and wait counts they hold through the other tile)
   const GemmProblem pw = problem_at<1>(args, r);
   if (b < pw.tiles_p * pw.tiles_q) {
-    tile_of_problem(pw, b, tile_p, tile_q);
+    tile_of_record<1>(r, b, tile_p, tile_q);
     wgrad_direct_body<1, 1>(pw, tile_p, tile_q, smem);
   }
   __syncthreads();
   const GemmProblem pd = problem_at<0>(args, r);
   if (b < pd.tiles_p * pd.tiles_q) {
-    tile_of_problem(pd, b, tile_p, tile_q);
+    tile_of_record<0>(r, b, tile_p, tile_q);
     if constexpr (DLDS) dgrad_lds_body<1, 1, true>(pd, tile_p, tile_q, smem);
     else dgrad_direct_body<1, 1>(pd, tile_p, tile_q, smem);
   }
@@ -174,10 +174,10 @@ __global__ __launch_bounds__(256) void gemm_wgrad_tail(const GemmArgs<2> args, c
   if (blk < rider.blocks) { head_wgrad_rider<NH>(rider, blk, smem); return; }
   blk -= rider.blocks;
   const int n0 = r.hd.tiles_p[1] * r.hd.tiles_q[1];
-  if (blk < n0) { const GemmProblem p0 = problem_at<1>(args, r); tile_of_problem(p0, blk, tile_p, tile_q); wgrad_narrow_body<1>(p0, tile_p, tile_q, smem); return; }
+  if (blk < n0) { const GemmProblem p0 = problem_at<1>(args, r); tile_of_record<1>(r, blk, tile_p, tile_q); wgrad_narrow_body<1>(p0, tile_p, tile_q, smem); return; }
   blk -= n0;
   const GemmProblem p1 = problem_at<0>(args, r);
-  tile_of_problem(p1, blk, tile_p, tile_q); wgrad_direct_body<1, 1>(p1, tile_p, tile_q, smem);
+  tile_of_record<0>(r, blk, tile_p, tile_q); wgrad_direct_body<1, 1>(p1, tile_p, tile_q, smem);
 }
 
 // ---- launchers ------------------------------------------------------------------------
@@ -207,6 +207,8 @@ inline hipError_t direct_launch(K kernel, GemmBatch& batch, int BP, int BQ, int 
 // accounting does not hold together — the kernel carries no record for a problem, a problem has no tiles, or the tile_base values
 // are not the running sum of the tile counts, so that a workgroup would be handed a tile of a problem it does not belong to, i.e. an
 // operand pointer out of range.  (Inside a problem tile_of_counts is a bijection onto its tiles: tests/cpp/packed_args_host.cpp.)
+// Also refused: tile counts beyond what the kernels' division-free decode is proven for (tile_decode, gemm_bodies.hip.h — the
+// reciprocal goes into the hot record) and leading dimensions beyond the lanes' 32-bit offsets (kMaxLeadingDim).
 // grouped: the problems' tiles follow each other in the grid (tile_base = running sum); else each problem's tiles count from 0.
 template <int N>
 inline bool pack_args(const GemmBatch& b, GemmArgs<N>& a, bool grouped = true) {
@@ -219,11 +221,14 @@ inline bool pack_args(const GemmBatch& b, GemmArgs<N>& a, bool grouped = true) {
     if (i >= b.n) continue;
     const GemmProblem& p = b.prob[i];
     if (p.tiles_p < 1 || p.tiles_q < 1 || p.tile_base != (grouped ? base : 0)) return false;
+    if (p.ldp > kMaxLeadingDim || p.ldq > kMaxLeadingDim) return false;  // a lane's 32-bit operand offset would wrap (gemm_common.hip.h)
+    if (!tile_magic_covers(p.tiles_p, p.tiles_q)) return false;       // more tiles than the kernels' division-free tile decode is exact for
     const int count = p.tiles_p * p.tiles_q;
     base += count;
     a.head.tile_base[i] = p.tile_base; a.head.tiles_p[i] = p.tiles_p; a.head.tiles_q[i] = p.tiles_q;
     GemmHot& h = a.hot[i];
     h.P = p.P; h.Q = p.Q; h.C = p.C; h.ldp = p.ldp; h.ldq = p.ldq; h.ldc = p.ldc; h.Pdim = p.Pdim; h.Qdim = p.Qdim; h.Kred = p.Kred; h.mode = p.mode;
+    h.tq_magic = tile_magic(p.tiles_q);
     GemmCold& c = a.cold[i];
     c.bias = p.bias; c.mask = p.mask; c.db = p.db; c.partial = p.partial; c.seed_w = p.seed_w; c.C2 = p.C2; c.dot_w = p.dot_w; c.dot_out = p.dot_out;
     c.xcopy_dst = p.xcopy_dst; c.ldm = p.ldm; c.relu = p.relu; c.xcopy_col = p.xcopy_col; c.xcopy_n = p.xcopy_n;

@@ -49,6 +49,7 @@ inline constexpr GemmFormSpec kGemmForms[GEMM_FORM_COUNT] = {
 // K >= 512 and K % 256 == 0: full-line loads + wave-private LDS transpose; else the plain direct body
 inline bool gemm_lds_ok(int kred) { return kred >= 512 && kred % 256 == 0; }
 inline bool gemm_tiles_ok(const GemmProblem& p, int bp, int bq) {
+  if (p.ldp > kMaxLeadingDim || p.ldq > kMaxLeadingDim) return false;      // the lanes' 32-bit operand offsets (gemm_common.hip.h)
   return p.Pdim > 0 && p.Qdim > 0 && p.Kred > 0 && p.Pdim % bp == 0 && p.Qdim % bq == 0;
 }
 // the reduction: every body splits it over the four waves (Kred / 4 each).  The k-contiguous operands advance in 16-k blocks per

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   HotArgs<1> r;
   const int b = request_args(args, r, (int)blockIdx.x);
   const GemmProblem pr = problem_at<0>(args, r);
-  tile_of_problem(pr, b, tile_p, tile_q);
+  tile_of_record<0>(r, b, tile_p, tile_q);
   const int q0 = tile_q * 16;
   QTrainHook hook(a, s_scale, s_dq, q0, tile_p);
   dgrad_lds_body<1, 1, true, QTrainHook>(pr, tile_p, tile_q, smem, s_scale, hook);
