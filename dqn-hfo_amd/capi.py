@@ -16,6 +16,7 @@ TUNE_SEPARATE_Q_TRAIN = 16
 TUNE_SEPARATE_FIRST_LAYER = 32
 TUNE_SEPARATE_CRITIC_FIRST_LAYERS = 64
 TUNE_LATE_GATHER = 128
+TUNE_NO_KERNARG_PRELOAD = 256
 # dqnhip_update_plan.forms bits (DQNHIP_PLAN_*), in bit order
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
               "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized")

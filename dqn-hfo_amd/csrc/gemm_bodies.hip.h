@@ -143,6 +143,92 @@ __device__ __forceinline__ GemmProblem problem_of_block(const GemmArgs<N>& a, in
   return problem_of_tile(a, r, b, tile_p, tile_q);
 }
 
+// ---- the preloaded form (GemmPreload, gemm_common.hip.h) ----
+// What a workgroup reads out of the 14 preloaded dwords: the tile of block b, its problem (0, or 1 from `split` on) and that problem's
+// operand bases.  Host and device share it (tests/cpp/kernarg_preload_host.cpp holds it against the packed GemmArgs).
+struct PreTile { int pi, tile_p, tile_q, tiles_p, tiles_q, tile_base; const float* P; const float* Q; };
+__host__ __device__ __forceinline__ PreTile preload_decode(const GemmPreload& w, int b) {
+  PreTile t;
+  const int split = (int)(w.flags >> kPreSplitShift);
+  t.pi = b >= split ? 1 : 0;
+  t.tile_base = t.pi ? split : 0;
+  t.tiles_p = (int)(w.tiles & ((1u << kPreTilesQShift) - 1)); t.tiles_q = (int)(w.tiles >> kPreTilesQShift);
+  tile_decode(t.tiles_p, t.tiles_q, w.magic, b - t.tile_base, t.tile_p, t.tile_q);
+  t.P = t.pi ? w.P1 : w.P0; t.Q = t.pi ? w.Q1 : w.Q0;
+  return t;
+}
+// The record form: the block holds ONE record of a kernel whose workgroups know their records at compile time, and in place of the
+// split the index `first` of the launch's first block that computes a tile of it (gemm_wgrad_tail's 64 x 64 tiles come behind its
+// riders and narrow tiles; k_dgrad_qtrain: 0).  Block b computes tile b - first of the record, or — in front of `first`, behind the
+// record's last tile — none of it (mine = false: that block takes the kernel's GemmArgs path).  Host and device share this too.
+struct PreRecordTile { bool mine; int tile_p, tile_q, tiles_p, tiles_q; };
+__host__ __device__ __forceinline__ PreRecordTile preload_record_decode(const GemmPreload& w, int b) {
+  PreRecordTile t;
+  const int bb = b - (int)(w.flags >> kPreSplitShift);
+  t.tiles_p = (int)(w.tiles & ((1u << kPreTilesQShift) - 1)); t.tiles_q = (int)(w.tiles >> kPreTilesQShift);
+  t.mine = bb >= 0 && bb < t.tiles_p * t.tiles_q;
+  tile_decode(t.tiles_p, t.tiles_q, w.magic, t.mine ? bb : 0, t.tile_p, t.tile_q);
+  return t;
+}
+// The host side.  A value that its field cannot hold makes the block "not valid" (all zero), never a truncated value.
+inline bool preload_record_fits(const GemmHot& h, int tiles_p, int tiles_q) {
+  return h.ldp >= 0 && h.ldp <= kMaxLeadingDim && h.ldq >= 0 && h.ldq <= kMaxLeadingDim && h.Kred >= 0 &&
+         tile_magic_covers(tiles_p, tiles_q) && tiles_p < (1 << kPreTilesQShift) && tiles_q < (1 << (32 - kPreTilesQShift)) &&
+         h.tq_magic == tile_magic(tiles_q);
+}
+// record i with the word that follows the flags: the split (grouped forms) or `first` (record form)
+template <int N>
+inline GemmPreload make_preload_words(const GemmArgs<N>& a, int i, uint32_t split_or_first) {
+  GemmPreload w{};
+  if (i < 0 || i >= N || i >= a.head.n || split_or_first > kPreNoSplit) return w;
+  const GemmHot& h = a.hot[i];
+  const int tp = a.head.tiles_p[i], tq = a.head.tiles_q[i];
+  if (!preload_record_fits(h, tp, tq)) return w;
+  w.P0 = h.P; w.Q0 = h.Q; w.ldp = (uint32_t)h.ldp; w.ldq = (uint32_t)h.ldq; w.Kred = (uint32_t)h.Kred;
+  w.tiles = (uint32_t)tp | (uint32_t)tq << kPreTilesQShift; w.magic = h.tq_magic;
+  w.flags = kPreValid | split_or_first << kPreSplitShift;
+  return w;
+}
+// the record form of record i (preload_record_decode)
+template <int N>
+inline GemmPreload make_preload_record(const GemmArgs<N>& a, int i, bool off, int first = 0) {
+  if (off || first < 0) return GemmPreload{};
+  return make_preload_words(a, i, (uint32_t)first);
+}
+// a grouped launch (preload_decode): one problem, or two of equal shape whose tiles follow each other in the grid
+template <int N>
+inline GemmPreload make_preload_grouped(const GemmArgs<N>& a, bool off) {
+  if (off || a.head.tile_base[0] != 0) return GemmPreload{};
+  if (a.head.n == 1) return make_preload_words(a, 0, kPreNoSplit);
+  if (N < 2 || a.head.n != 2) return GemmPreload{};
+  const GemmHot &h = a.hot[0], &g = a.hot[N > 1 ? 1 : 0];
+  const int tp = a.head.tiles_p[0], tq = a.head.tiles_q[0], split = a.head.tile_base[1];
+  if (g.ldp != h.ldp || g.ldq != h.ldq || g.Kred != h.Kred || a.head.tiles_p[1] != tp || a.head.tiles_q[1] != tq || g.tq_magic != h.tq_magic) return GemmPreload{};
+  if (split < 0 || (uint32_t)split >= kPreNoSplit) return GemmPreload{};
+  GemmPreload w = make_preload_words(a, 0, (uint32_t)split);
+  if (!(w.flags & kPreValid) || split != tp * tq) return GemmPreload{};
+  w.P1 = g.P; w.Q1 = g.Q;
+  return w;
+}
+// The device side: GEMM tile b of a valid block.  The operand bases, leading dimensions, reduction length and tile coordinates come
+// from the preloaded words — no scalar load stands in front of the body's first operand loads —; C, the output dimensions and the cold
+// record are the epilogue's and are read from the GemmArgs record of the tile's problem, requests that return under the operand loads.
+template <int N>
+__device__ __forceinline__ GemmProblem problem_of_preload(const GemmPreload& w, const GemmArgs<N>& a, int b, int& tile_p, int& tile_q) {
+  const PreTile t = preload_decode(w, b);
+  tile_p = t.tile_p; tile_q = t.tile_q;
+  const int pi = N == 1 ? 0 : t.pi;
+  const GemmHot& h = a.hot[pi];
+  return make_problem(t.P, t.Q, h.C, (int)w.ldp, (int)w.ldq, h.ldc, h.Pdim, h.Qdim, (int)w.Kred, h.mode, a.cold[pi], t.tiles_p, t.tiles_q, t.tile_base);
+}
+// ... and record I of a kernel whose records are a compile-time fact, for a block whose tile t (preload_record_decode) is its own
+template <int I, int N>
+__device__ __forceinline__ GemmProblem record_of_preload(const GemmPreload& w, const GemmArgs<N>& a, const PreRecordTile& t) {
+  static_assert(I < N, "record not carried");
+  const GemmHot& h = a.hot[I];
+  return make_problem(w.P0, w.Q0, h.C, (int)w.ldp, (int)w.ldq, h.ldc, h.Pdim, h.Qdim, (int)w.Kred, h.mode, a.cold[I], t.tiles_p, t.tiles_q, a.head.tile_base[I]);
+}
+
 // Each wave parks its NACC accumulators in LDS (lane-linear: conflict free), then wave w
 // returns, for every accumulator e with (e & 3) == w, the fixed-order sum over the 4 waves.
 template <int NACC>

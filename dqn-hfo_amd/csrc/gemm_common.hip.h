@@ -100,11 +100,39 @@ struct GemmArgs {
 };
 static_assert(sizeof(GemmHeader) == 64 && sizeof(GemmHot) == 64, "one 16-dword scalar load each");
 
+// ---- the kernarg preload block -------------------------------------------------------------------------------------------------
+// gfx950 delivers a kernel's first (up to) 14 kernarg dwords in SGPRs at wave launch — leading SCALAR parameters only, a struct is
+// never preloaded.  The chain kernels therefore take these 14 dwords as leading scalar parameters in front of their GemmArgs:
+// what a workgroup needs to form the addresses of its first operand loads and nothing else, so that those loads issue without a
+// scalar wait in front of them; everything else still comes from the GemmArgs behind them, requested in the loads' shadow.
+// The host derives the block from a packed GemmArgs (make_preload_*, gemm_direct.hip.h); GemmArgs itself is unchanged.
+//   one problem            P0 / Q0, one set of ldp / ldq / Kred / tile counts / magic; no split
+//   two of equal shape     P0 / Q0 / P1 / Q1, ONE set of the rest; tiles b >= split are problem 1's
+//   one record             P0 / Q0 and the rest of ONE record of a two-tile kernel; in place of the split its first block
+//   anything else          flags = 0: the kernel takes the GemmArgs path as it was, behind one uniform branch
+struct GemmPreload {
+  const float* P0; const float* Q0; const float* P1; const float* Q1;
+  uint32_t ldp, ldq, Kred;
+  uint32_t tiles;              // tiles_p | tiles_q << kPreTilesQShift
+  uint32_t magic;              // tile_magic(tiles_q)
+  uint32_t flags;              // kPreValid | (split or first block) << kPreSplitShift
+};
+static_assert(sizeof(GemmPreload) == 14 * 4, "16 user SGPRs less the kernarg pointer");
+constexpr uint32_t kPreValid = 1;
+constexpr int kPreSplitShift = 2, kPreTilesQShift = 20;
+constexpr uint32_t kPreNoSplit = (1u << (32 - kPreSplitShift)) - 1;      // one problem: no block index reaches it
+// the kernels' leading parameters / the words of a GemmPreload in a launch's argument list, in the struct's order
+#define DQN_PRELOAD_PARAMS const float* pre_P0, const float* pre_Q0, const float* pre_P1, const float* pre_Q1, \
+    uint32_t pre_ldp, uint32_t pre_ldq, uint32_t pre_Kred, uint32_t pre_tiles, uint32_t pre_magic, uint32_t pre_flags
+#define DQN_PRELOAD_WORDS(pre) (pre).P0, (pre).Q0, (pre).P1, (pre).Q1, (pre).ldp, (pre).ldq, (pre).Kred, (pre).tiles, (pre).magic, (pre).flags
+#define DQN_PRELOAD_BLOCK GemmPreload{pre_P0, pre_Q0, pre_P1, pre_Q1, pre_ldp, pre_ldq, pre_Kred, pre_tiles, pre_magic, pre_flags}
+
 // Where ONE kernel launch goes: a stream and, in the learner's timing mode, the event pair that brackets it.  Every launcher takes a
 // LaunchOn where it would take a stream (a bare hipStream_t converts: untimed) and hands it to exactly one launch().
 struct LaunchOn {
   hipStream_t stream;
   hipEvent_t start = nullptr, stop = nullptr;
+  bool no_preload = false;         // DQNHIP_TUNE_NO_KERNARG_PRELOAD: the launch's GemmPreload is marked "not valid" (A/B in one binary)
   LaunchOn(hipStream_t s) : stream(s) {}
   LaunchOn(hipStream_t s, hipEvent_t t0, hipEvent_t t1) : stream(s), start(t0), stop(t1) {}
 };

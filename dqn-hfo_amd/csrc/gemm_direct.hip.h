@@ -46,10 +46,15 @@ __global__ __launch_bounds__(256) void gemm_fwd_direct(const GemmArgs<kMaxGroup>
   fwd_direct_body<TP, TQ>(pr, tile_p, tile_q, smem);
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
-__global__ __launch_bounds__(256) void gemm_fwd_lds(const GemmArgs<kMaxGroup> args) {
+__global__ __launch_bounds__(256) void gemm_fwd_lds(DQN_PRELOAD_PARAMS, const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int tile_p, tile_q;
-  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  if (!(pre_flags & kPreValid)) {          // not a form the preload block expresses (or switched off): the GemmArgs path as it was
+    const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+    fwd_lds_body<TP, TQ, PIN, NSLOT>(pr, tile_p, tile_q, smem);
+    return;
+  }
+  const GemmProblem pr = problem_of_preload(DQN_PRELOAD_BLOCK, args, (int)blockIdx.x, tile_p, tile_q);
   fwd_lds_body<TP, TQ, PIN, NSLOT>(pr, tile_p, tile_q, smem);
 }
 template <int TPB, int TQ>
@@ -65,10 +70,15 @@ __device__ __forceinline__ void dgrad_lds_body(const GemmProblem& pr, int tile_p
   dgrad_lds_body<TPB, TQ, SCH, DgradNoHook>(pr, tile_p, tile_q, smem, nullptr, none);
 }
 template <int TPB, int TQ>
-__global__ __launch_bounds__(256) void gemm_dgrad_lds(const GemmArgs<kMaxGroup> args) {
+__global__ __launch_bounds__(256) void gemm_dgrad_lds(DQN_PRELOAD_PARAMS, const GemmArgs<kMaxGroup> args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int tile_p, tile_q;
-  const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+  if (!(pre_flags & kPreValid)) {
+    const GemmProblem pr = problem_of_block(args, tile_p, tile_q);
+    dgrad_lds_body<TPB, TQ>(pr, tile_p, tile_q, smem);
+    return;
+  }
+  const GemmProblem pr = problem_of_preload(DQN_PRELOAD_BLOCK, args, (int)blockIdx.x, tile_p, tile_q);
   dgrad_lds_body<TPB, TQ>(pr, tile_p, tile_q, smem);
 }
 template <int TPB, int TQB>
@@ -163,10 +173,22 @@ __global__ __launch_bounds__(256) void gemm_wgrad_narrow_rider(const GemmArgs<kM
 // The LAST launch of a net's backward under the shifted schedule (learner.hip tower_backward): layer 1's wgrad (prob[0]:
 // 64 x 64 tiles), the first layer's narrow wgrad (prob[1]: 16-output tiles) and the head's dW / db rider blocks.  The
 // first layer's wgrad alone is 64-128 short workgroups — a 6-us launch of launch floor; beside a full wgrad it costs ~1.
-// Long workgroups first in the grid.
+// Grid order: the rider blocks, the narrow tiles, the 64 x 64 tiles, the tails block (the long workgroups first measured the same,
+// profiles/r06_wgrad_tail_order.txt); the preloaded path below depends on it through the first-block word.
 template <int NH>
-__global__ __launch_bounds__(256) void gemm_wgrad_tail(const GemmArgs<2> args, const HeadWgradRider rider, const TailsArgs tails) {
+__global__ __launch_bounds__(256) void gemm_wgrad_tail(DQN_PRELOAD_PARAMS, const GemmArgs<2> args, const HeadWgradRider rider, const TailsArgs tails) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (pre_flags & kPreValid) {
+    // The preloaded words are the 64 x 64 wgrad's record: its workgroups are the long ones.  They come behind the rider blocks and
+    // the narrow tiles, from the block the words name on; every other block — the riders, the narrow tiles, the tails block behind
+    // the last tile — takes the scalar path below.
+    const PreRecordTile t = preload_record_decode(DQN_PRELOAD_BLOCK, (int)blockIdx.x);
+    if (t.mine) {
+      const GemmProblem p1 = record_of_preload<0>(DQN_PRELOAD_BLOCK, args, t);
+      wgrad_direct_body<1, 1>(p1, t.tile_p, t.tile_q, smem);
+      return;
+    }
+  }
   HotArgs<2> r;
   int blk = request_args(args, r, (int)blockIdx.x, tails.on, rider.blocks);
   int tile_p, tile_q;
@@ -247,6 +269,15 @@ inline hipError_t packed_launch(K kernel, GemmBatch& batch, int BP, int BQ, int 
   tile_batch(batch, BP, BQ);
   return packed_launch(kernel, batch, 0, lds_bytes, on);
 }
+// the same for a kernel that takes the preload block in front of its GemmArgs (GemmPreload, gemm_common.hip.h)
+template <typename K>
+inline hipError_t preload_launch(K kernel, GemmBatch& batch, int BP, int BQ, int lds_bytes, const LaunchOn& on) {
+  tile_batch(batch, BP, BQ);
+  GemmArgs<kMaxGroup> args;
+  if (!pack_args(batch, args)) return hipErrorInvalidValue;
+  const GemmPreload pre = make_preload_grouped(args, on.no_preload);
+  return launch(on, kernel, dim3(batch.total_tiles), dim3(256), lds_bytes, DQN_PRELOAD_WORDS(pre), args);
+}
 
 template <int TP, int TQ>
 constexpr int fwd_direct_lds_bytes() { return 4 * TP * TQ * 64 * 16; }
@@ -260,7 +291,7 @@ constexpr int fwd_lds_bytes() {
 }
 template <int TP, int TQ, bool PIN, int NSLOT = 2>
 inline hipError_t fwd_lds_launch(GemmBatch& b, const LaunchOn& on) {
-  return packed_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), on);
+  return preload_launch(gemm_fwd_lds<TP, TQ, PIN, NSLOT>, b, 16 * TP, 16 * TQ, (fwd_lds_bytes<TP, TQ, PIN, NSLOT>()), on);
 }
 template <int TPB, int TQ>
 constexpr int dgrad_direct_lds_bytes() { return 4 * TPB * 4 * TQ * 64 * 16; }
@@ -272,7 +303,7 @@ template <int TPB, int TQ>
 constexpr int dgrad_lds_bytes() { return 4 * ((2 * TQ * 512 > TPB * 4 * TQ * 256) ? 2 * TQ * 512 : TPB * 4 * TQ * 256) * 4; }
 template <int TPB, int TQ>
 inline hipError_t dgrad_lds_launch(GemmBatch& b, const LaunchOn& on) {
-  return packed_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), on);
+  return preload_launch(gemm_dgrad_lds<TPB, TQ>, b, 64 * TPB, 16 * TQ, dgrad_lds_bytes<TPB, TQ>(), on);
 }
 template <int TPB, int TQB>
 inline hipError_t wgrad_direct_launch(GemmBatch& b, const LaunchOn& on) {
@@ -331,7 +362,8 @@ inline hipError_t wgrad_tail_launch(GemmBatch& batch, const HeadWgradRider& ride
   if (lds > (size_t)kWgradTailLdsMax) return hipErrorInvalidValue;
   GemmArgs<2> args;
   if (batch.n != 2 || !pack_args(batch, args)) return hipErrorInvalidValue;
-  return launch(on, gemm_wgrad_tail<NH>, dim3(grid), dim3(256), lds, args, rider, tails);
+  const GemmPreload pre = make_preload_record(args, 0, on.no_preload, rider.blocks + w0.tiles_p * w0.tiles_q);   // (riders, narrow tiles, then the 64 x 64 tiles)
+  return launch(on, gemm_wgrad_tail<NH>, dim3(grid), dim3(256), lds, DQN_PRELOAD_WORDS(pre), args, rider, tails);
 }
 template <bool DLDS>
 inline hipError_t bwd_seq_launch(GemmBatch& batch, const LaunchOn& on) {

@@ -8,21 +8,38 @@ namespace dqnhip {
 
 // L1: compiled with the target actor's first-layer epilogue (HeadArgs::l1_*; Step(1) only — the acting path and the critic heads
 // instantiate L1 = false and carry neither its 44 registers nor its LDS row)
-template <int NH, int MODE, bool L1 = false>
-__global__ __launch_bounds__(256) void k_head_fwd(HeadArgs2 a2) {
+// The kernel's leading scalar parameters (the idea of GemmPreload, gemm_common.hip.h): head weights, biases and widths of its (up to)
+// two heads — what a block's FIRST vector loads, its bias and its NH weight strips, are addressed from — delivered in SGPRs at wave
+// launch where the unit is compiled with the kernarg preload option; the panel, the row count and the epilogue's fields still
+// come from HeadArgs2, read in those loads' shadow.  flags = 0 (DQNHIP_TUNE_NO_KERNARG_PRELOAD, a width its field cannot hold):
+// everything from HeadArgs2 as before, behind one uniform branch.
+struct HeadFwdPreload { const float* W0; const float* W1; const float* b0; const float* b1; uint32_t H0, H1, flags; };
+#define DQN_HEAD_PRELOAD_PARAMS const float* pre_W0, const float* pre_W1, const float* pre_b0, const float* pre_b1, \
+    uint32_t pre_H0, uint32_t pre_H1, uint32_t pre_flags
+#define DQN_HEAD_PRELOAD_WORDS(w) (w).W0, (w).W1, (w).b0, (w).b1, (w).H0, (w).H1, (w).flags
+inline HeadFwdPreload make_head_preload(const HeadArgs2& a2, bool two, bool off) {
+  HeadFwdPreload w{};
+  if (off || a2.p[0].H < 1 || (two && a2.p[1].H < 1)) return w;
+  w.W0 = a2.p[0].W; w.b0 = a2.p[0].b; w.H0 = (uint32_t)a2.p[0].H;
+  if (two) { w.W1 = a2.p[1].W; w.b1 = a2.p[1].b; w.H1 = (uint32_t)a2.p[1].H; }
+  w.flags = kPreValid;
+  return w;
+}
+// one head's blocks: W / b / H from either source, the rest from a
+template <int NH, int MODE, bool L1>
+__device__ __forceinline__ void head_fwd_block(const HeadArgs& a, const float* W, const float* b, const int H) {
   // one block per row (grid-strided when there are more rows than blocks): the 4 waves split K
   // (each lane one float4 strip per 1024 columns), butterfly within the wave, then the 4 wave
   // sums are added in fixed order.  For H <= 1024 the head weights stay in registers across rows.
-  const HeadArgs& a = a2.p[blockIdx.y];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __shared__ float s_acc[4][NH];
-  const bool hoist = a.H <= 1024;
-  const float bias_j = threadIdx.x < NH ? a.b[threadIdx.x] : 0.0f;      // requested now, used after the reduction
+  const bool hoist = H <= 1024;
+  const float bias_j = threadIdx.x < NH ? b[threadIdx.x] : 0.0f;      // requested now, used after the reduction
   f32x4 wreg[NH];
   if (hoist) {
 #pragma unroll
     for (int j = 0; j < NH; ++j)
-      wreg[j] = (threadIdx.x * 4 < a.H) ? *reinterpret_cast<const f32x4*>(a.W + (size_t)j * a.H + threadIdx.x * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+      wreg[j] = (threadIdx.x * 4 < H) ? *reinterpret_cast<const f32x4*>(W + (size_t)j * H + threadIdx.x * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   // (l1: this thread's four outputs' action-column weights and biases do not depend on the row)
   constexpr bool kL1 = (L1 && MODE == HEAD_ACTOR && NH == kNO);
@@ -48,11 +65,11 @@ __global__ __launch_bounds__(256) void k_head_fwd(HeadArgs2 a2) {
     f32x4 zs = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (kL1) { if (l1_on) zs = *reinterpret_cast<const f32x4*>(a.l1_zs + (size_t)row * a.l1_ld + threadIdx.x * 4); }
     auto dots = [&](auto tag) {
-      for (int k = threadIdx.x * 4; k < a.H; k += 1024) {
+      for (int k = threadIdx.x * 4; k < H; k += 1024) {
         const f32x4 xv = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k);
 #pragma unroll
         for (int j = 0; j < NH; ++j) {
-          const f32x4 wv = hoist ? wreg[j] : *reinterpret_cast<const f32x4*>(a.W + (size_t)j * a.H + k);
+          const f32x4 wv = hoist ? wreg[j] : *reinterpret_cast<const f32x4*>(W + (size_t)j * H + k);
           acc[j] = fmaf(xv.x, wv.x, acc[j]); acc[j] = fmaf(xv.y, wv.y, acc[j]);
           acc[j] = fmaf(xv.z, wv.z, acc[j]); acc[j] = fmaf(xv.w, wv.w, acc[j]);
         }
@@ -99,6 +116,13 @@ __global__ __launch_bounds__(256) void k_head_fwd(HeadArgs2 a2) {
       }
     }
   }
+}
+template <int NH, int MODE, bool L1 = false>
+__global__ __launch_bounds__(256) void k_head_fwd(DQN_HEAD_PRELOAD_PARAMS, HeadArgs2 a2) {
+  const HeadArgs& a = a2.p[blockIdx.y];
+  if (!(pre_flags & kPreValid)) { head_fwd_block<NH, MODE, L1>(a, a.W, a.b, a.H); return; }
+  const bool second = blockIdx.y != 0;
+  head_fwd_block<NH, MODE, L1>(a, second ? pre_W1 : pre_W0, second ? pre_b1 : pre_b0, (int)(second ? pre_H1 : pre_H0));
 }
 
 // (Round 4: a form with the head weights staged once per block in LDS, 16 rows per block, all of a wave's rows in flight
@@ -201,10 +225,11 @@ int head_forward(H* h, hipStream_t st, const HeadArgs& a, const HeadArgs* b = nu
       return 0;
     }
   }
+  const HeadFwdPreload w = make_head_preload(a2, b != nullptr, (h->cfg.tuning_flags & DQNHIP_TUNE_NO_KERNARG_PRELOAD) != 0);
   if (a.l1_y != nullptr || (b && b->l1_y != nullptr))      // Step(1): the target actor's head also finishes critic_target's first layer
-    HIPCHK(launch(st, k_head_fwd<NH, MODE, true>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
+    HIPCHK(launch(st, k_head_fwd<NH, MODE, true>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, DQN_HEAD_PRELOAD_WORDS(w), a2));
   else
-    HIPCHK(launch(st, k_head_fwd<NH, MODE, false>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, a2));
+    HIPCHK(launch(st, k_head_fwd<NH, MODE, false>, dim3(std::min(a.rows, 1024), b ? 2 : 1), dim3(256), 0, DQN_HEAD_PRELOAD_WORDS(w), a2));
   return 0;
 }
 

@@ -210,15 +210,8 @@ struct QTrainHook {
     if (owner && lane == 0) a.loss_partial[(q0 >> 2) + wave] = ((d2[0] + d2[1]) + d2[2]) + d2[3];
   }
 };
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dgrad_qtrain(const GemmArgs<1> args, const HeadTrainArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ float s_scale[16], s_dq[16];
-  int tile_p, tile_q;
-  HotArgs<1> r;
-  const int b = request_args(args, r, (int)blockIdx.x);
-  const GemmProblem pr = problem_at<0>(args, r);
-  tile_of_record<0>(r, b, tile_p, tile_q);
+// the workgroup of tile (tile_p, tile_q): the dgrad tile with the head arithmetic hooked in, then its slices of dZ_L
+__device__ __forceinline__ void dgrad_qtrain_block(const GemmProblem& pr, const int tile_p, const int tile_q, const HeadTrainArgs& a, float* smem, float* s_scale, float* s_dq) {
   const int q0 = tile_q * 16;
   QTrainHook hook(a, s_scale, s_dq, q0, tile_p);
   dgrad_lds_body<1, 1, true, QTrainHook>(pr, tile_p, tile_q, smem, s_scale, hook);
@@ -236,12 +229,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     *reinterpret_cast<f32x4*>(a.dZ + x0) = dz;
   }
 }
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_dgrad_qtrain(DQN_PRELOAD_PARAMS, const GemmArgs<1> args, const HeadTrainArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float s_scale[16], s_dq[16];
+  int tile_p, tile_q;
+  if (!(pre_flags & kPreValid)) {          // (switched off, or a value its field cannot hold: the GemmArgs path as it was)
+    HotArgs<1> r;
+    const int b = request_args(args, r, (int)blockIdx.x);
+    const GemmProblem pr = problem_at<0>(args, r);
+    tile_of_record<0>(r, b, tile_p, tile_q);
+    dgrad_qtrain_block(pr, tile_p, tile_q, a, smem, s_scale, s_dq);
+    return;
+  }
+  // the dgrad's operands from the preloaded words (GemmPreload, gemm_common.hip.h)
+  const PreRecordTile t = preload_record_decode(DQN_PRELOAD_BLOCK, (int)blockIdx.x);      // (every block of this grid is a tile of the record)
+  const GemmProblem pr = record_of_preload<0>(DQN_PRELOAD_BLOCK, args, t);
+  dgrad_qtrain_block(pr, t.tile_p, t.tile_q, a, smem, s_scale, s_dq);
+}
 inline hipError_t dgrad_qtrain_launch(GemmBatch& batch, const HeadTrainArgs& a, const LaunchOn& on) {
   batch.n = 1;
   tile_batch(batch, 64, 16);
   GemmArgs<1> args;
   if (!pack_args(batch, args)) return hipErrorInvalidValue;
-  return launch(on, k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), dgrad_lds_bytes<1, 1>(), args, a);
+  const GemmPreload pre = make_preload_record(args, 0, on.no_preload);
+  return launch(on, k_dgrad_qtrain<0>, dim3(batch.total_tiles), dim3(256), dgrad_lds_bytes<1, 1>(), DQN_PRELOAD_WORDS(pre), args, a);
 }
 
 // Fused head backward: in one pass over the tower top X4[rows][H]
@@ -428,45 +440,75 @@ __global__ __launch_bounds__(1024) void k_head_bwd(HeadBwdArgs a) {
 // actor's tower-top gradient.  Same arithmetic in the same order as the two kernels it replaces (bit-identical: the narrow
 // tile's values do not depend on which columns a workgroup owns, the head part is k_head_bwd's loop).  The q(s, mu(s)) riders
 // come last in the grid, as before.  The head's own dW / db are the wgrad-tail launch's riders (HeadWgradRider).
-template <bool F16 = false>
-__global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, const QHeadRider rider) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];     // the narrow dgrad's parking area (4 waves x 64 lanes x 16 B)
-  __shared__ float s_d[16][17];
-  __shared__ float s_dy[16 * kNO];
-  // what routes the workgroup, what the head part's first loads need and the narrow tile's operands: ONE round of scalar loads
-  // (request_args, gemm_bodies.hip.h, has the reasoning; left alone: the tile count, then the head's pointers, then the tile's)
-  int blk = (int)blockIdx.x;
-  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred), "s"(a.ls_mult));
-  else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
-  const int tiles = a.row_tiles * (a.dxc != nullptr ? 1 : (a.H + 255) >> 8);
-  if (blk >= tiles) { q_head_rider(rider, blk - tiles); return; }
-  const int rt = blk % a.row_tiles, cc = blk / a.row_tiles;
+// The kernarg preload block of k_dqda_head_bwd<false> (the idea of GemmPreload, gemm_common.hip.h, with this kernel's own words): what
+// routes a workgroup and what its first loads are addressed from — the head part's (ten head weights, the tower-top column, mu(s))
+// and the narrow tile's operands — as 14 leading scalar parameters, which gfx950 delivers in SGPRs at wave launch.  Everything
+// else (dA16, dZ, the tile's mask, dxc, the rider) still comes from DqdaHeadArgs / QHeadRider, read in those loads' shadow.
+// A value that does not fit its field, the fp16 form, or DQNHIP_TUNE_NO_KERNARG_PRELOAD: route = 0, the block is not valid and
+// the workgroup gathers the same values in one round of scalar loads, as before.
+struct DqdaPreload {
+  const float* W; const float* X4; const float* aout16; const float* P; const float* Q;
+  uint32_t ldp, ldq;
+  uint32_t h_kred;             // H | Kred << 16
+  uint32_t route;              // kPreValid | row_tiles << 1 | column chunks << 17 (dxc given: 1)
+};
+static_assert(sizeof(DqdaPreload) == 14 * 4, "16 user SGPRs less the kernarg pointer");
+#define DQN_DQDA_PRELOAD_PARAMS const float* pre_W, const float* pre_X4, const float* pre_aout16, const float* pre_P, const float* pre_Q, \
+    uint32_t pre_ldp, uint32_t pre_ldq, uint32_t pre_h_kred, uint32_t pre_route
+#define DQN_DQDA_PRELOAD_WORDS(w) (w).W, (w).X4, (w).aout16, (w).P, (w).Q, (w).ldp, (w).ldq, (w).h_kred, (w).route
+// what a workgroup's routing and first loads need, from either source
+struct DqdaFirst { int H, row_tiles, tiles; const float* W; const float* X4; const float* aout16; };
+__host__ __device__ __forceinline__ DqdaFirst dqda_preload_decode(const DqdaPreload& w) {
+  DqdaFirst f;
+  f.H = (int)(w.h_kred & 0xFFFFu);
+  f.row_tiles = (int)((w.route >> 1) & 0xFFFFu);
+  f.tiles = f.row_tiles * (int)(w.route >> 17);
+  f.W = w.W; f.X4 = w.X4; f.aout16 = w.aout16;
+  return f;
+}
+inline DqdaPreload make_dqda_preload(const DqdaHeadArgs& a, int row_tiles, bool off) {
+  DqdaPreload w{};
+  const int chunks = a.dxc != nullptr ? 1 : (a.H + 255) / 256;
+  if (off || a.dZ16 != nullptr || a.X4 == nullptr) return w;
+  if (a.H < 1 || a.H > 0xFFFF || a.pr.Kred < 0 || a.pr.Kred > 0xFFFF || row_tiles < 1 || row_tiles > 0xFFFF || chunks > 0x7FFF) return w;
+  if (a.pr.ldp < 0 || a.pr.ldp > kMaxLeadingDim || a.pr.ldq < 0 || a.pr.ldq > kMaxLeadingDim) return w;
+  w.W = a.W; w.X4 = a.X4; w.aout16 = a.aout16; w.P = a.pr.P; w.Q = a.pr.Q;
+  w.ldp = (uint32_t)a.pr.ldp; w.ldq = (uint32_t)a.pr.ldq;
+  w.h_kred = (uint32_t)a.H | (uint32_t)a.pr.Kred << 16;
+  w.route = kPreValid | (uint32_t)row_tiles << 1 | (uint32_t)chunks << 17;
+  return w;
+}
+// tile workgroup blk (f.tiles of them; the riders behind them are the kernel's business): pr = the narrow tile's problem (fp32 form)
+template <bool F16>
+__device__ __forceinline__ void dqda_head_block(const DqdaHeadArgs& a, const DqdaFirst& f, const GemmProblem& pr, const int blk,
+                                                float* smem, float (*s_d)[17], float* s_dy) {
+  const int rt = blk % f.row_tiles, cc = blk / f.row_tiles;
   const int tid = threadIdx.x, q0 = rt * 16;
   // (round 6: any tower-top width — the reference's own tower ends in 128 units; threads beyond it keep column H - 1's loads, take
   // part in the tile and the barriers, and store nothing)
-  const bool live = (cc << 8) + tid < a.H;
-  const int k = live ? (cc << 8) + tid : a.H - 1;
+  const bool live = (cc << 8) + tid < f.H;
+  const int k = live ? (cc << 8) + tid : f.H - 1;
   // everything the head part needs that does not depend on dQ/da goes out first: this thread's ten head weights, its column of
   // the 16 tower-top rows, and (160 threads) one output of mu(s)
   float wh[kNO], xv[16];
 #pragma unroll
-  for (int j = 0; j < kNO; ++j) wh[j] = a.W[(size_t)j * a.H + k];
+  for (int j = 0; j < kNO; ++j) wh[j] = f.W[(size_t)j * f.H + k];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) xv[r] = F16 ? (float)a.X416[(size_t)(q0 + r) * a.H + k] : a.X4[(size_t)(q0 + r) * a.H + k];
+  for (int r = 0; r < 16; ++r) xv[r] = F16 ? (float)a.X416[(size_t)(q0 + r) * f.H + k] : f.X4[(size_t)(q0 + r) * f.H + k];
   float out = 0.0f;
-  if (tid < 16 * kNO) out = a.aout16[(size_t)(q0 + tid / kNO) * kAP + tid % kNO];
+  if (tid < 16 * kNO) out = f.aout16[(size_t)(q0 + tid / kNO) * kAP + tid % kNO];
   f32x4 v;
   float sc16 = 0.0f;
   if constexpr (F16) {
     v = dgrad_narrow_tile16<8>(a.t16, rt, smem);
     // (dynamic loss scaling: the incoming panel carries ls_q x mult, the outgoing one ls_a x mult — DqdaHeadArgs::ls_mult, whose
-    // pointer came with the launch's one round of scalar loads above; the pair itself is read behind the tile)
+    // pointer came with the launch's one round of scalar loads; the pair itself is read behind the tile)
     float inv_ls = a.inv_ls;
     sc16 = a.scale16;
     if (a.ls_mult != nullptr) { inv_ls *= a.ls_mult[1]; sc16 *= a.ls_mult[0]; }
     v.x *= inv_ls; v.y *= inv_ls; v.z *= inv_ls; v.w *= inv_ls;
   }
-  else v = dgrad_narrow_tile<8>(a.pr, 0, rt, smem);
+  else v = dgrad_narrow_tile<8>(pr, 0, rt, smem);
   if (tid < 64) {                          // wave 0 holds the tile: lane (li, lg), register r = dX[row q0 + li][column 4 lg + r]
     const int li = tid & 15, lg = tid >> 4;
     s_d[li][(lg << 2) + 0] = v.x; s_d[li][(lg << 2) + 1] = v.y; s_d[li][(lg << 2) + 2] = v.z; s_d[li][(lg << 2) + 3] = v.w;
@@ -499,17 +541,47 @@ __global__ __launch_bounds__(256) void k_dqda_head_bwd(const DqdaHeadArgs a, con
     s0 += s1;
     const float dz = s0 * lrelu_mask(xv[r]);
     if (!live) continue;
-    if constexpr (F16) a.dZ16[(size_t)(q0 + r) * a.H + k] = (_Float16)(dz * sc16);
-    else a.dZ[(size_t)(q0 + r) * a.H + k] = dz;
+    if constexpr (F16) a.dZ16[(size_t)(q0 + r) * f.H + k] = (_Float16)(dz * sc16);
+    else a.dZ[(size_t)(q0 + r) * f.H + k] = dz;
   }
+}
+template <bool F16 = false>
+__global__ __launch_bounds__(256) void k_dqda_head_bwd(DQN_DQDA_PRELOAD_PARAMS, const DqdaHeadArgs a, const QHeadRider rider) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];     // the narrow dgrad's parking area (4 waves x 64 lanes x 16 B)
+  __shared__ float s_d[16][17];
+  __shared__ float s_dy[16 * kNO];
+  if constexpr (!F16) {
+    if (pre_route & kPreValid) {
+      // routing, the head part's first loads and the narrow tile's operands from the preloaded words: no scalar wait in front of them
+      const DqdaPreload w{pre_W, pre_X4, pre_aout16, pre_P, pre_Q, pre_ldp, pre_ldq, pre_h_kred, pre_route};
+      const DqdaFirst f = dqda_preload_decode(w);
+      const int blk = (int)blockIdx.x;
+      if (blk >= f.tiles) { q_head_rider(rider, blk - f.tiles); return; }
+      GemmProblem pr = a.pr;
+      pr.P = w.P; pr.Q = w.Q; pr.ldp = (int)w.ldp; pr.ldq = (int)w.ldq; pr.Kred = (int)(w.h_kred >> 16);
+      dqda_head_block<false>(a, f, pr, blk, smem, s_d, s_dy);
+      return;
+    }
+  }
+  // what routes the workgroup, what the head part's first loads need and the narrow tile's operands: ONE round of scalar loads
+  // (request_args, gemm_bodies.hip.h, has the reasoning; left alone: the tile count, then the head's pointers, then the tile's)
+  int blk = (int)blockIdx.x;
+  if constexpr (F16) asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X416), "s"(a.aout16), "s"(a.t16.P), "s"(a.t16.Q), "s"(a.t16.ldp), "s"(a.t16.Kred), "s"(a.ls_mult));
+  else asm volatile("" : "+s"(blk) : "s"(a.H), "s"(a.row_tiles), "s"(a.W), "s"(a.X4), "s"(a.aout16), "s"(a.pr.P), "s"(a.pr.Q), "s"(a.pr.ldp), "s"(a.pr.Kred));
+  DqdaFirst f;
+  f.H = a.H; f.row_tiles = a.row_tiles; f.tiles = a.row_tiles * (a.dxc != nullptr ? 1 : (a.H + 255) >> 8);
+  f.W = a.W; f.X4 = a.X4; f.aout16 = a.aout16;
+  if (blk >= f.tiles) { q_head_rider(rider, blk - f.tiles); return; }
+  dqda_head_block<F16>(a, f, a.pr, blk, smem, s_d, s_dy);
 }
 inline hipError_t dqda_head_bwd_launch(DqdaHeadArgs& a, const QHeadRider& rider, const LaunchOn& on) {
   a.row_tiles = a.rows / 16;
   a.pr.tiles_p = 1; a.pr.tiles_q = a.row_tiles; a.pr.tile_base = 0;
   // (dxc given: the tile alone, column chunk 0 of every row tile)
   const dim3 grid(a.row_tiles * (a.dxc != nullptr ? 1 : (a.H + 255) / 256) + rider.blocks);
-  if (a.dZ16 != nullptr) return launch(on, k_dqda_head_bwd<true>, grid, dim3(256), kNarrowDgradLds, a, rider);
-  return launch(on, k_dqda_head_bwd<false>, grid, dim3(256), kNarrowDgradLds, a, rider);
+  const DqdaPreload w = make_dqda_preload(a, a.row_tiles, on.no_preload);
+  if (a.dZ16 != nullptr) return launch(on, k_dqda_head_bwd<true>, grid, dim3(256), kNarrowDgradLds, DQN_DQDA_PRELOAD_WORDS(w), a, rider);
+  return launch(on, k_dqda_head_bwd<false>, grid, dim3(256), kNarrowDgradLds, DQN_DQDA_PRELOAD_WORDS(w), a, rider);
 }
 
 // ---- head backward for large minibatches (rows >= 1024) -------------------------------------

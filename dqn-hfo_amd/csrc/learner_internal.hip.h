@@ -319,11 +319,12 @@ struct RingUse {
 // Where one launch of family `fam` goes: `st`, and in timing mode a fresh event pair, filed in h->recs, that launch() has the
 // dispatch packet stamp.  The caller hands the result to exactly ONE launcher: events that no launch records cannot be read back.
 inline LaunchOn timed(H* h, Family fam, hipStream_t st) {
-  if (!h->timing) return st;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipEventCreate(&a); hipEventCreate(&b);
-  h->recs.push_back({fam, a, b});
-  return {st, a, b};
+  LaunchOn on(st);
+  on.no_preload = (h->cfg.tuning_flags & DQNHIP_TUNE_NO_KERNARG_PRELOAD) != 0;
+  if (!h->timing) return on;
+  hipEventCreate(&on.start); hipEventCreate(&on.stop);
+  h->recs.push_back({fam, on.start, on.stop});
+  return on;
 }
 
 // ---- dense (Caffe order) <-> internal arena ----------------------------------

@@ -202,6 +202,10 @@ typedef struct dqnhip_config {
  * layers in a launch of their own (rounds 3-5), instead of the gather in the critic's optimiser launch and the first layers as riders
  * of the actor's optimiser launch (round 5).  Same bits. */
 #define DQNHIP_TUNE_LATE_GATHER 128
+/* No kernarg preload.  The chain's fp32 GEMM kernels and the two head kernels take, in front of their argument struct, up to 14 scalar words that gfx950
+ * delivers in SGPRs at wave launch (what a workgroup's first operand loads are addressed from); with this bit the host marks every
+ * such block "not valid" and the workgroups read everything from the argument struct, behind one uniform branch.  Same bits. */
+#define DQNHIP_TUNE_NO_KERNARG_PRELOAD 256
 
 typedef struct dqnhip_learner* dqnhip_handle;
 
