@@ -27,6 +27,11 @@ KIND_W, KIND_M, KIND_V, KIND_G = 0, 1, 2, 3       # (KIND_M / KIND_V: solver his
 SOLVERS = ("Adam", "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta")      # DQNHIP_SOLVER_*, by value: Caffe's type strings
 
 
+LR_POLICIES = ("fixed", "step", "exp", "inv", "multistep", "poly", "sigmoid")      # DQNHIP_LR_*, by value: Caffe's lr_policy strings
+LR_MAX_STEPVALUES = 16                                                           # DQNHIP_LR_MAX_STEPVALUES
+REGULARIZATIONS = ("L2", "L1")                                                   # DQNHIP_REG_*, by value: Caffe's regularization_type strings
+
+
 class Config(C.Structure):
     """struct dqnhip_config (include/dqnhip.h)."""
     _fields_ = [
@@ -40,6 +45,8 @@ class Config(C.Structure):
         ("seed", C.c_uint64), ("stream", C.c_void_p), ("grad_arena", C.c_void_p),
         ("grad_arena_bytes", C.c_size_t), ("precision", C.c_int32), ("loss_scale", C.c_float),
         ("solver_type", C.c_int32), ("rms_decay", C.c_float),
+        ("lr_policy", C.c_int32), ("lr_gamma", C.c_float), ("lr_power", C.c_float), ("lr_stepsize", C.c_int32), ("lr_max_iter", C.c_int32),
+        ("lr_n_stepvalue", C.c_int32), ("lr_stepvalue", C.c_int32 * LR_MAX_STEPVALUES), ("weight_decay", C.c_float), ("regularization_type", C.c_int32),
         ("tuning_flags", C.c_int32),
         ("loss_scale_mode", C.c_int32), ("loss_scale_growth_interval", C.c_int32),
         ("loss_scale_min_mult", C.c_float), ("loss_scale_max_mult", C.c_float),
@@ -56,7 +63,8 @@ class LossScaleState(C.Structure):
 class UpdatePlan(C.Structure):
     """struct dqnhip_update_plan (include/dqnhip.h)."""
     _fields_ = [("struct_size", C.c_int32), ("forms", C.c_int32), ("launches_single", C.c_int32), ("launches_graph_first", C.c_int32),
-                ("launches_in_graph", C.c_int32), ("updates_per_graph", C.c_int32), ("collectives", C.c_int32), ("solver_type", C.c_int32)]
+                ("launches_in_graph", C.c_int32), ("updates_per_graph", C.c_int32), ("collectives", C.c_int32), ("solver_type", C.c_int32),
+                ("lr_policy", C.c_int32), ("regularised", C.c_int32)]
 
 
 class PerConfig(C.Structure):
@@ -137,6 +145,8 @@ H = C.c_void_p
 SIGNATURES = {
     "dqnhip_default_config": (None, [C.POINTER(Config), C.c_int32]),
     "dqnhip_solver_name": (C.c_char_p, [C.c_int32]),
+    "dqnhip_lr_policy_name": (C.c_char_p, [C.c_int32]),
+    "dqnhip_get_learning_rate": (C.c_int, [H, C.c_int32, fp]),
     "dqnhip_grad_arena_bytes": (C.c_size_t, [C.POINTER(Config)]),
     "dqnhip_last_error": (C.c_char_p, []),
     "dqnhip_create": (C.c_int, [C.POINTER(Config), C.POINTER(H)]),

@@ -41,6 +41,14 @@ DEFINE_bool(snapshot_memory, true, "Snapshot the replay memory along with the ne
 DEFINE_double(beta, .5, "Mix between off-policy and on-policy updates.");
 // MI355X learner flags (no counterpart in the reference; defaults reproduce its behaviour)
 DEFINE_int32(minibatch, kMinibatchSize, "Minibatch size of the HIP learner (reference: kMinibatchSize = 32); multiple of 32.");
+DEFINE_double(lr_gamma, 0, "-lr_policy step / exp / inv / multistep / sigmoid: Caffe's SolverParameter.gamma (NOT the discount: that is -gamma). "
+              "0: what the solver parameters carry (the reference's driver sets none: 0).");
+DEFINE_double(lr_power, 0, "-lr_policy inv / poly: SolverParameter.power. 0: what the solver parameters carry.");
+DEFINE_int32(lr_stepsize, 0, "-lr_policy step / sigmoid: SolverParameter.stepsize. 0: what the solver parameters carry.");
+DEFINE_string(lr_stepvalues, "", "-lr_policy multistep: SolverParameter.stepvalue as a comma-separated list, strictly increasing (at most 16). "
+              "Empty: what the solver parameters carry.");
+DEFINE_double(weight_decay, 0, "SolverParameter.weight_decay: SGDSolver::Regularize inside the optimiser pass (0: none, or what the solver parameters carry).");
+DEFINE_string(regularization_type, "", "L2 or L1 (SolverParameter.regularization_type). Empty: what the solver parameters carry (L2).");
 DEFINE_int32(select_actions_cap, 0, "Largest batch SelectActions accepts. 0: the reference's CHECK_LE(states_batch.size(), kMinibatchSize) "
                                     "(src/dqn.cpp:699) with this learner's -minibatch; -1: any batch (the device path has no MemoryData layer); n > 0: n.");
 DEFINE_int32(hip_device, 0, "HIP device ordinal of this process's learners.");
@@ -285,10 +293,49 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
       << "actor and critic solvers must share momentum / momentum2 / delta / clip_gradients";
   c.momentum = critic_solver_param_.momentum(); c.momentum2 = critic_solver_param_.momentum2();
   c.delta = critic_solver_param_.delta(); c.clip_gradients = critic_solver_param_.clip_gradients();
-  // -lr_policy (src/dqn_main.cpp:36, 255-256): the fused optimiser pass applies base_lr as it stands, i.e. Caffe's "fixed" policy
-  // (the reference's default); anything else would silently train with a different schedule than the user asked for
-  for (const caffe::SolverParameter* sp : {&actor_solver_param_, &critic_solver_param_})
-    CHECK(sp->lr_policy().empty() || sp->lr_policy() == "fixed") << "only -lr_policy fixed is implemented (got '" << sp->lr_policy() << "')";
+  // -lr_policy / -max_iter (src/dqn_main.cpp:36-37, 249-256) and what else SGDSolver::GetLearningRate / Regularize read of the solver
+  // parameters: ONE schedule and ONE decay serve both nets (the base rates are the solvers' own), so the two must agree.  The driver
+  // sets the policy and max_iter alone; the adaptor's -lr_* / -weight_decay / -regularization_type flags supply the rest.
+  {
+    const caffe::SolverParameter &a = actor_solver_param_, &k = critic_solver_param_;
+    bool same = a.lr_policy() == k.lr_policy() && a.max_iter() == k.max_iter() && a.gamma() == k.gamma() && a.power() == k.power() && a.stepsize() == k.stepsize() &&
+                a.weight_decay() == k.weight_decay() && a.regularization_type() == k.regularization_type() && a.stepvalue_size() == k.stepvalue_size();
+    for (int i = 0; same && i < a.stepvalue_size(); ++i) same = a.stepvalue(i) == k.stepvalue(i);
+    CHECK(same) << "actor and critic solvers must share lr_policy / max_iter / gamma / power / stepsize / stepvalue / weight_decay / regularization_type";
+    const std::string policy = k.lr_policy().empty() ? "fixed" : k.lr_policy();
+    c.lr_policy = -1;
+    for (int p = 0; dqnhip_lr_policy_name(p) != nullptr; ++p)
+      if (policy == dqnhip_lr_policy_name(p)) c.lr_policy = p;
+    CHECK(c.lr_policy >= 0) << "Unknown learning rate policy: " << policy;
+    c.lr_gamma = FLAGS_lr_gamma != 0 ? (float)FLAGS_lr_gamma : k.gamma();
+    c.lr_power = FLAGS_lr_power != 0 ? (float)FLAGS_lr_power : k.power();
+    c.lr_stepsize = FLAGS_lr_stepsize != 0 ? FLAGS_lr_stepsize : k.stepsize();
+    c.lr_max_iter = k.max_iter();
+    std::vector<int> sv;
+    if (!FLAGS_lr_stepvalues.empty()) {
+      std::stringstream ss(FLAGS_lr_stepvalues);
+      for (std::string tok; std::getline(ss, tok, ',');) {
+        char* end = nullptr;
+        const long v = strtol(tok.c_str(), &end, 10);
+        CHECK(end != tok.c_str() && *end == 0) << "-lr_stepvalues: '" << tok << "' is not an integer (a comma-separated list, e.g. 1000,5000)";
+        sv.push_back((int)v);
+      }
+    } else for (int i = 0; i < k.stepvalue_size(); ++i) sv.push_back(k.stepvalue(i));
+    CHECK_LE(sv.size(), (size_t)DQNHIP_LR_MAX_STEPVALUES) << "lr_policy multistep: 1 to " << DQNHIP_LR_MAX_STEPVALUES << " stepvalues required";
+    c.lr_n_stepvalue = (int)sv.size();
+    for (size_t i = 0; i < sv.size(); ++i) c.lr_stepvalue[i] = sv[i];
+    c.weight_decay = FLAGS_weight_decay != 0 ? (float)FLAGS_weight_decay : k.weight_decay();
+    const std::string reg = !FLAGS_regularization_type.empty() ? FLAGS_regularization_type : k.regularization_type();
+    CHECK(reg == "L2" || reg == "L1") << "Unknown regularization type: " << reg;
+    c.regularization_type = reg == "L1" ? DQNHIP_REG_L1 : DQNHIP_REG_L2;
+    if (c.lr_policy != DQNHIP_LR_FIXED || c.weight_decay != 0) {
+      // v1: a single learner without diagnostics (the library refuses the same; here it is the driver's abort, before anything is allocated)
+      CHECK_LE(FLAGS_debug_info_iter, 0) << "-debug_info_iter is not available with -lr_policy " << policy << " / -weight_decay " << c.weight_decay
+                                         << " (the diagnostics price the step as lr x Adam's correction)";
+      CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-lr_policy " << policy << " / -weight_decay " << c.weight_decay
+                                                               << " are single-learner options (-dp_world 1, no -dp_rendezvous)";
+    }
+  }
   // -solver (src/dqn_main.cpp:30 -> SolverParameter::set_type -> SolverRegistry::CreateSolver, src/dqn.cpp:628-629): Caffe's six type
   // strings; the fused optimiser pass runs ONE rule, so the two solvers must name the same type (the driver sets both from the flag)
   CHECK(actor_solver_param_.type() == critic_solver_param_.type()) << "actor and critic solvers must be of the same type (got '"

@@ -235,6 +235,9 @@ GatherArgs gather_args(H* h, const int* idx_dev, int pos) {
   // the counters stay gbase + pos, as in a sampled graph
   if (h->cap_idx != nullptr && pos > 0) g.idx_in = h->cap_idx + (size_t)pos * h->B;
   g.blocks = (h->B + 3) / 4 + 1;
+  g.sched = h->sched_dev;
+  // k_sched_soft<> of a solver without a bias correction reads the slot too: 0 makes the correction exactly 1 (GatherArgs::sched)
+  if (sched_family(h) && h->cfg.solver_type != DQNHIP_SOLVER_ADAM) { g.beta1 = 0.0f; g.beta2 = 0.0f; }
   return g;
 }
 
@@ -273,6 +276,33 @@ int adam_launch(H* h, hipStream_t st, int net, const float* partial, int n_parti
   // A learner whose solver is not Adam reaches k_solver_soft<> / k_solver_soft_gather<> and nothing else (solver_kernels.hip.h): the
   // same arguments (beta2's slot carries rms_decay: solver_hyper), the same grid rule, the same timing family; no first-layer riders
   const int solver = h->cfg.solver_type;
+  // A learner with an lr policy: the slot corr_pre points to holds the update's whole step scale (GatherArgs::sched), so the pass
+  // multiplies it by 1 — an Adam learner without a decay stays on the tuned kernels below, riders included.  Everything else with a
+  // policy or a decay runs k_sched_soft<> / k_sched_soft_gather<> (solver_kernels.hip.h), on the other solvers' schedule.
+  if (has_policy(h) || sched_family(h)) {
+    if (!corr_pre) return fail("adam_launch: a learner with lr_policy %s / weight_decay %g steps inside an update only (the pass reads the scalars its gather leaves in DevState)",
+                               dqnhip_lr_policy_name(h->cfg.lr_policy), (double)h->cfg.weight_decay);
+    if (has_policy(h)) a.lr = 1.0f;
+  }
+  if (sched_family(h)) {
+    if (fl != nullptr || early_gather != nullptr || next_l0 != nullptr)
+      return fail("internal: adam_launch: the optimiser launches of a learner with lr_policy %s / weight_decay %g carry no first-layer riders",
+                  dqnhip_lr_policy_name(h->cfg.lr_policy), (double)h->cfg.weight_decay);
+    if (solver != DQNHIP_SOLVER_ADAM) a.beta2 = h->cfg.rms_decay;
+    const DecayArgs d{h->cfg.weight_decay, h->cfg.regularization_type == DQNHIP_REG_L1 ? 1 : 0};
+    const LaunchOn on = timed(h, kFamAdam, st);
+    const int blocks = (int)std::min<size_t>((a.n4 + 255) / 256, (size_t)1536);
+    if (tick && h->cap_u >= 0 && h->cap_u + 1 < h->cap_n) {
+      const GatherArgs g = gather_args(h, nullptr, h->cap_u + 1);
+      const int ablocks = std::min(blocks, std::max(1536 - g.blocks, 1280));
+      h->sched_launches[1] += 1;
+      HIPCHK(sched_launch(solver, on, ablocks, a, d, &g));
+    } else {
+      h->sched_launches[0] += 1;
+      HIPCHK(sched_launch(solver, on, blocks, a, d, nullptr));
+    }
+    return 0;
+  }
   if (solver != DQNHIP_SOLVER_ADAM) {
     if (fl != nullptr || early_gather != nullptr || next_l0 != nullptr)
       return fail("internal: adam_launch: the %s solver's optimiser launches carry no first-layer riders", dqnhip_solver_name(solver));
@@ -912,6 +942,7 @@ int dqnhip_apply_update(dqnhip_handle h, int32_t net) {
   h->epoch += 1;
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
   if (h->next_phase != 0) return fail("dqnhip_apply_update: a phased update is in progress (next phase %d)", h->next_phase);
+  RC(sched_refuse(h, "dqnhip_apply_update"));
   HIPCHK(hipSetDevice(h->cfg.device));
   RC(sync_dirty16(h));
   const NetLayout& l = layout_of(h, net);
@@ -934,6 +965,7 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world) {
   h->epoch += 1;
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
   if (h->next_phase != 0) return fail("dqnhip_apply_update_sharded: a phased update is in progress (next phase %d)", h->next_phase);
+  RC(sched_refuse(h, "dqnhip_apply_update_sharded"));
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
     return fail("dqnhip_apply_update_sharded: the %s solver has no sharded form in this version (DESIGN.md 9); use dqnhip_apply_update", dqnhip_solver_name(h->cfg.solver_type));
   const NetLayout& l = layout_of(h, net);

@@ -1,7 +1,8 @@
 // learner_args.hip.h — the ARGUMENT layer: the plain structs and constants that host code and kernels share.  No __global__,
 // no launcher, nothing that instantiates a kernel: a host-only translation unit includes this (through learner_internal.hip.h)
 // and embeds no device code.  Layers, includes pointing downwards only:
-//   arguments   gemm_common.hip.h (GEMM problems, LaunchOn / launch, tails, flags), this header, gemm_plan.hip.h (the fp32 family's
+//   arguments   gemm_common.hip.h (GEMM problems, LaunchOn / launch, tails, flags), this header, lr_schedule.hip.h (Caffe's lr policies:
+//               one function for the host and the device), gemm_plan.hip.h (the fp32 family's
 //               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
 //   bodies      gemm_bodies.hip.h, update_bodies.hip.h, solver_bodies.hip.h (the optimiser pass of the solvers other than Adam):
 //               __device__ functions only
@@ -17,6 +18,7 @@
 #include <stdint.h>
 
 #include "gemm_common.hip.h"
+#include "lr_schedule.hip.h"      // LrSchedule, lr_rate: one text for the host and the scalars block of the gather
 
 namespace dqnhip {
 
@@ -143,6 +145,11 @@ struct GatherArgs {
   int ahead;
   int store_base;                   // 1 (first update of a multi-update graph): also store the live counters to gbase
   int blocks;
+  // A learner with an lr policy (device-resident, allocated at create; null: a fixed learner — the scalars block is the code it was):
+  // corr[net] then carries the update's whole step scale, lr_rate(iter) x the bias correction in one float32 multiply (Caffe's
+  // local_rate * correction), and the optimiser pass multiplies it by a.lr = 1.  A solver without a correction passes beta1 = beta2 = 0:
+  // sqrt(1 - 0) / (1 - 0) is exactly 1.  Last member: nothing before it moves.
+  const LrSchedule* sched;
 };
 
 // ---- head layers (head_fwd_kernels.hip.h, head_kernels.hip.h) ----------------------------------------------------------------

@@ -89,6 +89,8 @@ const char* dqnhip_solver_name(int32_t solver_type) {
   return solver_type >= 0 && solver_type <= DQNHIP_SOLVER_ADADELTA ? kNames[solver_type] : nullptr;
 }
 
+const char* dqnhip_lr_policy_name(int32_t lr_policy) { return lr_policy_name(lr_policy); }
+
 int dqnhip_get_config(dqnhip_handle h, dqnhip_config* out) {
   if (!h || !out) return fail("null argument");
   *out = h->cfg;
@@ -97,10 +99,11 @@ int dqnhip_get_config(dqnhip_handle h, dqnhip_config* out) {
 }
 
 size_t dqnhip_grad_arena_bytes(const dqnhip_config* cfg) {
-  if (validate(cfg)) return 0;
+  dqnhip_config full;
+  if (validate(cfg, &full)) return 0;
   NetLayout la, lc;
-  layout_init(la, cfg->state_size, *cfg, true);
-  layout_init(lc, cfg->state_size + kNO, *cfg, false);
+  layout_init(la, full.state_size, full, true);
+  layout_init(lc, full.state_size + kNO, full, false);
   return grad_arena_floats(la, lc) * sizeof(float);
 }
 
@@ -109,7 +112,9 @@ static int create_impl(H* h, const dqnhip_config* cfg);
 int dqnhip_create(const dqnhip_config* cfg, dqnhip_handle* out) {
   if (!out) return fail("out is null");
   *out = nullptr;
-  RC(validate(cfg));
+  dqnhip_config full;
+  RC(validate(cfg, &full));
+  cfg = &full;
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail("device %d not available (%d visible)", cfg->device, ndev);
@@ -154,6 +159,12 @@ static int create_impl(H* h, const dqnhip_config* cfg) {
   RC(dalloc(&r.act, (size_t)r.cap * kAP)); RC(dalloc(&r.reward, r.cap)); RC(dalloc(&r.mc, r.cap));
   HIPCHK(hipMalloc(&r.term, r.cap)); HIPCHK(hipMemsetAsync(r.term, 0, r.cap, h->stream));
   HIPCHK(hipMalloc(&h->st, sizeof(DevState))); HIPCHK(hipMemsetAsync(h->st, 0, sizeof(DevState), h->stream));
+  if (has_policy(h)) {      // (a fixed learner allocates nothing and passes null: GatherArgs::sched)
+    h->sched = schedule_of(*cfg);
+    HIPCHK(hipMalloc(&h->sched_dev, sizeof(LrSchedule)));
+    HIPCHK(hipMemcpyAsync(h->sched_dev, &h->sched, sizeof(LrSchedule), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
   HIPCHK(hipMalloc(&h->done_counter, sizeof(int))); HIPCHK(hipMemsetAsync(h->done_counter, 0, sizeof(int), h->stream));
   // panels and activations
   RC(dalloc(&h->Xa_s, (size_t)B * h->la.kp[0])); RC(dalloc(&h->Xa_n, (size_t)B * h->la.kp[0]));
@@ -301,6 +312,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   for (void* p : h->allocs16) hipFree(p);
   if (h->stage_dev) hipFree(h->stage_dev);
   if (h->shard_total) hipFree(h->shard_total);
+  if (h->sched_dev) hipFree(h->sched_dev);
   if (h->act_buf) hipFree(h->act_buf);
   for (int i = 0; i <= h->L; ++i) if (h->actp16[i]) hipFree(h->actp16[i]);
   if (h->actp16_out) hipFree(h->actp16_out);

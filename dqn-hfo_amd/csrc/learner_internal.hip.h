@@ -276,6 +276,9 @@ struct dqnhip_learner {
   int ix_next = 0;                      // the bank the next graph takes (round robin: the busy banks are the most recent ones, in order)
   hipGraphExec_t ix_graph[kIxBanks][kIxSizes] = {{nullptr}};   // [bank][16, 8, 4, 2, 1 updates]
   long long opt_launches[3] = {0, 0, 0};   // optimiser launches enqueued or captured: k_adam_soft*, k_solver_soft<>, k_solver_soft_gather<> (dqnhip_debug_read "optimiser_launches")
+  // lr policy / weight decay (cfg.lr_policy, cfg.weight_decay): the schedule as the device reads it (GatherArgs::sched; null: fixed)
+  LrSchedule sched{}; LrSchedule* sched_dev = nullptr;
+  long long sched_launches[2] = {0, 0};    // k_sched_soft<>, k_sched_soft_gather<> enqueued or captured (dqnhip_debug_read "sched_launches")
   int ix_nodes[kIxSizes] = {0};         // kernel nodes of the captured graph of each size (dqnhip_debug_read "indexed_graph_launches")
   const int* cap_idx = nullptr;         // while an indexed graph is captured / an indexed update runs eagerly: the bank's index slots ...
   float* cap_stats = nullptr;           // ... and its stats slots (device aliases); tick_args / gather_args read them
@@ -331,7 +334,15 @@ inline LaunchOn timed(H* h, Family fam, hipStream_t st) {
 void dense_to_arena(const NetLayout& l, const float* dense, std::vector<float>& arena);
 void arena_to_dense(const NetLayout& l, const std::vector<float>& arena, float* dense);
 inline const NetLayout& layout_of(const H* h, int net) { return (net & 1) ? h->lc : h->la; }
-int validate(const dqnhip_config* c);
+// validates *c — of today's struct_size, or of the size before the lr_policy .. regularization_type block existed — into *full
+int validate(const dqnhip_config* c, dqnhip_config* full);
+LrSchedule schedule_of(const dqnhip_config& c);
+inline bool has_policy(const H* h) { return h->cfg.lr_policy != DQNHIP_LR_FIXED; }
+inline bool has_decay(const H* h) { return h->cfg.weight_decay != 0.0f; }
+// does this learner's optimiser pass run k_sched_soft<>?  (an Adam learner with a policy and no decay keeps the tuned kernels)
+inline bool sched_family(const H* h) { return has_decay(h) || (has_policy(h) && h->cfg.solver_type != DQNHIP_SOLVER_ADAM); }
+// the v1 refusals of a learner with a policy or a decay: fails, as `what`, naming both
+int sched_refuse(const H* h, const char* what);
 bool is_pow2(float x);                                   // a positive, normal power of two (loss-scale multipliers)
 // shape predicates of the launch schedules (learner_plan.hip)
 bool bwd_layer_is_pair(const NetLayout& l, int i, int rows);

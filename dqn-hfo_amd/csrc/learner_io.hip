@@ -851,6 +851,16 @@ int dqnhip_set_iters(dqnhip_handle h, int32_t actor_iter, int32_t critic_iter) {
   return 0;
 }
 
+// the rate net's next step will apply: lr_rate (lr_schedule.hip.h), host build, at the net's current iteration
+int dqnhip_get_learning_rate(dqnhip_handle h, int32_t net, float* out) {
+  if (!h || !out) return fail("null argument");
+  if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
+  int32_t it[2] = {0, 0};
+  RC(dqnhip_get_iters(h, &it[0], &it[1]));
+  *out = lr_rate(schedule_of(h->cfg), net, it[net]);
+  return 0;
+}
+
 // ---- introspection ----------------------------------------------------------------------
 
 int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t count) {
@@ -861,6 +871,11 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   if (!strcmp(name, "optimiser_launches")) {      // [k_adam_soft*, k_solver_soft<>, k_solver_soft_gather<>] enqueued or captured so far
     if (count < 3) return fail("buffer too small for '%s'", name);
     for (int k = 0; k < 3; ++k) host[k] = (float)h->opt_launches[k];
+    return 0;
+  }
+  if (!strcmp(name, "sched_launches")) {          // [k_sched_soft<>, k_sched_soft_gather<>] enqueued or captured so far (a name of its own: "optimiser_launches" keeps its three words)
+    if (count < 2) return fail("buffer too small for '%s'", name);
+    for (int k = 0; k < 2; ++k) host[k] = (float)h->sched_launches[k];
     return 0;
   }
   if (!strcmp(name, "indexed_graph_launches")) {
@@ -1038,6 +1053,7 @@ int dqnhip_diag_collect(dqnhip_handle h, dqnhip_diag_report* out) {
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
     return fail("dqnhip_diag_collect: diagnostics are not available with the %s solver (the step, lag and moment records are defined through Adam's m and v: DESIGN.md 9)",
                 dqnhip_solver_name(h->cfg.solver_type));
+  RC(sched_refuse(h, "dqnhip_diag_collect"));      // (k_diag_prep prices the step as lr x adam_correction)
   if (h->dp_shard) return fail("dqnhip_diag_collect: diagnostics are not available with a sharded optimiser (DQNHIP_DP_SHARD_OPT: m and v of foreign slices are stale)");
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!h->diag && diag_build(h)) { diag_free(h); return 1; }

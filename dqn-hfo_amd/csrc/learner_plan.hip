@@ -82,9 +82,38 @@ bool is_pow2(float x) {
   return std::isfinite(x) && x >= 1.17549435e-38f && std::frexp(x, &e) == 0.5f;
 }
 
-int validate(const dqnhip_config* c) {
-  if (!c) return fail("config is null");
-  if (c->struct_size != (int32_t)sizeof(dqnhip_config)) return fail("dqnhip_config.struct_size %d != %zu (ABI mismatch)", c->struct_size, sizeof(dqnhip_config));
+static_assert(kLrFixed == DQNHIP_LR_FIXED && kLrStep == DQNHIP_LR_STEP && kLrExp == DQNHIP_LR_EXP && kLrInv == DQNHIP_LR_INV &&
+              kLrMultistep == DQNHIP_LR_MULTISTEP && kLrPoly == DQNHIP_LR_POLY && kLrSigmoid == DQNHIP_LR_SIGMOID &&
+              kLrMaxStepvalues == DQNHIP_LR_MAX_STEPVALUES && kRegL2 == DQNHIP_REG_L2 && kRegL1 == DQNHIP_REG_L1, "lr_schedule.hip.h mirrors dqnhip.h");
+
+LrSchedule schedule_of(const dqnhip_config& c) {
+  LrSchedule s{};
+  s.policy = c.lr_policy; s.base_lr[0] = c.actor_lr; s.base_lr[1] = c.critic_lr; s.gamma = c.lr_gamma; s.power = c.lr_power;
+  s.stepsize = c.lr_stepsize; s.max_iter = c.lr_max_iter; s.n_stepvalue = c.lr_n_stepvalue;
+  for (int i = 0; i < kLrMaxStepvalues; ++i) s.stepvalue[i] = c.lr_stepvalue[i];
+  return s;
+}
+
+int sched_refuse(const H* h, const char* what) {
+  if (!has_policy(h) && !has_decay(h)) return 0;
+  return fail("%s: not available on a learner with lr_policy %s / weight_decay %g in this version (single learner, inside an update only, no diagnostics: DESIGN.md 9)",
+              what, dqnhip_lr_policy_name(h->cfg.lr_policy), (double)h->cfg.weight_decay);
+}
+
+int validate(const dqnhip_config* in, dqnhip_config* full) {
+  if (!in) return fail("config is null");
+  // the struct as it is, or as it was before the lr_policy .. regularization_type block was put in behind rms_decay (a caller compiled
+  // against that header: its tail — tuning_flags and the loss-scale fields — sits 96 bytes lower; the block reads as zero)
+  constexpr size_t kBlock0 = offsetof(dqnhip_config, lr_policy), kBlock1 = offsetof(dqnhip_config, tuning_flags);
+  if (in->struct_size == (int32_t)sizeof(dqnhip_config)) *full = *in;
+  else if (in->struct_size == (int32_t)(sizeof(dqnhip_config) - (kBlock1 - kBlock0))) {
+    memset(full, 0, sizeof *full);
+    memcpy(full, in, kBlock0);
+    memcpy((char*)full + kBlock1, (const char*)in + kBlock0, sizeof(dqnhip_config) - kBlock1);
+    full->struct_size = (int32_t)sizeof(dqnhip_config);
+  }
+  else return fail("dqnhip_config.struct_size %d != %zu (ABI mismatch)", in->struct_size, sizeof(dqnhip_config));
+  const dqnhip_config* c = full;
   if (c->minibatch <= 0 || c->minibatch % 32) return fail("minibatch must be a positive multiple of 32 (got %d)", c->minibatch);
   if (c->state_size < 1) return fail("state_size must be >= 1");
   if (c->num_hidden < 1 || c->num_hidden > kMaxL) return fail("num_hidden out of range");
@@ -122,6 +151,12 @@ int validate(const dqnhip_config* c) {
   }
   if (c->solver_type != DQNHIP_SOLVER_ADAM && c->dp_world > 1)
     return fail("the %s solver needs dp_world = 1 (got %d): its data-parallel forms do not exist in this version", solver, c->dp_world);
+  // SGDSolver::GetLearningRate / Regularize (lr_schedule.hip.h has the refusals)
+  char msg[256];
+  if (lr_schedule_check(schedule_of(*c), c->weight_decay, c->regularization_type, msg, sizeof msg)) return fail("%s", msg);
+  if ((c->lr_policy != DQNHIP_LR_FIXED || c->weight_decay != 0.0f) && c->dp_world > 1)
+    return fail("lr_policy %s / weight_decay %g need dp_world = 1 (got %d): their data-parallel forms do not exist in this version",
+                dqnhip_lr_policy_name(c->lr_policy), (double)c->weight_decay, c->dp_world);
   return 0;
 }
 
@@ -212,6 +247,8 @@ UpdatePlan plan_of(const H* h) {
   // the first-layer riders step their slice with Adam's expression (adam_apply4): the other solvers' optimiser launches carry none —
   // the schedule DQNHIP_TUNE_SEPARATE_FIRST_LAYER | DQNHIP_TUNE_LATE_GATHER give an Adam learner
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM) { p.critic_l0 = false; p.early_l0 = false; }
+  // ... and neither do k_sched_soft<>'s (an lr policy on another solver, a weight decay on any)
+  if (sched_family(h)) { p.critic_l0 = false; p.early_l0 = false; }
   return p;
 }
 // ... while a multi-update graph is being captured (cap_u: the position of the update in it)

@@ -30,6 +30,17 @@ int state_refuse(const H* h, const char* what) {
   return 0;
 }
 
+// the LRSC section of a learner: its schedule's words (only the stepvalues in use: what lies behind them is not the learner's), decay, kind
+LrSection lr_section_of(const dqnhip_config& c) {
+  const LrSchedule s = schedule_of(c);
+  LrSection o{};
+  o.policy = s.policy; o.base_lr[0] = s.base_lr[0]; o.base_lr[1] = s.base_lr[1]; o.gamma = s.gamma; o.power = s.power;
+  o.stepsize = s.stepsize; o.max_iter = s.max_iter; o.n_stepvalue = s.n_stepvalue;
+  for (int i = 0; i < s.n_stepvalue && i < kLrMaxStepvalues; ++i) o.stepvalue[i] = s.stepvalue[i];
+  o.weight_decay = c.weight_decay; o.regularization_type = c.regularization_type;
+  return o;
+}
+
 // the window [head, head + size) of a ring array with rows of `width` bytes at a pitch of `pitch` bytes <-> dense host rows, logical order
 int window_copy(const H* h, void* dev, size_t pitch, void* host, size_t width, int head, int size, bool to_host) {
   const int cap = h->ring.cap;
@@ -63,6 +74,7 @@ struct StateJob {
   std::vector<uint8_t> user;
   HostSection host{};
   bool has_solver = false; SolverSection solver{};      // a learner whose solver is not Adam
+  bool has_lr = false; LrSection lr{};                  // a learner with an lr policy or a weight decay
   PerSection per{};                      // p_max comes from the record
   dqnhip_state_info_t info{};            // the config's share; the record fills the rest
   int device = 0, cap = 0;
@@ -195,6 +207,7 @@ int write_job(StateAsync* a, std::string* err) {
   for (int net = 0; net < 4; ++net) out.push_back({kTagW[net], net, nullptr, 0});
   for (int net = 0; net < 2; ++net) { out.push_back({kTagM[net], 4 + 2 * net, nullptr, 0}); out.push_back({kTagV[net], 5 + 2 * net, nullptr, 0}); }
   if (j.has_solver) out.push_back({kTagSolver, -1, &j.solver, sizeof j.solver});
+  if (j.has_lr) out.push_back({kTagLrSched, -1, &j.lr, sizeof j.lr});
   out.push_back({kTagDev, -1, &devs, sizeof devs});
   if (j.has_ls) out.push_back({kTagLossScale, -1, &ls, sizeof ls});
   out.push_back({kTagHost, -1, &j.host, sizeof j.host});
@@ -559,6 +572,8 @@ int dqnhip_save_state_async(dqnhip_handle h, const char* filename, int32_t flags
   j.host = HostSection{h->sample_states_calls, h->cfg.seed};
   j.has_solver = h->cfg.solver_type != DQNHIP_SOLVER_ADAM;
   j.solver = SolverSection{h->cfg.solver_type, h->cfg.rms_decay, {0, 0}};
+  j.has_lr = has_policy(h) || has_decay(h);
+  j.lr = lr_section_of(h->cfg);
   if (has_per) {
     const dqnhip_per_config& pc = h->per->cfg;
     j.per = PerSection{pc.alpha, pc.beta0, pc.beta_anneal_iters, pc.eps, pc.seed, 0.0f, 0, (int64_t)h->per->syncs};
@@ -680,6 +695,9 @@ int dqnhip_save_state(dqnhip_handle h, const char* filename, int32_t flags, cons
   // a learner whose solver is not Adam says so; an Adam learner's file is what it was before the other solvers existed
   const SolverSection solver{h->cfg.solver_type, h->cfg.rms_decay, {0, 0}};
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM) sec.push_back({kTagSolver, &solver, sizeof solver});
+  // ... and so does a learner with an lr policy or a weight decay (SOLV's rules: without either, the file is byte for byte what it was)
+  const LrSection lrs = lr_section_of(h->cfg);
+  if (has_policy(h) || has_decay(h)) sec.push_back({kTagLrSched, &lrs, sizeof lrs});
   const DevSection dev{st.actor_iter, st.critic_iter, st.update_counter, st.critic_loss, st.avg_q, st.flags, st.skipped_steps};
   sec.push_back({kTagDev, &dev, sizeof dev});
   const LossScaleSection ls{{st.ls_mult[0][0], st.ls_mult[1][0]}, {st.ls_good[0], st.ls_good[1]}, {st.ls_backoffs[0], st.ls_backoffs[1]},
@@ -755,6 +773,22 @@ int dqnhip_load_state(dqnhip_handle h, const char* filename) {
   if (in.solver_type != h->cfg.solver_type)
     return fail("dqnhip_load_state: %s: the file was written by a learner with the %s solver, this learner's solver is %s (the histories mean something else)", filename,
                 dqnhip_solver_name(in.solver_type), dqnhip_solver_name(h->cfg.solver_type));
+  // the schedule and the decay: both sides must agree, in either direction (the rate of every later step depends on them)
+  {
+    const Entry* e = p.find(kTagLrSched);
+    const bool mine = has_policy(h) || has_decay(h);
+    if (e && e->bytes != sizeof(LrSection))
+      return fail("dqnhip_load_state: %s: section LRSC holds %llu bytes, expected %zu", filename, (unsigned long long)e->bytes, sizeof(LrSection));
+    LrSection theirs{};
+    if (e) memcpy(&theirs, p.at(e), sizeof theirs);
+    const LrSection ours = lr_section_of(h->cfg);
+    if ((e != nullptr) != mine || (e && memcmp(&theirs, &ours, sizeof ours) != 0)) {
+      const char* tn = e ? dqnhip_lr_policy_name(theirs.policy) : "fixed";
+      return fail("dqnhip_load_state: %s: the file was written by a learner with lr_policy %s / weight_decay %g, this learner has lr_policy %s / weight_decay %g "
+                  "(or another parameter of the schedule, the base rates or the kind of decay differs)", filename, tn ? tn : "?", e ? (double)theirs.weight_decay : 0.0,
+                  dqnhip_lr_policy_name(h->cfg.lr_policy), (double)h->cfg.weight_decay);
+    }
+  }
   const bool with_mem = in.has_memory != 0;
   // a section of exactly `bytes` bytes
   auto need = [&](uint32_t tag, uint64_t bytes, const uint8_t** out) -> int {

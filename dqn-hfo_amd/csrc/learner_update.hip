@@ -233,19 +233,13 @@ static int ix_run(H* h, const int32_t* idx, int sz, int kind) {
   return 0;
 }
 
-}  // namespace dqnhip_host
-
-extern "C" {
-
-int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
-  if (!h || !out) return fail("null argument");
-  if (out->struct_size != (int32_t)sizeof(dqnhip_update_plan)) return fail("dqnhip_update_plan.struct_size %d != %zu (ABI mismatch)", out->struct_size, sizeof(dqnhip_update_plan));
-  if (h->next_phase != 0) return fail("dqnhip_get_update_plan: a phased update is in progress (next phase %d)", h->next_phase);
-  if (h->timing) return fail("dqnhip_get_update_plan: kernel timing is on (timed launches are not captured)");
+// dqnhip_get_update_plan's report, whole (the caller's struct may be the shorter one of an earlier header)
+static int update_plan_fill(H* h, dqnhip_update_plan* out) {
   HIPCHK(hipSetDevice(h->cfg.device));
   const UpdatePlan p = plan_of(h);
   memset(out, 0, sizeof *out);
   out->struct_size = (int32_t)sizeof *out;
+  out->lr_policy = h->cfg.lr_policy; out->regularised = has_decay(h) ? 1 : 0;
   out->forms = (p.fp16 ? DQNHIP_PLAN_FP16 : 0) | (p.dp ? DQNHIP_PLAN_DATA_PARALLEL : 0) | (p.shifted_c ? DQNHIP_PLAN_BWD_SHIFTED_CRITIC : 0) |
                (p.shifted_a ? DQNHIP_PLAN_BWD_SHIFTED_ACTOR : 0) | (p.head_rides_c ? DQNHIP_PLAN_HEAD_WGRAD_RIDES_CRITIC : 0) |
                (p.head_rides_a ? DQNHIP_PLAN_HEAD_WGRAD_RIDES_ACTOR : 0) | (p.fuse_q ? DQNHIP_PLAN_Q_TRAIN_IN_DGRAD : 0) |
@@ -263,6 +257,25 @@ int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
   RC(count_launches(h, true, 1, &nf));
   RC(count_launches(h, true, 2, &n2));
   out->launches_single = n1; out->launches_graph_first = nf; out->launches_in_graph = n2 - nf;
+  return 0;
+}
+
+}  // namespace dqnhip_host
+
+extern "C" {
+
+int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out) {
+  if (!h || !out) return fail("null argument");
+  // the struct as it is, or as it was before lr_policy / regularised were appended (the caller gets the words it knows)
+  const int32_t asked = out->struct_size;
+  if (asked != (int32_t)sizeof(dqnhip_update_plan) && asked != (int32_t)offsetof(dqnhip_update_plan, lr_policy))
+    return fail("dqnhip_update_plan.struct_size %d != %zu (ABI mismatch)", out->struct_size, sizeof(dqnhip_update_plan));
+  if (h->next_phase != 0) return fail("dqnhip_get_update_plan: a phased update is in progress (next phase %d)", h->next_phase);
+  if (h->timing) return fail("dqnhip_get_update_plan: kernel timing is on (timed launches are not captured)");
+  dqnhip_update_plan full;
+  RC(update_plan_fill(h, &full));
+  memcpy(out, &full, (size_t)asked);
+  out->struct_size = asked;
   return 0;
 }
 

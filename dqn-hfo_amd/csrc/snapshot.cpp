@@ -17,6 +17,7 @@
 
 #include "../../include/dqnhip.h"
 #include "snapshot_codec.h"
+#include "lr_schedule.hip.h"
 
 namespace fs = std::filesystem;
 
@@ -261,13 +262,22 @@ std::string esc(const std::string& s) {            // the reference concatenates
 // caffe.SolverState{iter = 1, learned_net = 2, history = 3, current_step = 4}.  SGDSolver::PreSolve gives every solver one history
 // blob per parameter; AdamSolver and AdaDeltaSolver append a second set: history 1 of every blob, then history 2 of every blob
 // (Adam: all m, then all v).  h2 is read by a two-history solver only.
-std::string solverstate_proto(const std::vector<ParamBlob>& tbl, int iter, const std::string& learned_net, const float* h1, const float* h2, bool two) {
+// current_step: what SGDSolver::GetLearningRate last left in current_step_ — the step / multistep count of the last step taken,
+// iteration iter - 1 (0 before the first step and under every other policy).  Restore ignores it: the schedule here is stateless.
+int current_step_of(const dqnhip_config& c, int iter) {
+  if (iter <= 0 || (c.lr_policy != DQNHIP_LR_STEP && c.lr_policy != DQNHIP_LR_MULTISTEP)) return 0;
+  dqnhip::LrSchedule s{};
+  s.policy = c.lr_policy; s.stepsize = c.lr_stepsize; s.n_stepvalue = c.lr_n_stepvalue;
+  for (int i = 0; i < dqnhip::kLrMaxStepvalues; ++i) s.stepvalue[i] = c.lr_stepvalue[i];
+  return dqnhip::lr_current_step(s, iter - 1);
+}
+std::string solverstate_proto(const std::vector<ParamBlob>& tbl, int iter, const std::string& learned_net, const float* h1, const float* h2, bool two, int current_step) {
   std::string o;
   put_int(o, 1, iter);
   put_bytes(o, 2, learned_net);
   for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, h1 + b.offset, b.count));
   if (two) for (auto& b : tbl) put_bytes(o, 3, blob_proto(b.shape, h2 + b.offset, b.count));
-  put_int(o, 4, 0);                                                                           // current_step
+  put_int(o, 4, current_step);
   return o;
 }
 
@@ -289,7 +299,7 @@ std::string caffemodel_bytes(const dqnhip_config& c, int net, const float* w) {
 std::string solverstate_bytes(const dqnhip_config& c, int net, int iter, const std::string& learned_net, const float* h1, const float* h2) {
   std::vector<ParamBlob> tbl; size_t total = 0;
   blob_table_of(c, net, tbl, total);
-  return solverstate_proto(tbl, iter, learned_net, h1, h2, two_histories(c.solver_type));
+  return solverstate_proto(tbl, iter, learned_net, h1, h2, two_histories(c.solver_type), current_step_of(c, iter));
 }
 int publish_file(const std::string& path, const std::string& data, std::string* err) {
   const std::string tmp = path + ".tmp";
@@ -368,7 +378,7 @@ int dqnhip_solver_snapshot(dqnhip_handle h, int32_t net, const char* prefix, int
   std::vector<float> m(total), v(total);
   if (dqnhip_get_params(h, net, DQNHIP_KIND_M, m.data(), total)) return 1;
   if (two && dqnhip_get_params(h, net, DQNHIP_KIND_V, v.data(), total)) return 1;
-  if (!write_file(base + ".solverstate", solverstate_proto(tbl, iter, base + ".caffemodel", m.data(), v.data(), two))) return fail("cannot write " + base + ".solverstate");
+  if (!write_file(base + ".solverstate", solverstate_proto(tbl, iter, base + ".caffemodel", m.data(), v.data(), two, current_step_of(cfg, iter)))) return fail("cannot write " + base + ".solverstate");
   if (iter_out) *iter_out = iter;
   return 0;
 }

@@ -26,6 +26,7 @@ constexpr uint32_t kTagRing = tag4('R', 'I', 'N', 'G'), kTagStates = tag4('R', '
                    kTagAct = tag4('R', 'A', 'C', 'T'), kTagReward = tag4('R', 'R', 'E', 'W'), kTagMc = tag4('R', 'M', 'C', 'T'),
                    kTagTerm = tag4('R', 'T', 'R', 'M');
 constexpr uint32_t kTagSolver = tag4('S', 'O', 'L', 'V');      // written by a learner whose solver is not Adam, right behind ADV1
+constexpr uint32_t kTagLrSched = tag4('L', 'R', 'S', 'C');     // written by a learner with an lr policy or a weight decay, behind ADV1 / SOLV
 constexpr uint32_t kTagPerCfg = tag4('P', 'E', 'R', 'C'), kTagPerLeaves = tag4('P', 'E', 'R', 'L'), kTagUser = tag4('U', 'S', 'E', 'R');
 
 // the fixed-size sections, as they lie in the file (little endian, no padding inside)
@@ -33,9 +34,13 @@ struct DevSection { int32_t actor_iter, critic_iter; uint64_t update_counter; fl
 struct LossScaleSection { float mult[2]; int32_t good[2], backoffs[2], growths[2]; };      // [actor, critic]
 struct HostSection { uint64_t sample_states_calls, seed; };
 struct SolverSection { int32_t solver_type; float rms_decay; int32_t reserved[2]; };
+// the words of LrSchedule (lr_schedule.hip.h), then the decay and its kind
+struct LrSection { int32_t policy; float base_lr[2]; float gamma, power; int32_t stepsize, max_iter, n_stepvalue; int32_t stepvalue[16];
+                   float weight_decay; int32_t regularization_type; };
 struct RingSection { int32_t ring_head, ring_size; };
 struct PerSection { float alpha, beta0; int32_t beta_anneal_iters; float eps; uint64_t seed; float p_max; int32_t reserved; int64_t syncs; };
 static_assert(sizeof(SolverSection) == 16, "SOLV is 16 bytes");
+static_assert(sizeof(LrSection) == 104, "LRSC is 104 bytes");
 static_assert(sizeof(DevSection) == 32 && sizeof(LossScaleSection) == 32 && sizeof(HostSection) == 16 && sizeof(RingSection) == 8 &&
               sizeof(PerSection) == 40, "the sections have no padding");
 

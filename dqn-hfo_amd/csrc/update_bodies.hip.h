@@ -34,6 +34,13 @@ __device__ __forceinline__ float adam_correction(float beta1, float beta2, int t
   return (float)(sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
 }
 
+// A scheduled learner's step scale (GatherArgs::sched): the rate of iteration `iter` times the bias correction, both rounded to
+// float32 first.  Out of line: the scalars block of a fixed learner keeps its registers and its code.
+__device__ __noinline__ float lr_rate_scaled(const LrSchedule& s, int net, int iter, float corr) {
+#pragma clang fp contract(off)
+  return lr_rate(s, net, iter) * corr;
+}
+
 // ---- minibatch gather (k_gather; rider of k_adam_soft_gather / k_adam_soft_fwd1_gather) ---------------------------------------
 __device__ __forceinline__ void gather_block(const GatherArgs& g, const int blk) {
   const DevState* st = g.st;
@@ -51,7 +58,11 @@ __device__ __forceinline__ void gather_block(const GatherArgs& g, const int blk)
       const int t = (which == 0 ? it_a : it_c) + 1;
       const double pw = pow((double)(isb1 ? g.beta1 : g.beta2), (double)t);
       const double p1 = __shfl_down(pw, 1, 64);          // lane 2*which: pw = beta2^t, p1 = beta1^t
-      if (threadIdx.x < 4 && !isb1) g.corr[which] = (float)(sqrt(1.0 - pw) / (1.0 - p1));
+      if (threadIdx.x < 4 && !isb1) {
+        const float corr = (float)(sqrt(1.0 - pw) / (1.0 - p1));
+        if (g.sched != nullptr) g.corr[which] = lr_rate_scaled(*g.sched, which, t - 1, corr);
+        else g.corr[which] = corr;
+      }
     }
     return;
   }

@@ -86,7 +86,9 @@ class DQN:
                  device=0, dp_world=1, dp_rank=0, use_graph=False, stream=None, grad_arena=None,
                  grad_arena_bytes=0, tid=0, save_path="state/dqn", precision="fp32", loss_scale=0.0, tuning=0,
                  loss_scale_mode="static", loss_scale_growth_interval=None, loss_scale_min_mult=None, loss_scale_max_mult=None,
-                 act_precision="fp32", solver="Adam", rms_decay=0.99, delta=None):
+                 act_precision="fp32", solver="Adam", rms_decay=0.99, delta=None,
+                 lr_policy="fixed", lr_gamma=0.0, lr_power=0.0, lr_stepsize=0, lr_stepvalues=(), lr_max_iter=0,
+                 weight_decay=0.0, regularization="L2"):
         self.lib = capi.load()
         cfg = capi.Config()
         self.lib.dqnhip_default_config(C.byref(cfg), state_size)
@@ -121,6 +123,18 @@ class DQN:
         cfg.solver_type, cfg.rms_decay = capi.SOLVERS.index(solver), rms_decay
         if delta is not None:
             cfg.delta = delta
+        # Caffe's lr_policy / weight_decay (SolverParameter); one schedule and one decay serve both nets, the base rates are actor_lr / critic_lr
+        if lr_policy not in capi.LR_POLICIES:
+            raise DQNFatal("Unknown learning rate policy: %s (known policies: %s)" % (lr_policy, ", ".join(capi.LR_POLICIES)))
+        if regularization not in capi.REGULARIZATIONS:
+            raise DQNFatal("Unknown regularization type: %s (known types: %s)" % (regularization, ", ".join(capi.REGULARIZATIONS)))
+        if len(lr_stepvalues) > capi.LR_MAX_STEPVALUES:
+            raise DQNFatal("lr_policy multistep: 1 to %d stepvalues required (got %d)" % (capi.LR_MAX_STEPVALUES, len(lr_stepvalues)))
+        cfg.lr_policy, cfg.lr_gamma, cfg.lr_power = capi.LR_POLICIES.index(lr_policy), lr_gamma, lr_power
+        cfg.lr_stepsize, cfg.lr_max_iter, cfg.lr_n_stepvalue = int(lr_stepsize), int(lr_max_iter), len(lr_stepvalues)
+        for i, sv in enumerate(lr_stepvalues):
+            cfg.lr_stepvalue[i] = int(sv)
+        cfg.weight_decay, cfg.regularization_type = weight_decay, capi.REGULARIZATIONS.index(regularization)
         self.cfg = cfg
         self.h = capi.H()
         self._ck(self.lib.dqnhip_create(C.byref(cfg), C.byref(self.h)))
@@ -161,6 +175,12 @@ class DQN:
     def solver(self):
         """Caffe's type string of this learner's solver (dqnhip_solver_name)."""
         return self.lib.dqnhip_solver_name(self.cfg.solver_type).decode()
+
+    def learning_rate(self, net):
+        """The rate net's next optimiser step applies (dqnhip_get_learning_rate: the lr policy at the net's current iteration)."""
+        out = C.c_float()
+        self._ck(self.lib.dqnhip_get_learning_rate(self.h, int(net), C.byref(out)))
+        return out.value
 
     def _ck(self, rc):
         if rc != 0:
@@ -661,6 +681,10 @@ class DQN:
             out = np.zeros(3, np.float32)
             self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
             return out.astype(np.int64)
+        if name == "sched_launches":          # ... and [k_sched_soft<>, k_sched_soft_gather<>]: the pass of a learner with an lr policy or a weight decay
+            out = np.zeros(2, np.float32)
+            self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
+            return out.astype(np.int64)
         wide = name in ("actor_out", "dq_da", "actor_target_out", "dxc")
         out = np.empty(B * (10 if wide else 1), np.float32)
         self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
@@ -684,7 +708,8 @@ class DQN:
         self._ck(self.lib.dqnhip_get_update_plan(self.h, C.byref(p)))
         return {"forms": [n for i, n in enumerate(capi.PLAN_FORMS) if p.forms >> i & 1], "launches_single": p.launches_single,
                 "launches_graph_first": p.launches_graph_first, "launches_in_graph": p.launches_in_graph,
-                "updates_per_graph": p.updates_per_graph, "collectives": p.collectives, "solver": capi.SOLVERS[p.solver_type]}
+                "updates_per_graph": p.updates_per_graph, "collectives": p.collectives, "solver": capi.SOLVERS[p.solver_type],
+                "lr_policy": capi.LR_POLICIES[p.lr_policy], "regularised": bool(p.regularised)}
 
     # -- update diagnostics (include/dqnhip.h: Caffe's debug_info, reduced on the device; opt-in) --------------
     def diag_collect_raw(self):

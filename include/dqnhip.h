@@ -97,8 +97,38 @@ enum dqnhip_solver {
 #define DQNHIP_LOSS_SCALE_STATIC 0   /* the built-in scales x loss_scale, fixed at create time (default)                 */
 #define DQNHIP_LOSS_SCALE_DYNAMIC 1  /* ... x a power-of-two multiplier per net that the optimiser launch adjusts itself */
 
+/* dqnhip_config.lr_policy: Caffe's learning-rate policies (SolverParameter.lr_policy, the reference driver's -lr_policy flag:
+ * src/dqn_main.cpp:36, 255-256; SGDSolver::GetLearningRate).  0 — a zero-filled field — is "fixed", every learner
+ * there was before the field existed.  With base = actor_lr / critic_lr and iter the net's solver iteration before its increment:
+ *   fixed      base
+ *   step       base * gamma^(iter / stepsize)                  (integer division)         stepsize > 0, gamma > 0
+ *   exp        base * gamma^iter                                                          gamma > 0
+ *   inv        base * (1 + gamma * iter)^(-power)                                         gamma >= 0
+ *   multistep  base * gamma^k, k = number of stepvalues <= iter                           1..16 strictly increasing positive values, gamma > 0
+ *   poly       base * max(0, 1 - iter / max_iter)^power        (0 from max_iter on)       max_iter > 0, power >= 0
+ *   sigmoid    base / (1 + exp(-gamma * (iter - stepsize)))                               stepsize >= 0
+ * Evaluated in double from the float32 fields and rounded once (Caffe: float powf) — ON THE DEVICE, per update, from the iteration
+ * counters (a captured graph replays sixteen updates with sixteen different rates).  One schedule serves both nets.
+ * weight_decay / regularization_type: SGDSolver::Regularize inside the optimiser pass, after the clip, decay_mult 1 on
+ * weights and biases alike: gd = fmaf(weight_decay, r, g * clip_scale) with r = w (L2) or sign(w), sign(0) = 0 (L1); the solver's
+ * rule then runs on gd.  The clip norm is the unregularised gradient's.
+ * A learner with a policy or a decay (v1): single learner only (no dp_world > 1, dqnhip_dp_init*, dqnhip_apply_update*), no
+ * dqnhip_diag_collect.  An Adam learner with a policy and no decay keeps its kernels (the rate reaches them through
+ * DevState::adam_corr); every other such learner runs k_sched_soft<> and takes the schedule without first-layer riders. */
+#define DQNHIP_LR_FIXED 0
+#define DQNHIP_LR_STEP 1
+#define DQNHIP_LR_EXP 2
+#define DQNHIP_LR_INV 3
+#define DQNHIP_LR_MULTISTEP 4
+#define DQNHIP_LR_POLY 5
+#define DQNHIP_LR_SIGMOID 6
+#define DQNHIP_LR_MAX_STEPVALUES 16
+#define DQNHIP_REG_L2 0
+#define DQNHIP_REG_L1 1
+
 typedef struct dqnhip_config {
-  int32_t struct_size;       /* = sizeof(dqnhip_config); ABI check            */
+  int32_t struct_size;       /* = sizeof(dqnhip_config); ABI check (or that size less the 96 bytes of the lr_policy ..
+                                regularization_type block: a caller compiled before it existed — a fixed learner without decay) */
   int32_t minibatch;         /* kMinibatchSize (32); multiple of 32           */
   int32_t state_size;        /* num_features = 50 + 9*players; >= 1           */
   int32_t num_hidden;        /* tower depth (4); 1..DQNHIP_MAX_HIDDEN         */
@@ -143,6 +173,16 @@ typedef struct dqnhip_config {
                                 Every field above these two keeps the offset it had before they existed — a caller compiled
                                 against that header and run on this library (which fills the struct through
                                 dqnhip_default_config) still sets what it means to set; from here on the offsets grew by 8. */
+  int32_t lr_policy;         /* FLAGS_lr_policy: DQNHIP_LR_* (0 = fixed, the default)                              */
+  float lr_gamma;            /* SolverParameter.gamma (NOT the discount, which is `gamma` above)                   */
+  float lr_power;            /* SolverParameter.power                                                              */
+  int32_t lr_stepsize;       /* SolverParameter.stepsize                                                           */
+  int32_t lr_max_iter;       /* SolverParameter.max_iter (read by poly alone)                                      */
+  int32_t lr_n_stepvalue;    /* number of lr_stepvalue entries in use (multistep)                                  */
+  int32_t lr_stepvalue[DQNHIP_LR_MAX_STEPVALUES];   /* SolverParameter.stepvalue                                   */
+  float weight_decay;        /* SolverParameter.weight_decay (0: none, the default)                                */
+  int32_t regularization_type;   /* DQNHIP_REG_L2 (default) / DQNHIP_REG_L1.  These 24 words sit where they do for the reason
+                                solver_type does; from here on the offsets grew by another 96. */
   int32_t tuning_flags;      /* DQNHIP_TUNE_* bits: A/B switches that select an alternative
                                 SCHEDULE of the same arithmetic (0 = the measured winners).
                                 The library reads no environment variable; every bit has a
@@ -215,6 +255,8 @@ void dqnhip_default_config(dqnhip_config* cfg, int32_t state_size);
 
 /* Caffe's type string of a DQNHIP_SOLVER_* value ("Adam", "SGD", "Nesterov", "AdaGrad", "RMSProp", "AdaDelta"); NULL: no such solver. */
 const char* dqnhip_solver_name(int32_t solver_type);
+/* Caffe's lr_policy string of a DQNHIP_LR_* value ("fixed", "step", "exp", "inv", "multistep", "poly", "sigmoid"); NULL: no such policy. */
+const char* dqnhip_lr_policy_name(int32_t lr_policy);
 
 /* Bytes the caller must provide in cfg->grad_arena (0 on invalid config). */
 size_t dqnhip_grad_arena_bytes(const dqnhip_config* cfg);
@@ -372,7 +414,13 @@ typedef struct dqnhip_update_plan {
   int32_t updates_per_graph;    /* 16 */
   int32_t collectives;          /* RCCL calls per update once a communicator is up (not counted in launches_*), else 0 */
   int32_t solver_type;          /* DQNHIP_SOLVER_* of the learner (0 = Adam; this word was reserved, always 0, before the other solvers existed) */
+  int32_t lr_policy;            /* DQNHIP_LR_* of the learner (appended; a caller may pass the struct_size without the two words and gets the rest) */
+  int32_t regularised;          /* 1: weight_decay != 0 */
 } dqnhip_update_plan;
+/* The rate net's NEXT optimiser step will apply (lr_policy at the net's current iteration): the host build of the function the
+ * device evaluates, at the host's mirror of the counter (dqnhip_get_iters; no sync).  Both evaluate in double and round once; the two pow() / exp() implementations may land on
+ * different sides of a float32 rounding boundary, so the value can differ from the device's in the last float32 bit. */
+int dqnhip_get_learning_rate(dqnhip_handle h, int32_t net, float* out);
 /* Fails while a phased update is in progress or kernel timing is on; launches_* are 0 for a sharded optimiser (its
  * sequence contains collectives and is not captured here). */
 int dqnhip_get_update_plan(dqnhip_handle h, dqnhip_update_plan* out);
@@ -897,6 +945,8 @@ int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t
  * Solver: a learner whose solver is not Adam writes a 16-byte SOLV section (solver_type, rms_decay) behind the history sections, an
  * Adam learner writes none (its file is what it was before the other solvers existed); dqnhip_load_state refuses a file whose solver
  * is not the learner's, in either direction, before it touches the learner.  ADM<net> / ADV<net> carry history 1 / history 2.
+ * Schedule: a learner with an lr policy or a weight decay writes a 104-byte LRSC section (the schedule's words, the decay, its kind)
+ * behind them, by the same rules: a learner with neither writes the file it always wrote, and a load refuses any difference.
  *
  * v1 refuses, in both calls: a learner in any sharing relationship (parameters or replay memory, either role), dp_world > 1 or a
  * live communicator, a phased update in progress, kernel timing on.  Env front-end handles attached to a learner that loads see

@@ -111,8 +111,20 @@ class SolverParameter {
   DQNHIP_SHIM_FIELD(float, delta, 1e-8f)
   DQNHIP_SHIM_FIELD(float, rms_decay, 0.99f)           // (RMSProp)
   DQNHIP_SHIM_FIELD(float, clip_gradients, -1.0f)
+  // the lr policy's parameters and the regulariser (SGDSolver::GetLearningRate / Regularize); the reference's driver sets none of them
+  DQNHIP_SHIM_FIELD(float, gamma, 0.0f)
+  DQNHIP_SHIM_FIELD(float, power, 0.0f)
+  DQNHIP_SHIM_FIELD(int, stepsize, 0)
+  DQNHIP_SHIM_FIELD(float, weight_decay, 0.0f)
+  DQNHIP_SHIM_FIELD(std::string, regularization_type, "L2")
 #undef DQNHIP_SHIM_FIELD
+ public:
+  int stepvalue_size() const { return (int)stepvalue_.size(); }          // repeated int32 stepvalue
+  int stepvalue(int i) const { return stepvalue_[i]; }
+  void add_stepvalue(int v) { stepvalue_.push_back(v); }
+  void clear_stepvalue() { stepvalue_.clear(); }
  private:
+  std::vector<int> stepvalue_;
   NetParameter net_param_;
 };
 
