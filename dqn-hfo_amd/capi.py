@@ -136,6 +136,21 @@ class DiagReport(C.Structure):
                 ("fp16", C.c_int32), ("loss_scale_mode", C.c_int32), ("loss_scale_critic", C.c_float), ("loss_scale_dqda", C.c_float),
                 ("loss_scale_actor", C.c_float), ("mult_critic", C.c_float), ("mult_actor", C.c_float), ("reserved", C.c_int32)]
 
+
+class SweepReport(C.Structure):
+    """struct dqnhip_sweep_report (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("first", C.c_int32), ("n", C.c_int32), ("n_chunks", C.c_int32),
+                ("n_terminal", C.c_int64), ("n_action_match", C.c_int64),
+                ("q", DiagRow), ("y", DiagRow), ("td", DiagRow), ("q_policy", DiagRow), ("mc", DiagRow), ("q_minus_mc", DiagRow),
+                ("reward", DiagRow), ("td_hist", C.c_int32 * DIAG_BINS), ("actor_iter", C.c_int32), ("critic_iter", C.c_int32)]
+
+
+class SweepRows(C.Structure):
+    """struct dqnhip_sweep_rows (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("q", C.POINTER(C.c_float)), ("y", C.POINTER(C.c_float)), ("td", C.POINTER(C.c_float)),
+                ("q_policy", C.POINTER(C.c_float)), ("action_match", C.POINTER(C.c_int32))]
+
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int32)
 up = C.POINTER(C.c_uint8)
@@ -235,6 +250,8 @@ SIGNATURES = {
     "dqnhip_per_set_priorities": (C.c_int, [H, C.c_int32, C.c_int32, fp]),
     "dqnhip_per_sample": (C.c_int, [H, C.c_uint64, C.c_int32, ip, fp]),
     "dqnhip_per_debug_read": (C.c_int, [H, C.c_char_p, fp, C.c_size_t]),
+    "dqnhip_evaluate_memory": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(SweepReport), C.POINTER(SweepRows)]),
+    "dqnhip_per_refresh": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(SweepReport)]),
     "dqnhip_save_state": (C.c_int, [H, C.c_char_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "dqnhip_load_state": (C.c_int, [H, C.c_char_p]),
     "dqnhip_state_info": (C.c_int, [C.c_char_p, C.POINTER(StateInfo)]),

@@ -195,8 +195,9 @@ __device__ __forceinline__ void diag_panel_item(const DiagSeg& sg, int strip, Di
 
 // ---- the [B] row buffers ---------------------------------------------------------------------------------------------------
 struct DiagRowAcc { float mn, mx; double s, ss; unsigned cnt; };
-// over the block: min / max / sums of the finite values, cnt summed; thread 0 holds the result.  No finite value: min = max = 0
-__device__ __forceinline__ DiagRowAcc diag_row_block(DiagRowAcc r, DiagLds& sm) {
+// over the block: min / max / sums of the finite values, cnt summed; every thread holds the result.  No finite value: min = +inf,
+// max = -inf (what a further reduction over several blocks' results needs: sweep_kernels.hip.h)
+__device__ __forceinline__ DiagRowAcc diag_row_block_raw(DiagRowAcc r, DiagLds& sm) {
   const int t = threadIdx.x;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -211,6 +212,11 @@ __device__ __forceinline__ DiagRowAcc diag_row_block(DiagRowAcc r, DiagLds& sm) 
     const DiagAcc& p = sm.acc[0][w];
     o.mn = fminf(o.mn, __uint_as_float(p.nz)); o.mx = fmaxf(o.mx, p.mx); o.s += p.sa; o.ss += p.ss; o.cnt += p.nnf;
   }
+  return o;
+}
+// ... as a report states it: no finite value: min = max = 0
+__device__ __forceinline__ DiagRowAcc diag_row_block(DiagRowAcc r, DiagLds& sm) {
+  DiagRowAcc o = diag_row_block_raw(r, sm);
   if (o.mn > o.mx) { o.mn = 0.0f; o.mx = 0.0f; }
   return o;
 }

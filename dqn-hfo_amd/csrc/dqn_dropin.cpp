@@ -64,6 +64,12 @@ DEFINE_int32(debug_info_iter, 0, "Every this many critic iterations Update() log
              "(dqnhip_diag_collect; Caffe's debug_info of the reference's debug builds): gradient norms and clip scales, per-blob mean "
              "|w| / |g| / |step| / |lag|, per-panel mean |a|, leaky fraction and dead units, Q / TD spreads, actor outputs out of bounds. "
              "Every line starts \"[Agent<t>] [Diag]\". 0: off, nothing is collected and the log is what it was.");
+DEFINE_int32(evaluate_memory_freq, 0, "Every this many critic iterations Update() evaluates the nets as they stand over the WHOLE replay memory on the "
+             "device (dqnhip_evaluate_memory: the update's forward passes, no step) and logs one line \"[Agent<t>] [Memory]\": mean and rms TD "
+             "error, mean Q(s,a), TD target, Q(s,mu(s)) and Q(s,a) - on_policy_target, and how often mu(s) picks the stored action. "
+             "0: off, nothing runs and the log is what it was. -precision fp32, single learner.");
+DEFINE_bool(per_refresh_on_load, false, "-prioritized_replay: LoadReplayMemory() recomputes every loaded transition's priority from its TD error under the "
+            "nets as they stand (dqnhip_per_refresh) instead of leaving all of them at p_max, and logs one \"[Agent<t>] [Memory]\" line.");
 DEFINE_bool(prioritized_replay, false, "Proportional prioritized experience replay (Schaul et al. 2016) on the device: minibatches are drawn with "
             "probability p^alpha / sum from a sum tree over the replay memory, the critic's loss carries importance weights, |TD error| is "
             "written back. UpdateActorCritic() then draws nothing from the host engine. Not combinable with -deferred_updates, "
@@ -109,6 +115,7 @@ DEFINE_int32(hip_agent_device_stride, 0, "Agent thread t of this process uses HI
 
 
 #define DQNHIP_CK(call) CHECK((call) == 0) << dqnhip_last_error()
+static void LogMemorySweep(const dqnhip_sweep_report& r, int tid, const char* what);      // (beside LogDiagnostics, below)
 
 namespace {
 
@@ -267,6 +274,11 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
                << "(libdqnhip.so has no CPU backend). Run the reference's own Caffe build for the CPU solver, or start this binary with -gpu=true.";
   CHECK(!(FLAGS_deferred_updates && FLAGS_pipelined_stats)) << "-deferred_updates cannot be combined with -pipelined_stats (both decide when an update's (loss, avg_q) reach the host)";
   CHECK(!(FLAGS_deferred_updates && FLAGS_device_sampling)) << "-deferred_updates cannot be combined with -device_sampling (deferred updates run on the indices random_engine draws)";
+  CHECK(!FLAGS_per_refresh_on_load || FLAGS_prioritized_replay) << "-per_refresh_on_load needs -prioritized_replay (it rewrites the priorities a load leaves at p_max; a uniform learner has none)";
+  if (FLAGS_evaluate_memory_freq > 0 || FLAGS_per_refresh_on_load) {
+    CHECK(FLAGS_precision == "fp32") << "-evaluate_memory_freq / -per_refresh_on_load need -precision fp32 (the replay sweep has no fp16 form in this version)";
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-evaluate_memory_freq / -per_refresh_on_load are single-learner options (-dp_world 1, no -dp_rendezvous)";
+  }
   if (FLAGS_prioritized_replay) {
     CHECK(!FLAGS_deferred_updates) << "-prioritized_replay cannot be combined with -deferred_updates (a deferred burst runs on indices drawn ahead; a prioritized update's indices do not exist before its predecessor's write-back)";
     CHECK(!FLAGS_pipelined_stats) << "-prioritized_replay cannot be combined with -pipelined_stats";
@@ -526,6 +538,12 @@ void DQN::LoadReplayMemory(const std::string& f) {
   LOG(INFO) << "Loading replay memory from " << f;
   DQNHIP_CK(dqnhip_load_replay_memory(h_, f.c_str()));
   LOG(INFO) << "replay_mem_size = " << memory_size();
+  if (FLAGS_per_refresh_on_load && memory_size() > 0) {
+    dqnhip_sweep_report r;
+    r.struct_size = (int32_t)sizeof r;
+    DQNHIP_CK(dqnhip_per_refresh(h_, 0, -1, &r));
+    LogMemorySweep(r, tid_, "priorities refreshed at");
+  }
 }
 void DQN::SnapshotReplayMemory(const std::string& f) { SubmitPending(); JoinSnapshot(); DQNHIP_CK(dqnhip_snapshot_replay_memory(h_, f.c_str())); }
 
@@ -745,6 +763,7 @@ void DQN::Update() {
     const bool due = c % FLAGS_loss_display_iter == 0 || a % FLAGS_loss_display_iter == 0 ||
                      c >= last_snapshot_iter_ + FLAGS_snapshot_freq || a >= last_snapshot_iter_ + FLAGS_snapshot_freq ||
                      (FLAGS_debug_info_iter > 0 && c % FLAGS_debug_info_iter == 0) ||      // (the diagnostics describe the last update run)
+                     (FLAGS_evaluate_memory_freq > 0 && c % FLAGS_evaluate_memory_freq == 0) ||      // (the sweep sees the nets this update left)
                      pend_n_ + uncollected_ >= kMaxUncollected;
     if (due) CollectDeferred();              // (the last replayed Bookkeep is this update's: it logs / snapshots)
     else if (pend_n_ == kSubmitEvery) SubmitPending();
@@ -797,6 +816,14 @@ static void LogDiagnostics(dqnhip_handle h, int tid) {
             << ", |dq_da| = " << r.dq_da_sum_abs / (B * DQNHIP_ACTOR_OUT) << " (max " << r.dq_da_max_abs << ")";
 }
 
+// -evaluate_memory_freq / -per_refresh_on_load: one line from a replay sweep's report.  Means are sum / n.
+static void LogMemorySweep(const dqnhip_sweep_report& r, int tid, const char* what) {
+  const double n = r.n > 0 ? (double)r.n : 1.0;
+  LOG(INFO) << "[Agent" << tid << "] [Memory] " << what << " iter " << r.critic_iter << ": td mean " << r.td.sum / n << " rms " << std::sqrt(r.td.sum_sq / n)
+            << ", q " << r.q.sum / n << ", y " << r.y.sum / n << ", q_policy " << r.q_policy.sum / n << ", q - mc " << r.q_minus_mc.sum / n
+            << ", action match = " << (double)r.n_action_match / n << ", n = " << r.n;
+}
+
 // src/dqn.cpp:806-825 behind UpdateActorCritic(), on the iteration numbers that update left
 void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_it) {
   if (critic_it % FLAGS_loss_display_iter == 0) {
@@ -818,6 +845,14 @@ void DQN::Bookkeep(const std::pair<float, float>& res, int critic_it, int actor_
   // -debug_info_iter: the diagnostics of this update (deferred updates: Update() made the collection due at this update, so the
   // replayed Bookkeep that gets here is the last update's and the device still holds what it left)
   if (FLAGS_debug_info_iter > 0 && critic_it % FLAGS_debug_info_iter == 0) LogDiagnostics(h_, tid_);
+  // -evaluate_memory_freq: behind the loss lines and the diagnostics (a sweep overwrites the row buffers they are collected from).  Deferred
+  // updates: as for the diagnostics, the replayed Bookkeep that gets here is the last update's — everything pending has been run
+  if (FLAGS_evaluate_memory_freq > 0 && critic_it % FLAGS_evaluate_memory_freq == 0) {
+    dqnhip_sweep_report r;
+    r.struct_size = (int32_t)sizeof r;
+    DQNHIP_CK(dqnhip_evaluate_memory(h_, 0, -1, &r, nullptr));
+    LogMemorySweep(r, tid_, "evaluated at");
+  }
   if (critic_it >= last_snapshot_iter_ + FLAGS_snapshot_freq || actor_it >= last_snapshot_iter_ + FLAGS_snapshot_freq) {
     snapshot_from_update_ = true;
     Snapshot();

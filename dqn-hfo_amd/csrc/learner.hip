@@ -909,6 +909,48 @@ int run_phase(H* h, int phase, const int* idx_dev) {
   return fail("phase must be 0, 1, 2, 10 or 11 (got %d)", phase);
 }
 
+// ---- one chunk of a replay sweep, up to its row kernel (dqnhip_evaluate_memory / dqnhip_per_refresh) --------------------------
+// Phase 0's gather and forward launches as the stand-alone update issues them (the first layers merged where the plan merges them),
+// Step(1)'s head arithmetic in the launch of its own (k_head_q_train: the DQNHIP_TUNE_SEPARATE_Q_TRAIN form, whatever the plan says —
+// there is no dgrad launch to carry it), then critic(s, mu(s)) on the critic AS IT STANDS, every layer from its launcher (no optimiser
+// launch carries its first layer), and its q head.  Leaves q_t, q1, y, q2, aout16, the gathered reward / mc / term and the panels.
+int sweep_forward(H* h, const int* idx_dev, DevState* flag_sink) {
+  if (h->fp16) return fail("internal: sweep_forward on an fp16 learner");
+  const UpdatePlan P = plan_of(h);
+  select_panels(h, 0);
+  const int B = h->B, L = h->L;
+  const NetLayout &la = h->la, &lc = h->lc;
+  hipStream_t st = h->stream;
+  {
+    // the gather's row blocks alone: its last block — this update's Adam corrections and soft-update switch into DevState — is not launched
+    const GatherArgs g = gather_args(h, idx_dev, -1);
+    HIPCHK(launch(st, k_gather, dim3(g.blocks - 1), dim3(256), 0, g));
+  }
+  HeadArgs hA = actor_head_args(h, DQNHIP_ACTOR); hA.X = h->act[1][L]; hA.xc = h->Xc_pl;
+  HeadArgs hAT = actor_head_args(h, DQNHIP_ACTOR_TARGET); hAT.X = h->act[0][L]; hAT.xc = h->Xc_nx;
+  FwdPass pAT{DQNHIP_ACTOR_TARGET, &la, h->act[0]}, pA{DQNHIP_ACTOR, &la, h->act[1]};
+  FwdPass pCT{DQNHIP_CRITIC_TARGET, &lc, h->act[2]}, pC1{DQNHIP_CRITIC, &lc, h->act[3]};
+  const bool merged_l0 = P.first_layers_merged;
+  if (merged_l0) {
+    RC(first_layers_launch(h, st, B, true));
+    hAT.l1_zs = h->Zs; hAT.l1_wt = h->Wact_t;
+    hAT.l1_b = wat(h, DQNHIP_CRITIC_TARGET, lc.b_off[0]); hAT.l1_y = h->act[2][1]; hAT.l1_ld = lc.kp[1]; hAT.l1_n = lc.dims[1];
+  }
+  const FwdPass ap[2] = {pAT, pA}, cp[2] = {pCT, pC1};
+  RC(tower_forward(h, st, ap, 2, B, merged_l0 ? 1 : 0));
+  RC((head_forward<kNO, HEAD_ACTOR>(h, st, hAT, &hA)));
+  RC(tower_forward(h, st, cp, 2, B, merged_l0 ? 1 : 0));
+  HeadTrainArgs t = q_train_args(h);
+  t.Xt = h->act[2][L]; t.X = h->act[3][L]; t.st = flag_sink;
+  HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
+  FwdPass pC2{DQNHIP_CRITIC, &lc, h->act[4]};
+  RC(tower_forward(h, st, &pC2, 1, B));
+  HeadArgs hq{}; hq.X = h->act[4][L]; hq.ldx = lc.dims[L]; hq.H = lc.dims[L]; hq.rows = B;
+  hq.W = wat(h, DQNHIP_CRITIC, lc.hw_off); hq.b = wat(h, DQNHIP_CRITIC, lc.hb_off); hq.q = h->q2;
+  RC((head_forward<1, HEAD_Q>(h, st, hq)));
+  return 0;
+}
+
 int to_bf16_launch(H* h, int net) {
   HIPCHK(launch(h->stream, k_to_bf16, dim3(1024), dim3(256), 0, (const float*)h->g[net], layout_of(h, net).arena / 4, h->g16[net]));
   return 0;

@@ -52,6 +52,7 @@ void drop_graphs(H* h) {
   for (auto& g : h->graph_small) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   for (auto& bank : h->ix_graph) for (auto& g : bank) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   for (int& n : h->ix_nodes) n = 0;
+  for (auto& g : h->sweep_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   if (h->dp_graph) { hipGraphExecDestroy(h->dp_graph); h->dp_graph = nullptr; }
   if (h->dp_graph_n) { hipGraphExecDestroy(h->dp_graph_n); h->dp_graph_n = nullptr; }
   h->dp_graph_failed = false; h->dp_graph_n_failed = false; h->graph_failed = false;
@@ -285,6 +286,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   drop_graphs(h);
   per_free(h);
   diag_free(h);
+  sweep_free(h);
   for (int i = 0; i < 2; ++i) {
     if (h->pipe_ev[i]) hipEventDestroy(h->pipe_ev[i]);
     if (h->pipe_idx_pinned[i]) hipHostFree(h->pipe_idx_pinned[i]);

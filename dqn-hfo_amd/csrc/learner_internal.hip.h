@@ -9,8 +9,9 @@
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
 //   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
-//                       introspection, update diagnostics (dqnhip_diag_collect), the launches of the asynchronous state save and of the
-//                       asynchronous Caffe snapshot (snapshot_kernels.hip.h)
+//                       introspection, update diagnostics (dqnhip_diag_collect), the replay sweep (dqnhip_evaluate_memory /
+//                       dqnhip_per_refresh: sweep_kernels.hip.h; its forward launches are sweep_forward's, learner.hip), the launches
+//                       of the asynchronous state save and of the asynchronous Caffe snapshot (snapshot_kernels.hip.h)
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state, and the host side of
 //                       dqnhip_save_state_async and dqnhip_snapshot_async (the writer thread they share; the kernels are launched
@@ -136,6 +137,7 @@ struct PerHost {
   long long syncs = 0;                  // k_per_sync launches so far
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
+struct SweepHost;                       // replay sweep (learner_io.hip; the kernels: sweep_kernels.hip.h)
 struct StateAsync;                      // asynchronous learner-state save and Caffe snapshot (learner_state.hip; the kernels: state_kernels.hip.h, snapshot_kernels.hip.h)
 
 }  // namespace dqnhip_host
@@ -289,6 +291,10 @@ struct dqnhip_learner {
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
   DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
+  // replay sweep (dqnhip_evaluate_memory / dqnhip_per_refresh): its scratch, allocated by the first sweep, and one captured chunk of
+  // each kind (by refresh)
+  SweepHost* sweep = nullptr;
+  hipGraphExec_t sweep_graph[2] = {nullptr, nullptr};
   StateAsync* sasync = nullptr;         // dqnhip_save_state_async / dqnhip_snapshot_async: the writer thread, the pinned ring and each kind's staging buffer, allocated at first use
 };
 
@@ -400,6 +406,11 @@ int to_bf16_launch(H* h, int net);                       // k_to_bf16: the bf16 
 int shard_scal_launch(H* h, float* tail);                // k_shard_scal: this rank's share of the clip norm -> tail[3]
 int run_phase(H* h, int phase, const int* idx_dev);
 int sync_dirty16(H* h);
+// One chunk of a replay sweep up to its row kernel: the update's gather on idx_dev (without its scalars block: DevState stays as it
+// is) and the update's forward launches — actor_target(s'), actor(s), critic_target, critic(s, a), k_head_q_train, critic(s, mu(s))
+// and its q head — on the learner's panels and row buffers.  No backward, no optimiser.  flag_sink: where k_head_q_train raises its
+// non-finite-target flag instead of the learner's DevState (the sticky flags belong to updates).  fp32 learners.
+int sweep_forward(H* h, const int* idx_dev, DevState* flag_sink);
 int prepare_kernels(const H* h);                         // the launch attributes (dynamic-LDS limits) of the update's kernels
 // learner_update.hip
 int refresh_ring(H* h);
@@ -418,6 +429,9 @@ struct CaptureSpec {
 };
 int capture_updates(H* h, const CaptureSpec& s, hipGraph_t* graph);
 int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out, int* kernel_nodes = nullptr);      // ... and instantiate
+// n_chunks runs of `body` (one chunk of a replay sweep: its launches read the chunk base from device memory) on the learner's stream:
+// replays of *g, captured from `body` on first use, or eagerly where graphs are off
+int run_chunks(H* h, hipGraphExec_t* g, int n_chunks, int (*body)(H*, const int*));
 int ix_harvest_all(H* h);                                // waits for every indexed update enqueued so far and files its scalars
 // learner_create.hip
 int ensure_stage(H* h, size_t bytes);
@@ -447,6 +461,7 @@ int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behin
 int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
 int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
 void diag_free(H* h);                                    // dqnhip_diag_collect's scratch
+void sweep_free(H* h);                                   // the replay sweep's scratch
 // asynchronous learner-state save: the launchers of state_kernels.hip.h, on the learner's stream (learner_io.hip) ...
 int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev);
 int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a);

@@ -1,10 +1,11 @@
 // learner_io.hip — everything of the C-ABI around the update: acting (SelectActions / CriticForward), the replay memory and
-// its .replaymemory files, parameter access, multi-agent sharing, introspection, update diagnostics (include/dqnhip.h).
+// its .replaymemory files, parameter access, multi-agent sharing, introspection, update diagnostics, the replay sweep (include/dqnhip.h).
 #include "learner_internal.hip.h"
 #include "head_fwd_kernels.hip.h"
 #include "io_kernels.hip.h"
 #include "per_kernels.hip.h"
 #include "diag_kernels.hip.h"
+#include "sweep_kernels.hip.h"
 #include "state_kernels.hip.h"
 #include "snapshot_kernels.hip.h"
 
@@ -1113,6 +1114,150 @@ int dqnhip_diag_collect(dqnhip_handle h, dqnhip_diag_report* out) {
     out->mult_critic = h->ls_dynamic ? s.ls_mult[1][0] : 1.0f; out->mult_actor = h->ls_dynamic ? s.ls_mult[0][0] : 1.0f;
   }
   return 0;
+}
+
+// ---- replay sweep (include/dqnhip.h has the definitions; the row kernel, the finaliser and the order of every sum: sweep_kernels.hip.h;
+// the forward launches of a chunk: sweep_forward, learner.hip) ------------------------------------------------------------------------
+
+}  // extern "C"
+namespace dqnhip_host {
+
+struct SweepHost {
+  SweepDev* dev = nullptr; int* idx = nullptr; SweepPart* parts = nullptr; SweepOut* out = nullptr;
+  float* rows[4] = {nullptr, nullptr, nullptr, nullptr}; int* match = nullptr;      // q, y, td, q_policy; [chunks x B] each
+  DevState* flag_sink = nullptr;        // where a chunk's k_head_q_train raises its flag (the learner's sticky flags belong to updates)
+  long long cap = 0;                    // the ring capacity the scratch was sized for (a learner may join another ring later: sweep_ready)
+  int chunks = 0;                       // ceil(cap / B): the largest window
+};
+void sweep_free(H* h) {
+  SweepHost* w = h->sweep;
+  if (!w) return;
+  hipFree(w->dev); hipFree(w->idx); hipFree(w->parts); hipFree(w->out); hipFree(w->match); hipFree(w->flag_sink);
+  for (float* r : w->rows) hipFree(r);
+  delete w;
+  h->sweep = nullptr;
+}
+static int sweep_build(H* h) {
+  SweepHost* w = new SweepHost();
+  h->sweep = w;                         // (from here on sweep_free releases whatever was allocated)
+  w->cap = RO(h)->ring.cap;
+  w->chunks = (int)((w->cap + h->B - 1) / h->B);
+  const size_t rows = (size_t)w->chunks * h->B;
+  auto alloc = [&](void** p, size_t bytes) -> int { HIPCHK(hipMalloc(p, bytes)); HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream)); return 0; };
+  RC(alloc((void**)&w->dev, sizeof(SweepDev)));
+  RC(alloc((void**)&w->idx, (size_t)h->B * sizeof(int)));
+  RC(alloc((void**)&w->parts, (size_t)w->chunks * sizeof(SweepPart)));
+  RC(alloc((void**)&w->out, sizeof(SweepOut)));
+  for (float*& r : w->rows) RC(alloc((void**)&r, rows * sizeof(float)));
+  RC(alloc((void**)&w->match, rows * sizeof(int)));
+  RC(alloc((void**)&w->flag_sink, sizeof(DevState)));
+  return 0;
+}
+// the scratch, sized for the ring this learner uses NOW: dqnhip_share_replay_memory may have pointed it at a ring of another capacity
+// since the last sweep — the window, the chunk slots and the row outputs are counted in that ring's transitions.  The captured chunks
+// hold the old addresses: dropped with the scratch, behind everything enqueued
+static int sweep_ready(H* h) {
+  if (h->sweep && h->sweep->cap != (long long)RO(h)->ring.cap) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (auto& g : h->sweep_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+    sweep_free(h);
+  }
+  if (!h->sweep && sweep_build(h)) { sweep_free(h); return 1; }
+  return 0;
+}
+// one chunk: [refresh: slots of the chunk's indices] . the forward launches . the row kernel . [refresh: the update's write-back]
+template <bool REFRESH>
+static int sweep_chunk(H* h, const int*) {
+  SweepHost* w = h->sweep;
+  if (REFRESH) RC(per_fill_launch(h, w->idx));         // (before the row kernel, which leaves the NEXT chunk's indices in w->idx)
+  RC(sweep_forward(h, w->idx, w->flag_sink));
+  SweepRowsArgs a{};
+  a.sw = w->dev; a.B = h->B;
+  a.q = h->q1; a.y = h->y; a.q_policy = h->q2; a.mc = h->mb_mc; a.reward = h->mb_reward; a.term = h->mb_term;
+  a.stored = h->Xc_tr + h->S; a.ld_stored = h->lc.kp[0]; a.aout16 = h->aout16;
+  a.idx = w->idx; a.parts = w->parts;
+  a.o_q = w->rows[0]; a.o_y = w->rows[1]; a.o_td = w->rows[2]; a.o_q_policy = w->rows[3]; a.o_match = w->match;
+  a.td_abs = REFRESH ? h->per->td_abs : nullptr;
+  HIPCHK(launch(h->stream, k_sweep_rows, dim3(1), dim3(256), 0, a));
+  if (REFRESH) RC(per_update_launch(h));
+  return 0;
+}
+// the two bodies a captured chunk is taken from (CaptureSpec::body's signature; a chunk's indices are its own, in device memory)
+static int sweep_chunk_eval(H* h, const int* unused) { return sweep_chunk<false>(h, unused); }
+static int sweep_chunk_refresh(H* h, const int* unused) { return sweep_chunk<true>(h, unused); }
+static void sweep_row(dqnhip_diag_row& o, const SweepMom& m) { o.min = m.mn; o.max = m.mx; o.sum = m.s; o.sum_sq = m.ss; o.n_nonfinite = m.nnf; }
+
+// what: the entry point's name.  rows: an evaluation's per-row outputs (null: none)
+static int sweep_run(H* h, const char* what, bool refresh, int32_t first, int32_t n, dqnhip_sweep_report* out, const dqnhip_sweep_rows* rows) {
+  if (out && out->struct_size != (int32_t)sizeof(dqnhip_sweep_report))
+    return fail("%s: dqnhip_sweep_report.struct_size %d != %zu (ABI mismatch)", what, out->struct_size, sizeof(dqnhip_sweep_report));
+  if (rows && rows->struct_size != (int32_t)sizeof(dqnhip_sweep_rows))
+    return fail("%s: dqnhip_sweep_rows.struct_size %d != %zu (ABI mismatch)", what, rows->struct_size, sizeof(dqnhip_sweep_rows));
+  if (refresh && !h->per) return fail("%s: the replay sweep refreshes priorities, and prioritized replay is not enabled on this learner (dqnhip_per_enable)", what);
+  if (h->next_phase != 0) return fail("%s: the replay sweep overwrites the update's panels, and a phased update is in progress (next phase %d)", what, h->next_phase);
+  if (h->cfg.dp_world > 1 || h->comm || h->dp_half || h->dp_shard)
+    return fail("%s: the replay sweep is not available on a data-parallel learner (dp_world > 1, dqnhip_dp_init) in this version", what);
+  if (h->fp16) return fail("%s: the replay sweep is not available with precision = DQNHIP_FP16 in this version", what);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RingUse ring_use(h);
+  RC(refresh_ring(h));
+  const long long size = RO(h)->h_size;
+  if (first < 0 || first > size || n < -1 || (n >= 0 && (long long)first + n > size))
+    return fail("%s: the replay sweep's window [%d,%lld) lies outside the memory [0,%lld)", what, first, n < 0 ? size : (long long)first + n, size);
+  if (n < 0) n = (int32_t)(size - first);
+  if (n == 0) {
+    // a no-op: nothing is allocated, launched or captured; the report is all zero but for the iteration counters as they stand
+    if (!out) return 0;
+    int it[2];
+    static_assert(offsetof(DevState, critic_iter) == offsetof(DevState, actor_iter) + sizeof(int), "actor_iter, critic_iter are adjacent");
+    HIPCHK(hipMemcpyAsync(it, &h->st->actor_iter, sizeof it, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memset(out, 0, sizeof *out);
+    out->struct_size = (int32_t)sizeof *out;
+    out->first = first; out->actor_iter = it[0]; out->critic_iter = it[1];
+    return 0;
+  }
+  RC(sweep_ready(h));
+  SweepHost* w = h->sweep;
+  const int n_chunks = (n + h->B - 1) / h->B;
+  if (n_chunks > w->chunks) return fail("internal: %s: %d chunks exceed the scratch's %d", what, n_chunks, w->chunks);
+  h->epoch += 1;                         // the panels a dqnhip_update_chained chain left for its next call are about to be overwritten
+  if (refresh) RC(per_sync_if_needed(h));
+  HIPCHK(launch(h->stream, k_sweep_begin, dim3((h->B + 255) / 256), dim3(256), 0, w->dev, (int)first, (int)n, w->idx, h->B));
+  RC(run_chunks(h, &h->sweep_graph[refresh ? 1 : 0], n_chunks, refresh ? sweep_chunk_refresh : sweep_chunk_eval));
+  HIPCHK(launch(h->stream, k_sweep_final, dim3(1), dim3(256), 0, (const SweepDev*)w->dev, (const DevState*)h->st, (const SweepPart*)w->parts, h->B, w->out));
+  SweepOut res{};
+  HIPCHK(hipMemcpyAsync(&res, w->out, sizeof res, hipMemcpyDeviceToHost, h->stream));
+  if (rows) {
+    float* dst[4] = {rows->q, rows->y, rows->td, rows->q_policy};
+    for (int k = 0; k < 4; ++k) if (dst[k]) HIPCHK(hipMemcpyAsync(dst[k], w->rows[k], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (rows->action_match) HIPCHK(hipMemcpyAsync(rows->action_match, w->match, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!out) return 0;
+  memset(out, 0, sizeof *out);
+  out->struct_size = (int32_t)sizeof *out;
+  out->first = first; out->n = res.n; out->n_chunks = res.n_chunks;
+  out->n_terminal = res.n_terminal; out->n_action_match = res.n_match;
+  dqnhip_diag_row* rr[kSweepQuantities] = {&out->q, &out->y, &out->td, &out->q_policy, &out->mc, &out->q_minus_mc, &out->reward};
+  for (int k = 0; k < kSweepQuantities; ++k) sweep_row(*rr[k], res.mom[k]);
+  memcpy(out->td_hist, res.hist, sizeof out->td_hist);
+  out->actor_iter = res.actor_iter; out->critic_iter = res.critic_iter;
+  return 0;
+}
+
+}  // namespace dqnhip_host
+extern "C" {
+
+int dqnhip_evaluate_memory(dqnhip_handle h, int32_t first, int32_t n, dqnhip_sweep_report* out, const dqnhip_sweep_rows* rows) {
+  if (!h) return fail("dqnhip_evaluate_memory: null handle");
+  if (!out) return fail("dqnhip_evaluate_memory: null report");
+  return sweep_run(h, "dqnhip_evaluate_memory", false, first, n, out, rows);
+}
+
+int dqnhip_per_refresh(dqnhip_handle h, int32_t first, int32_t n, dqnhip_sweep_report* out) {
+  if (!h) return fail("dqnhip_per_refresh: null handle");
+  return sweep_run(h, "dqnhip_per_refresh", true, first, n, out, nullptr);
 }
 
 int dqnhip_get_stream(dqnhip_handle h, void** stream) {

@@ -133,6 +133,16 @@ static int replay_or_run(H* h, GraphSlot slot, const int* idx_dev) {
   return run_update(h, idx_dev);
 }
 
+int run_chunks(H* h, hipGraphExec_t* g, int n_chunks, int (*body)(H*, const int*)) {
+  CaptureSpec s; s.body = body;
+  const hipGraphExec_t ge = graph_of(h, g, s);
+  for (int c = 0; c < n_chunks; ++c) {
+    if (ge) HIPCHK(hipGraphLaunch(ge, h->stream));
+    else RC(body(h, nullptr));
+  }
+  return 0;
+}
+
 // kernel nodes of a captured sequence
 static int count_kernel_nodes(hipGraph_t g, int* out) {
   size_t cnt = 0;

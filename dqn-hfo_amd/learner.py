@@ -809,6 +809,51 @@ class DQN:
         self._ck(self.lib.dqnhip_per_debug_read(self.h, name.encode(), _p(out), out.size))
         return out.astype(np.int64) if name == "slot" else out
 
+    # -- replay sweep (include/dqnhip.h: the nets evaluated over the stored memory, opt-in) -------------------
+    @staticmethod
+    def _sweep_dict(r):
+        out = {k: {"min": v.min, "max": v.max, "sum": v.sum, "sum_sq": v.sum_sq, "n_nonfinite": v.n_nonfinite}
+               for k, v in (("q", r.q), ("y", r.y), ("td", r.td), ("q_policy", r.q_policy), ("mc", r.mc), ("q_minus_mc", r.q_minus_mc),
+                            ("reward", r.reward))}
+        out.update({"first": r.first, "n": r.n, "n_chunks": r.n_chunks, "n_terminal": r.n_terminal, "n_action_match": r.n_action_match,
+                    "td_hist": np.array(r.td_hist, np.int32), "actor_iter": r.actor_iter, "critic_iter": r.critic_iter})
+        return out
+
+    def evaluate_memory_raw(self, first=0, n=-1, rows=None):
+        """dqnhip_evaluate_memory -> the ctypes report (capi.SweepReport); rows: a capi.SweepRows or None."""
+        r = capi.SweepReport()
+        r.struct_size = C.sizeof(capi.SweepReport)
+        self._ck(self.lib.dqnhip_evaluate_memory(self.h, int(first), int(n), C.byref(r), C.byref(rows) if rows is not None else None))
+        return r
+
+    def evaluate_memory(self, first=0, n=-1, rows=False):
+        """The nets as they stand evaluated over the logical transitions [first, first + n) (n = -1: to the end of the memory), as a
+        plain dict shaped like diagnostics()'s rows: q, y, td, q_policy, mc, q_minus_mc, reward (min, max, sum, sum_sq, n_nonfinite),
+        n, n_chunks, n_terminal, n_action_match, td_hist (int32[64]), actor_iter, critic_iter.  rows=True adds "rows": the per-transition
+        arrays q, y, td, q_policy (float32[n]) and action_match (int32[n]).  Overwrites what debug_read / diagnostics read."""
+        if not rows:
+            return self._sweep_dict(self.evaluate_memory_raw(first, n))
+        count = self.memory_size() - int(first) if int(n) < 0 else int(n)
+        arr = {k: np.zeros(max(count, 0), np.float32) for k in ("q", "y", "td", "q_policy")}
+        arr["action_match"] = np.zeros(max(count, 0), np.int32)
+        sr = capi.SweepRows()
+        sr.struct_size = C.sizeof(capi.SweepRows)
+        for k in ("q", "y", "td", "q_policy"):
+            setattr(sr, k, _p(arr[k]))
+        sr.action_match = arr["action_match"].ctypes.data_as(capi.ip)
+        # (the count the arrays were sized for, never -1: a shared ring may have grown since memory_size() was read)
+        out = self._sweep_dict(self.evaluate_memory_raw(first, n if int(n) >= 0 or count < 0 else count, sr))      # (count < 0: first lies outside, refused)
+        out["rows"] = arr
+        return out
+
+    def per_refresh(self, first=0, n=-1):
+        """dqnhip_per_refresh: the sweep of evaluate_memory on a prioritized learner, every leaf of the window rewritten to
+        (|td| + eps)^alpha.  Returns evaluate_memory's dict."""
+        r = capi.SweepReport()
+        r.struct_size = C.sizeof(capi.SweepReport)
+        self._ck(self.lib.dqnhip_per_refresh(self.h, int(first), int(n), C.byref(r)))
+        return self._sweep_dict(r)
+
     # -- native learner-state file (include/dqnhip.h: exact resume, opt-in) ----------------------------------
     def save_state(self, path, memory=True, user=b"", wait=True):
         """dqnhip_save_state: everything a bit-exact resume needs, in one file; `user` is an opaque section of the caller's.

@@ -914,6 +914,54 @@ int dqnhip_per_sample(dqnhip_handle h, uint64_t counter, int32_t n_batches, int3
  * last update, [minibatch] each: "u", "slot", "prob", "w", "td_abs".  count: floats the buffer holds. */
 int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
 
+/* ---- replay sweep: the nets evaluated over the stored memory (opt-in) ------------------------------------------------------------
+ * No reference counterpart: the reference's -learn_offline only logs the smoothed loss of the minibatches it happened to draw.
+ * dqnhip_evaluate_memory runs the update's forward passes — no backward, no optimiser step — over the logical transitions
+ * [first, first + n) (as dqnhip_read_memory counts them; n = -1: from first to the end of the memory; n = 0: a no-op — nothing is
+ * allocated, launched or captured — whose report is valid: all zero but for the iteration counters) in chunks of `minibatch` consecutive transitions, and reduces, per transition, with the nets as they stand:
+ *   q            Q(s, a_stored) of the online critic
+ *   y            the TD target exactly as the update forms it (src/dqn.cpp:892-900): terminal mask, gamma, the beta mix with
+ *                on_policy_target, the target nets
+ *   td           q - y, one float32 subtraction (dqnhip_diag_collect's definition)
+ *   q_policy     Q(s, mu(s)) of the online critic as it stands (the update evaluates it on the critic it has just stepped)
+ *   mc, reward   the stored on_policy_target and reward
+ *   q_minus_mc   q - mc, one float32 subtraction
+ *   action_match GetAction (TACKLE masked, the first maximum wins) gives the same index on mu(s) and on the stored actor output
+ * Each dqnhip_diag_row holds min, max, sum, sum_sq over the FINITE values and n_nonfinite (no finite value: min = max = 0); td_hist is
+ * the exponent histogram of td by dqnhip_diag_collect's bin rule (finite, non-zero values).  Every double sum is formed in one fixed
+ * order without floating-point atomics (csrc/sweep_kernels.hip.h): two sweeps with nothing in between return byte-identical reports,
+ * with and without use_graph.  The last chunk is padded with the window's last index; pad rows are counted nowhere.
+ * rows (may be NULL; so may each pointer in it): host arrays of n elements, one per transition of the window.
+ * A sweep overwrites the update's per-minibatch scratch: the gathered minibatch (input panels, reward / mc / terminal, "idx"), the
+ * activation panels, the [minibatch] row buffers q_target / y / q_train / q_policy / dq / actor_out / actor_target_out and the loss
+ * partials (what dqnhip_debug_read and dqnhip_diag_collect read: collect diagnostics of an update BEFORE sweeping); a refresh also
+ * the sampler's "slot", "prob" and "td_abs" (dqnhip_per_debug_read).  It ends a dqnhip_update_chained chain as any other update call
+ * does, and keeps 20 bytes of device memory per slot of the ring's capacity from the first sweep on.  It leaves
+ * everything else as it was: weights, solver histories, target nets, iteration counters, the sampling counters, the replay memory, the
+ * sticky flags, the (critic_loss, avg_q) pair and uncollected stats of dqnhip_update_indexed_n.
+ * Blocks until the report is there.  An out-of-range window is refused and nothing runs.
+ * v1 refuses: a phased update in progress; dp_world > 1 or a learner after dqnhip_dp_init*; precision = DQNHIP_FP16.  Learners that
+ * share parameters or a replay memory may evaluate.
+ *
+ * dqnhip_per_refresh: the same sweep on a prioritized learner (dqnhip_per_enable), and per chunk the update's own write-back: the
+ * leaf of every transition of the window becomes (|td| + eps)^alpha; a non-finite td leaves the old leaf; p_max is only ever raised;
+ * the nodes above are recomputed.  The remedy for a `.replaymemory` load, which gives every transition p_max.  out may be NULL. */
+typedef struct dqnhip_sweep_report {
+  int32_t struct_size;       /* in: sizeof(dqnhip_sweep_report) */
+  int32_t first, n, n_chunks;
+  int64_t n_terminal, n_action_match;
+  dqnhip_diag_row q, y, td, q_policy, mc, q_minus_mc, reward;
+  int32_t td_hist[DQNHIP_DIAG_BINS];
+  int32_t actor_iter, critic_iter;
+} dqnhip_sweep_report;
+typedef struct dqnhip_sweep_rows {
+  int32_t struct_size;       /* in: sizeof(dqnhip_sweep_rows) */
+  float *q, *y, *td, *q_policy;
+  int32_t* action_match;
+} dqnhip_sweep_rows;
+int dqnhip_evaluate_memory(dqnhip_handle h, int32_t first, int32_t n, dqnhip_sweep_report* out, const dqnhip_sweep_rows* rows);
+int dqnhip_per_refresh(dqnhip_handle h, int32_t first, int32_t n, dqnhip_sweep_report* out);
+
 /* ---- native learner-state file: exact resume (opt-in) -------------------------------------------------------------------------
  * No reference counterpart: the reference resumes from its three snapshot files (src/dqn_main.cpp:213-220, 268-286), which cannot
  * hold what this learner keeps on the device beside the weights — the target nets (Restore re-clones them), the sampling
