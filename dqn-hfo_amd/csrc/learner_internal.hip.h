@@ -13,11 +13,13 @@
 //                       dqnhip_per_refresh: sweep_kernels.hip.h; its forward launches are sweep_forward's, learner.hip), the launches
 //                       of the asynchronous state save and of the asynchronous Caffe snapshot (snapshot_kernels.hip.h)
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
-//   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state, and the host side of
-//                       dqnhip_save_state_async and dqnhip_snapshot_async (the writer thread they share; the kernels are launched
-//                       from learner_io.hip); host only
+//   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state; host only
+//   learner_save_async.hip  the host side of dqnhip_save_state_async and dqnhip_snapshot_async: the writer thread they share and
+//                       each one's staging buffer and job (the kernels are launched from learner_io.hip); host only.
+//                       learner_state.hip.h: what the two units above share
 //   snapshot.cpp        Caffe snapshot layout (no device code); snapshot_codec.h: its builders on host pointers, for the writer thread
-//   state_codec.cpp     the learner-state file's container (header, table, CRCs), dqnhip_state_info / _read_user (no device code, no HIP)
+//   state_codec.cpp     the learner-state file's container (header, table, CRCs) and its manifest (the order of the sections),
+//                       dqnhip_state_info / _read_user (no device code, no HIP)
 //   gzip_parallel.cpp   one gzip member from chunks deflated by a pool of threads: the asynchronous snapshot's .replaymemory (no HIP)
 // This header includes the ARGUMENT layer only (learner_args.hip.h has the map of the kernel headers): a unit includes the headers
 // of the kernels it launches and embeds exactly those (tests/test_kernel_inventory.py), the host-only units embed no device code.
@@ -138,7 +140,7 @@ struct PerHost {
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
 struct SweepHost;                       // replay sweep (learner_io.hip; the kernels: sweep_kernels.hip.h)
-struct StateAsync;                      // asynchronous learner-state save and Caffe snapshot (learner_state.hip; the kernels: state_kernels.hip.h, snapshot_kernels.hip.h)
+struct SaveWriter;                      // asynchronous learner-state save and Caffe snapshot (learner_save_async.hip; the kernels: state_kernels.hip.h, snapshot_kernels.hip.h)
 
 }  // namespace dqnhip_host
 
@@ -295,7 +297,7 @@ struct dqnhip_learner {
   // each kind (by refresh)
   SweepHost* sweep = nullptr;
   hipGraphExec_t sweep_graph[2] = {nullptr, nullptr};
-  StateAsync* sasync = nullptr;         // dqnhip_save_state_async / dqnhip_snapshot_async: the writer thread, the pinned ring and each kind's staging buffer, allocated at first use
+  SaveWriter* sasync = nullptr;        // dqnhip_save_state_async / dqnhip_snapshot_async: the writer thread, the pinned ring and each kind's staging buffer, allocated at first use
 };
 
 namespace dqnhip_host {
@@ -466,10 +468,10 @@ void sweep_free(H* h);                                   // the replay sweep's s
 int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev);
 int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a);
 int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a);
-// ... and its host side (learner_state.hip)
+// ... and its host side (learner_save_async.hip)
 int state_async_join(H* h, const char* what);            // waits for a save in flight; fails, as `what`, with its message if it failed
 void state_async_free(H* h);                             // dqnhip_destroy: joins both kinds of job, stops the writer thread, frees; never fails
-// asynchronous Caffe snapshot (dqnhip_snapshot_async): the launcher of snapshot_kernels.hip.h (learner_io.hip), the join (learner_state.hip)
+// asynchronous Caffe snapshot (dqnhip_snapshot_async): the launcher of snapshot_kernels.hip.h (learner_io.hip), the join (learner_save_async.hip)
 int snap_pack_replay_launch(H* h, uint8_t* stream_dev);
 int snapshot_async_join(H* h, const char* what);         // waits for a snapshot in flight; fails, as `what`, with its message if it failed
 

@@ -1298,7 +1298,7 @@ int dqnhip_get_kernel_timing(dqnhip_handle h, const char* family, float* avg_ms,
 
 }  // extern "C"
 
-// ---- asynchronous learner-state save: the launchers of state_kernels.hip.h (the host side: learner_state.hip) ----
+// ---- asynchronous learner-state save: the launchers of state_kernels.hip.h (the host side: learner_save_async.hip) ----
 namespace dqnhip_host {
 
 int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev) {

@@ -22,7 +22,7 @@
 namespace fs = std::filesystem;
 
 extern "C" int dqnhip_internal_set_error(const char* msg);
-// joins an asynchronous snapshot in flight (learner_state.hip); fails, as `what`, with its message if it failed
+// joins an asynchronous snapshot in flight (learner_save_async.hip); fails, as `what`, with its message if it failed
 extern "C" int dqnhip_internal_snapshot_join(dqnhip_handle h, const char* what);
 
 namespace {
@@ -235,8 +235,7 @@ int load_net_proto(const std::string& bytes, const std::vector<ParamBlob>& tbl, 
   return matched > 0 ? 0 : fail(path + ": no layer of this net found");
 }
 
-// Caffe's solvers that keep two history blobs per parameter (AdamSolver::AdamPreSolve, AdaDeltaSolver::AdaDeltaPreSolve)
-bool two_histories(int solver_type) { return solver_type == DQNHIP_SOLVER_ADAM || solver_type == DQNHIP_SOLVER_ADADELTA; }
+using dqnhip_snap::two_histories;
 
 // ---- file search helpers (src/dqn.cpp:80-121, 559-580) ------------------------------------------
 std::vector<std::string> files_matching_regexp(const std::string& regexp) {
@@ -283,8 +282,21 @@ std::string solverstate_proto(const std::vector<ParamBlob>& tbl, int iter, const
 
 }  // namespace
 
-// ---- the builders on host pointers: what the asynchronous snapshot's writer thread (learner_state.hip) calls ----
+// ---- the builders on host pointers: what the asynchronous snapshot's writer thread (learner_save_async.hip) calls ----
 namespace dqnhip_snap {
+
+bool two_histories(int solver_type) { return solver_type == DQNHIP_SOLVER_ADAM || solver_type == DQNHIP_SOLVER_ADADELTA; }
+Names names_of(const std::string& save_path, const std::string& prefix, int actor_iter, int critic_iter) {
+  static const char* const kNet[2] = {"_actor", "_critic"};      // snapshot_prefix of the solvers, src/dqn_main.cpp:247-248
+  const int iters[2] = {actor_iter, critic_iter};
+  Names n;
+  for (int net = 0; net < 2; ++net) {
+    const std::string tail = std::string(kNet[net]) + "_iter_" + std::to_string(iters[net]);      // Solver::SnapshotFilename
+    n.from[net] = save_path + tail; n.to[net] = prefix + tail;
+  }
+  n.memory = prefix + "_iter_" + std::to_string(std::max(actor_iter, critic_iter)) + ".replaymemory";
+  return n;
+}
 
 size_t dense_count(const dqnhip_config& c, int net) {
   std::vector<ParamBlob> tbl; size_t total = 0;
@@ -442,20 +454,15 @@ int dqnhip_snapshot(dqnhip_handle h, const char* save_path, const char* snapshot
   int32_t actor_iter = 0, critic_iter = 0;
   if (dqnhip_solver_snapshot(h, DQNHIP_ACTOR, (sp + "_actor").c_str(), &actor_iter)) return 1;    // snapshot_prefix of the solvers, src/dqn_main.cpp:247-248
   if (dqnhip_solver_snapshot(h, DQNHIP_CRITIC, (sp + "_critic").c_str(), &critic_iter)) return 1;
-  std::error_code ec;
-  auto mv = [&](const std::string& a, const std::string& b) -> int {
-    if (!fs::is_regular_file(a, ec)) return fail("missing " + a);                                  // CHECK(is_regular_file), :593-601
-    if (a != b) fs::rename(a, b, ec);
-    return ec ? fail("rename " + a + " -> " + b + " failed") : 0;
-  };
-  const std::string af = sp + "_actor_iter_" + std::to_string(actor_iter), at = pre + "_actor_iter_" + std::to_string(actor_iter);
-  const std::string cf = sp + "_critic_iter_" + std::to_string(critic_iter), ct = pre + "_critic_iter_" + std::to_string(critic_iter);
-  if (mv(af + ".caffemodel", at + ".caffemodel") || mv(af + ".solverstate", at + ".solverstate")) return 1;
-  if (mv(cf + ".caffemodel", ct + ".caffemodel") || mv(cf + ".solverstate", ct + ".solverstate")) return 1;
+  const dqnhip_snap::Names names = dqnhip_snap::names_of(sp, pre, actor_iter, critic_iter);
+  std::string err;
+  for (int net = 0; net < 2; ++net)
+    for (const char* ext : {".caffemodel", ".solverstate"})
+      if (dqnhip_snap::move_file(names.from[net] + ext, names.to[net] + ext, &err)) return fail(err);
   if (snapshot_memory) {
-    const std::string mem = pre + "_iter_" + std::to_string(std::max(actor_iter, critic_iter)) + ".replaymemory";
-    if (dqnhip_snapshot_replay_memory(h, mem.c_str())) return 1;
-    if (!fs::is_regular_file(mem, ec)) return fail("missing " + mem);
+    std::error_code ec;
+    if (dqnhip_snapshot_replay_memory(h, names.memory.c_str())) return 1;
+    if (!fs::is_regular_file(names.memory, ec)) return fail("missing " + names.memory);
   }
   if (remove_old) dqnhip_snap::remove_old_snapshots(pre, actor_iter, critic_iter);
   return 0;

@@ -1,6 +1,6 @@
 // snapshot_stream.h — the uncompressed `.replaymemory` stream (reference src/dqn.cpp:1146-1178) as the asynchronous Caffe snapshot
 // (dqnhip_snapshot_async) assembles it: what k_snap_pack_replay (snapshot_kernels.hip.h, launched from learner_io.hip) runs, its host
-// side (learner_state.hip) and the host test (tests/cpp/snapshot_stream_host.cpp) share.  Plain C++: no HIP header is needed.
+// side (learner_save_async.hip) and the host test (tests/cpp/snapshot_stream_host.cpp) share.  Plain C++: no HIP header is needed.
 //
 // The stream:  i32 n, then n records of R = 4 S + 49 bytes in logical order (logical i <- physical slot (head + i) % cap):
 //     S x f32 state | 10 x f32 actor output (the first 10 of act[cap][16]) | f32 reward | f32 on-policy target | u8 terminal (0 / 1)

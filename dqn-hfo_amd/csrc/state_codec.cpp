@@ -86,6 +86,49 @@ std::vector<uint8_t> build_head(const dqnhip_state_info_t& info, const std::vect
 
 uint32_t crc32_of(const void* p, uint64_t n) { return crc_of(p, n); }
 
+std::vector<ManifestEntry> manifest(const StateShape& s) {
+  std::vector<ManifestEntry> m;
+  for (int i = 0; i < kParSections; ++i) m.push_back({kTagPar[i], s.dense[par_net(i)] * sizeof(float), Src::Par, i});
+  // a learner whose solver is not Adam says so, and so does one with an lr policy or a weight decay: without either, the file is
+  // byte for byte what it was before those existed
+  if (s.has_solver) m.push_back({kTagSolver, sizeof(SolverSection), Src::Solver, 0});
+  if (s.has_lr) m.push_back({kTagLrSched, sizeof(LrSection), Src::Lr, 0});
+  m.push_back({kTagDev, sizeof(DevSection), Src::Dev, 0});
+  if (s.has_loss_scale) m.push_back({kTagLossScale, sizeof(LossScaleSection), Src::LossScale, 0});
+  m.push_back({kTagHost, sizeof(HostSection), Src::Host, 0});
+  if (s.with_memory) {
+    m.push_back({kTagRing, sizeof(RingSection), Src::Ring, 0});
+    for (int i = 0; i < ring_arrays(s.has_per); ++i) {
+      if (kRingArray[i].tag == kTagPerLeaves) m.push_back({kTagPerCfg, sizeof(PerSection), Src::PerCfg, 0});      // the leaves follow their PERC
+      m.push_back({kRingArray[i].tag, (uint64_t)s.ring_size * ring_row_bytes(i, s.state_size), Src::RingArray, i});
+    }
+  }
+  if (s.user_bytes) m.push_back({kTagUser, s.user_bytes, Src::User, 0});
+  return m;
+}
+
+const void* FixedSections::of(Src s) const {
+  const void* const by_src[] = {nullptr, nullptr, &solver, &lr, &dev, &ls, &host, &ring, &per, user};      // Src's order; Par, RingArray: the saver's own bytes
+  return by_src[(int)s];
+}
+
+dqnhip_state_info_t info_of(const dqnhip_config& c, int32_t flags, const StateShape& s, int32_t actor_iter, int32_t critic_iter, uint64_t update_counter) {
+  dqnhip_state_info_t info{};
+  info.struct_size = (int32_t)sizeof info; info.version = (int32_t)kVersion; info.flags = flags;
+  info.precision = c.precision; info.minibatch = c.minibatch; info.state_size = c.state_size; info.num_hidden = c.num_hidden;
+  for (int i = 0; i < c.num_hidden; ++i) info.hidden[i] = c.hidden[i];
+  info.replay_capacity = c.replay_capacity; info.memory_size = s.with_memory ? s.ring_size : 0;
+  info.actor_iter = actor_iter; info.critic_iter = critic_iter;
+  info.has_memory = s.with_memory; info.has_per = s.with_memory && s.has_per; info.has_loss_scale = s.has_loss_scale;
+  info.seed = c.seed; info.update_counter = update_counter;
+  return info;
+}
+
+std::string ring_range_error(int head, int size, int cap) {
+  if (head >= 0 && head < cap && size >= 0 && size <= cap) return "";
+  return "the ring's (head, size) = (" + std::to_string(head) + ", " + std::to_string(size) + ") is outside its capacity " + std::to_string(cap);
+}
+
 int write_file(const char* filename, const dqnhip_state_info_t& info, const std::vector<Section>& sections, std::string* err) {
   if (sections.size() > kMaxSections) return set(err, std::string(filename) + ": too many sections");
   std::vector<StreamEntry> e;

@@ -1,5 +1,6 @@
-// state_codec.h — the learner-state file's container (DESIGN.md 9 has the byte layout): what learner_state.hip needs of
-// state_codec.cpp.  Host code only; not installed, not part of the C-ABI.
+// state_codec.h — the learner-state file's container and its manifest, the ordered list of a file's sections (DESIGN.md 9 has the
+// byte layout): what learner_state.hip and learner_save_async.hip need of state_codec.cpp.  Host code only; not installed, not
+// part of the C-ABI.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dqnhip.h"
+#include "state_image.h"          // kRingArrays
 
 namespace dqnhip_state {
 
@@ -43,6 +45,44 @@ static_assert(sizeof(SolverSection) == 16, "SOLV is 16 bytes");
 static_assert(sizeof(LrSection) == 104, "LRSC is 104 bytes");
 static_assert(sizeof(DevSection) == 32 && sizeof(LossScaleSection) == 32 && sizeof(HostSection) == 16 && sizeof(RingSection) == 8 &&
               sizeof(PerSection) == 40, "the sections have no padding");
+
+// ---- the manifest: which sections a learner's file holds, in which order, each of how many bytes.  The one description of the
+// file's composition in the code: both savers walk it, the load takes every expected size from it ----
+// the eight parameter sections, in file order: W of the four nets, then (history 1, history 2) of each online net
+constexpr int kParSections = 8;
+constexpr uint32_t kTagPar[kParSections] = {kTagW[0], kTagW[1], kTagW[2], kTagW[3], kTagM[0], kTagV[0], kTagM[1], kTagV[1]};
+constexpr int par_net(int i) { return i < 4 ? i : (i - 4) / 2; }
+constexpr int par_kind(int i) { return i < 4 ? DQNHIP_KIND_W : (i - 4) % 2 ? DQNHIP_KIND_V : DQNHIP_KIND_M; }
+// the ring's arrays (state_image.h: kRingArrays), logical order, dense rows.  per_row 0: state_size elements
+struct RingArrayDesc { uint32_t tag, elem_bytes; int32_t per_row; };
+constexpr RingArrayDesc kRingArray[kRingArrays] = {{kTagStates, 4, 0}, {kTagNext, 4, 0}, {kTagAct, 4, DQNHIP_ACTOR_OUT}, {kTagReward, 4, 1},
+                                                   {kTagMc, 4, 1}, {kTagTerm, 1, 1}, {kTagPerLeaves, 4, 1}};
+constexpr int ring_arrays(bool has_per) { return has_per ? kRingArrays : kRingArrays - 1; }      // the leaves: a prioritized learner's
+constexpr uint32_t ring_width(int i, int state_size) { return (uint32_t)(kRingArray[i].per_row ? kRingArray[i].per_row : state_size); }
+constexpr uint32_t ring_row_bytes(int i, int state_size) { return ring_width(i, state_size) * kRingArray[i].elem_bytes; }
+
+// what a learner's file contains
+struct StateShape {
+  uint64_t dense[4] = {0, 0, 0, 0};      // float count of each net's dense parameters
+  int32_t state_size = 0;
+  bool has_solver = false, has_lr = false, has_loss_scale = false, with_memory = false, has_per = false;   // has_per: only with_memory
+  int32_t ring_size = 0;
+  uint64_t user_bytes = 0;
+};
+// where a section's bytes come from: parameter section `index`, ring array `index`, or one of the fixed structs
+enum class Src { Par, RingArray, Solver, Lr, Dev, LossScale, Host, Ring, PerCfg, User };
+struct ManifestEntry { uint32_t tag; uint64_t bytes; Src src; int index; };
+std::vector<ManifestEntry> manifest(const StateShape& s);
+// the fixed structs of one save (and the caller's user bytes), by source
+struct FixedSections {
+  SolverSection solver{}; LrSection lr{}; DevSection dev{}; LossScaleSection ls{}; HostSection host{}; RingSection ring{}; PerSection per{};
+  const void* user = nullptr;
+  const void* of(Src s) const;
+};
+// the header of a learner's file: its config, and the three values only the device knows
+dqnhip_state_info_t info_of(const dqnhip_config& c, int32_t flags, const StateShape& s, int32_t actor_iter, int32_t critic_iter, uint64_t update_counter);
+// empty, or why (head, size) is no window of a ring of `cap` slots
+std::string ring_range_error(int head, int size, int cap);
 
 struct Section { uint32_t tag; const void* data; uint64_t bytes; };
 struct Entry { uint32_t tag, crc; uint64_t offset, bytes; };

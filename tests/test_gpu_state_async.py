@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import state_ref
 from synth import synth_replay
 from test_gpu_state_file import _bits, _same
 
@@ -99,6 +100,25 @@ def test_fp16_dynamic_loss_scale(pkg, gpu, tmp_path):
               updates=5)
     _pair(pkg, d, tmp_path)
     assert pkg.state_info(str(tmp_path / "p1.learnerstate"))["has_loss_scale"] == 1
+    d.close()
+
+
+def test_every_optional_section_at_once(pkg, gpu, tmp_path):
+    """SOLV, LRSC, LSCL, the memory, PERC / PERL and USER in one file: a non-Adam solver under an lr policy with a weight decay, fp16 with
+    dynamic loss scaling, prioritized replay, a wrapped window of odd size, user bytes of odd length"""
+    d = _make(pkg, S=59, B=128, hidden=(128, 128), cap=96, fill=130, precision="fp16", loss_scale_mode="dynamic", loss_scale_growth_interval=3,
+              solver="RMSProp", actor_lr=1e-5, critic_lr=1e-3, momentum=0.0, rms_decay=0.99, lr_policy="step", lr_gamma=0.5, lr_stepsize=2,
+              weight_decay=1e-3, regularization="L2", per=dict(alpha=0.6, beta0=0.4, beta_anneal_iters=20), updates=5)
+    assert d.memory_size() == 95
+    user = bytes(range(7))
+    a, _ = _pair(pkg, d, tmp_path, user=user)
+    info, sections = state_ref.read_bytes(a)
+    assert list(sections) == ["WGT0", "WGT1", "WGT2", "WGT3", "ADM0", "ADV0", "ADM1", "ADV1", "SOLV", "LRSC", "DEVS", "LSCL", "HOST",
+                              "RING", "RSTA", "RNXT", "RACT", "RREW", "RMCT", "RTRM", "PERC", "PERL", "USER"]
+    out = state_ref.decode(info, sections)
+    assert out["states"].shape == (95, 59) and len(out["terminal"]) == len(out["leaves"]) == 95 and out["ring"]["ring_head"] != 0
+    assert out["user"] == user and out["dev"]["actor_iter"] == 5 and len(sections["SOLV"]) == 16 and len(sections["LRSC"]) == 104
+    assert (info["has_memory"], info["has_per"], info["has_loss_scale"]) == (1, 1, 1)
     d.close()
 
 
