@@ -5,6 +5,7 @@ import os
 from ._build import LIB, build
 
 MAX_HIDDEN = 8
+NSTEP_MAX = 64           # DQNHIP_NSTEP_MAX
 DP_ID_BYTES = 128        # DQNHIP_DP_ID_BYTES
 DP_PER_LAYER, DP_HALF_GRADS, DP_SHARD_OPT = 1, 2, 4    # dqnhip_dp_init flags
 DP_UNVERIFIED_OK = 256   # lets DP_PER_LAYER / DP_SHARD_OPT through for dp_world > 1 (never run on real links)
@@ -19,7 +20,7 @@ TUNE_LATE_GATHER = 128
 TUNE_NO_KERNARG_PRELOAD = 256
 # dqnhip_update_plan.forms bits (DQNHIP_PLAN_*), in bit order
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
-              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized")
+              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized", "n_step")
 LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
 FP32, FP16 = 0, 1                                   # DQNHIP_FP32 / DQNHIP_FP16: dqnhip_config.precision, dqnhip_set_act_precision
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
@@ -250,6 +251,11 @@ SIGNATURES = {
     "dqnhip_per_set_priorities": (C.c_int, [H, C.c_int32, C.c_int32, fp]),
     "dqnhip_per_sample": (C.c_int, [H, C.c_uint64, C.c_int32, ip, fp]),
     "dqnhip_per_debug_read": (C.c_int, [H, C.c_char_p, fp, C.c_size_t]),
+    "dqnhip_nstep_enable": (C.c_int, [H, C.c_int32]),
+    "dqnhip_nstep_get": (C.c_int, [H, ip]),
+    "dqnhip_nstep_debug_read": (C.c_int, [H, C.c_char_p, fp, C.c_size_t]),
+    "dqnhip_nstep_debug_read_f64": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_double), C.c_size_t]),
+    "dqnhip_nstep_validate": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(C.c_int64), ip]),
     "dqnhip_evaluate_memory": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(SweepReport), C.POINTER(SweepRows)]),
     "dqnhip_per_refresh": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(SweepReport)]),
     "dqnhip_save_state": (C.c_int, [H, C.c_char_p, C.c_int32, C.c_void_p, C.c_size_t]),

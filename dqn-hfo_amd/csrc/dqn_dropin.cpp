@@ -77,6 +77,13 @@ DEFINE_bool(prioritized_replay, false, "Proportional prioritized experience repl
 DEFINE_double(per_alpha, 0.6, "-prioritized_replay: the priority exponent (0: uniform). The paper's customary value, not measured on this workload.");
 DEFINE_double(per_beta, 0.4, "-prioritized_replay: the importance exponent at critic iteration 0. The paper's customary value, not measured on this workload.");
 DEFINE_int32(per_beta_anneal_iters, 0, "-prioritized_replay: critic iterations over which the importance exponent rises linearly to 1 (0: constant).");
+DEFINE_int32(n_step, 1, "N-step returns on the device (dqnhip_nstep_enable): the off-policy target of a sampled transition becomes "
+             "sum_{k<m} gamma^k r_{t+k} + gamma^m Q'(s_{t+m}, mu'(s_{t+m})), m <= N, shorter at an episode's end and at the memory's end. "
+             "1: off, nothing is called and the learner is what it was. Typical N (3 - 5) is the literature's value (D4PG, Rainbow), not "
+             "measured on this workload. Composes with -prioritized_replay; not combinable with -deferred_updates, -pipelined_stats, "
+             "-dp_world > 1, -evaluate_memory_freq or -per_refresh_on_load.");
+DEFINE_bool(n_step_validate_on_load, false, "LoadReplayMemory() checks, on the device, that every loaded non-terminal transition's next state is its "
+            "successor's state (dqnhip_nstep_validate: what n-step windows rely on) and aborts on a violation.");
 DEFINE_bool(native_state, false, "Snapshot() additionally writes <prefix>_iter_<N>.learnerstate (dqnhip_save_state: targets, sampling counters, loss-scale "
             "state, the ring's position, priorities, this object's random_engine and smoothed sums), and RestoreCriticSolver() loads the one "
             "that belongs to the restored iterations: resume is then bit-identical to never having stopped. The reference's files are "
@@ -284,6 +291,13 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     CHECK(!FLAGS_pipelined_stats) << "-prioritized_replay cannot be combined with -pipelined_stats";
     CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-prioritized_replay is a single-learner option (-dp_world 1, no -dp_rendezvous)";
   }
+  CHECK(FLAGS_n_step >= 1 && FLAGS_n_step <= DQNHIP_NSTEP_MAX) << "-n_step must lie in [1, " << DQNHIP_NSTEP_MAX << "] (got " << FLAGS_n_step << ")";
+  if (FLAGS_n_step > 1) {
+    CHECK(!FLAGS_deferred_updates) << "-n_step cannot be combined with -deferred_updates (a deferred burst runs as multi-update graphs on host-drawn indices, which n-step returns do not have in this version)";
+    CHECK(!FLAGS_pipelined_stats) << "-n_step cannot be combined with -pipelined_stats";
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-n_step is a single-learner option (-dp_world 1, no -dp_rendezvous)";
+    CHECK(FLAGS_evaluate_memory_freq == 0 && !FLAGS_per_refresh_on_load) << "-n_step cannot be combined with -evaluate_memory_freq / -per_refresh_on_load (the replay sweep forms 1-step targets)";
+  }
   std::vector<int> wa = TowerWidths(actor_solver_param_.net_param()), wc = TowerWidths(critic_solver_param_.net_param());
   if (wa.empty()) wa = kDefaultTower;
   if (wc.empty()) wc = kDefaultTower;
@@ -407,6 +421,10 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     pc.alpha = (float)FLAGS_per_alpha; pc.beta0 = (float)FLAGS_per_beta; pc.beta_anneal_iters = FLAGS_per_beta_anneal_iters;
     pc.seed = (uint64_t)seed;
     DQNHIP_CK(dqnhip_per_enable(h_, &pc));
+  }
+  if (FLAGS_n_step > 1) {
+    DQNHIP_CK(dqnhip_nstep_enable(h_, FLAGS_n_step));
+    LOG(INFO) << "[Agent" << tid << "] n-step returns: n = " << FLAGS_n_step;
   }
   if (dp_) {
     // one communicator per agent thread's learner: agents are independent DQNs (src/dqn_main.cpp:264), each its own group
@@ -538,6 +556,13 @@ void DQN::LoadReplayMemory(const std::string& f) {
   LOG(INFO) << "Loading replay memory from " << f;
   DQNHIP_CK(dqnhip_load_replay_memory(h_, f.c_str()));
   LOG(INFO) << "replay_mem_size = " << memory_size();
+  if (FLAGS_n_step_validate_on_load && memory_size() > 0) {
+    int64_t bad = 0; int32_t first_bad = -1;
+    DQNHIP_CK(dqnhip_nstep_validate(h_, 0, -1, &bad, &first_bad));
+    if (bad != 0) LOG(FATAL) << "[Agent" << tid_ << "] " << f << ": " << bad << " non-terminal transition(s) whose next state is not their successor's state (first: " << first_bad
+                             << "): n-step windows would mix episodes";
+    LOG(INFO) << "[Agent" << tid_ << "] [Memory] " << memory_size() << " transitions validated: every non-terminal transition is followed by its successor";
+  }
   if (FLAGS_per_refresh_on_load && memory_size() > 0) {
     dqnhip_sweep_report r;
     r.struct_size = (int32_t)sizeof r;
@@ -889,7 +914,8 @@ std::pair<float, float> DQN::UpdateActorCritic() {
     else DQNHIP_CK(dqnhip_update(h_, nullptr, &loss, &avgq));                 // CHECK(isfinite(target / loss)): the call fails
     return std::make_pair(loss, avgq);
   }
-  if (dp_ || FLAGS_pipelined_stats || !FLAGS_chained_updates) return UpdateActorCritic(SampleTransitionsFromMemory(minibatch_));
+  // (-n_step: the unchained call on the host-drawn indices — random_engine advances as the reference's does)
+  if (dp_ || FLAGS_pipelined_stats || !FLAGS_chained_updates || FLAGS_n_step > 1) return UpdateActorCritic(SampleTransitionsFromMemory(minibatch_));
   // The driver calls this in bursts (src/dqn_main.cpp:359-361), each call drawing its indices from random_engine (:501-509).  What the
   // NEXT call will draw is known now — unless something else draws from the engine or the memory changes in between: take it from a
   // COPY of the engine and hand it to the library as a prediction (dqnhip_update_chained: the next update's gather and first layers

@@ -1,4 +1,4 @@
-// head_kernels.hip.h — the head layers' training kernels, launched by learner.hip: TD target + Euclidean loss (k_head_q_train, or
+// head_kernels.hip.h — the head layers' training kernels, launched by learner.hip: TD target + Euclidean loss (k_head_q_train, its restatements k_head_q_train_w / k_head_q_train_n, or
 // inside the critic's top-layer dgrad launch: k_dgrad_qtrain), the heads' backward with the inverting gradients (k_head_bwd,
 // k_head_bwd_big + k_head_wred, k_dqda_head_bwd).  The heads' forward: head_fwd_kernels.hip.h.
 #pragma once
@@ -118,6 +118,88 @@ static __global__ __launch_bounds__(256) void k_head_q_train_w(HeadTrainWArgs aw
     a.dq[row] = dq_row;
     d2 = (d * d) * w;
     aw.w[row] = w; aw.td_abs[row] = fabsf(d);
+  }
+  if ((a.dZ != nullptr || a.dZ16 != nullptr) && row < a.rows) {     // (wave-uniform condition)
+    const float dqv = __shfl(dq_row, 0, 64);
+    const size_t x0 = (size_t)row * a.H;
+    const float sc16 = a.dZ16 != nullptr ? ls_live(a.scale16, a.ls_mult) : 0.0f;
+    auto seed = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 xv = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), wv = *reinterpret_cast<const f32x4*>(a.W + k);
+        f32x4 dz;
+        dz.x = (dqv * wv.x) * lrelu_mask(xv.x); dz.y = (dqv * wv.y) * lrelu_mask(xv.y);
+        dz.z = (dqv * wv.z) * lrelu_mask(xv.z); dz.w = (dqv * wv.w) * lrelu_mask(xv.w);
+        if constexpr (decltype(tag)::value)
+          *reinterpret_cast<head_h4*>(a.dZ16 + x0 + k) = head_h4{(_Float16)(dz.x * sc16), (_Float16)(dz.y * sc16), (_Float16)(dz.z * sc16), (_Float16)(dz.w * sc16)};
+        else
+          *reinterpret_cast<f32x4*>(a.dZ + x0 + k) = dz;
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, seed);
+  }
+  if (lane == 0) s_part[wave] = d2;
+  __syncthreads();
+  if (threadIdx.x == 0) a.loss_partial[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
+// n-step returns: k_head_q_train (WEIGHTED: k_head_q_train_w) restated with a per-row discount — again a copy, so that the two keep
+// their instruction streams.  a.reward[row] is the window's discounted reward sum R and disc[row] = gamma^m (k_gather_n); the
+// target is k_head_q_train's expression with disc[row] in a.gamma's place and R in r's: off = term ? R : (float)((double)R +
+// disc (double)q').  At m = 1 (every row of an n = 1 learner) disc is gamma and R is r: the 1-step kernels' bits.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_head_q_train_n(HeadTrainNArgs an) {
+  const HeadTrainWArgs& aw = an.w;
+  const HeadTrainArgs& a = aw.t;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  __shared__ float s_part[4];
+  float at = 0.0f, ao = 0.0f;
+  float bt0 = 0.0f, b0 = 0.0f, r = 0.0f, mcv = 0.0f, tm = 0.0f, pr = 1.0f;
+  double disc = 0.0;
+  if (row < a.rows && lane == 0) {
+    bt0 = a.bt[0]; b0 = a.b[0]; r = a.reward[row]; mcv = a.mc[row]; tm = a.term[row]; disc = an.disc[row];
+    if constexpr (WEIGHTED) pr = aw.prob[row];
+  }
+  float pmin = INFINITY;
+  if constexpr (WEIGHTED)
+    for (int j = lane; j < a.rows; j += 64) pmin = fminf(pmin, aw.prob[j]);
+  if (row < a.rows) {
+    const size_t x0 = (size_t)row * a.H;
+    auto dots = [&](auto tag) {
+      for (int k = lane * 4; k < a.H; k += 256) {
+        const f32x4 v0 = head_ld4t<decltype(tag)::value>(a.Xt, a.Xt16, x0 + k), w0 = *reinterpret_cast<const f32x4*>(a.Wt + k);
+        const f32x4 v1 = head_ld4t<decltype(tag)::value>(a.X, a.X16, x0 + k), w1 = *reinterpret_cast<const f32x4*>(a.W + k);
+        at = fmaf(v0.x, w0.x, at); at = fmaf(v0.y, w0.y, at); at = fmaf(v0.z, w0.z, at); at = fmaf(v0.w, w0.w, at);
+        ao = fmaf(v1.x, w1.x, ao); ao = fmaf(v1.y, w1.y, ao); ao = fmaf(v1.z, w1.z, ao); ao = fmaf(v1.w, w1.w, ao);
+      }
+    };
+    HEAD_DISPATCH(a.X16 != nullptr, dots);
+  }
+  at = wave_sum64(at); ao = wave_sum64(ao);
+  if constexpr (WEIGHTED) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pmin = fminf(pmin, __shfl_xor(pmin, off, 64));
+  }
+  float d2 = 0.0f, dq_row = 0.0f;
+  if (row < a.rows && lane == 0) {
+    const float qt = at + bt0, q = ao + b0;
+    a.q_target[row] = qt; a.q[row] = q;
+    const float off_policy = tm != 0.0f ? r : (float)((double)r + disc * (double)qt);
+    const float target = (float)(a.beta * (double)mcv + (1 - a.beta) * (double)off_policy);
+    a.y[row] = target;
+    if (!isfinite(target)) atomicOr(&a.st->flags, kFlagTarget);   // CHECK(std::isfinite(target)), src/dqn.cpp:898
+    const float d = q - target;
+    if constexpr (WEIGHTED) {
+      const float beta = per_beta_now(aw.beta0, aw.beta_anneal_iters, a.st->critic_iter);
+      const float w = beta == 0.0f ? 1.0f : powf(__fdiv_rn(pmin, pr), beta);
+      dq_row = (a.inv_batch * d) * w;
+      d2 = (d * d) * w;
+      aw.w[row] = w; aw.td_abs[row] = fabsf(d);
+    } else {
+      dq_row = a.inv_batch * d;
+      d2 = d * d;
+    }
+    a.dq[row] = dq_row;
   }
   if ((a.dZ != nullptr || a.dZ16 != nullptr) && row < a.rows) {     // (wave-uniform condition)
     const float dqv = __shfl(dq_row, 0, 64);

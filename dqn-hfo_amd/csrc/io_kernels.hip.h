@@ -81,6 +81,37 @@ static __global__ void k_sample_states(Ring ring, const DevState* rs, const int*
   for (int c = lane; c < ring.S; c += 64) out[(size_t)row * ring.S + c] = ring.state[slot * ring.SP + c];
 }
 
+// dqnhip_nstep_validate: the invariant n-step windows stand on — a non-terminal transition's stored next state IS the state of its
+// logical successor, bit for bit over the S floats.  One wave per transition of [first, first + n), waves striding over the range; the
+// ring's last transition has no successor and is exempt.  Each block folds its waves' count and smallest offending logical index in
+// LDS and adds them to the two result words with one integer atomic each: whatever the order, the same two numbers.
+static __global__ __launch_bounds__(256) void k_nstep_validate(NstepValidateArgs a) {
+  __shared__ int s_cnt[4], s_min[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const Ring& ring = a.ring;
+  const int size = a.rs->ring_size;
+  const long long head = a.rs->ring_head;
+  int cnt = 0, mn = 0x7FFFFFFF;
+  for (long long i = (long long)blockIdx.x * 4 + wave; i < a.n; i += (long long)gridDim.x * 4) {
+    const long long li = (long long)a.first + i;
+    if (li >= size - 1) continue;                                  // (wave-uniform) the last transition, or beyond the memory
+    const long long slot = (head + li) % ring.cap, succ = (head + li + 1) % ring.cap;
+    if (ring.term[slot]) continue;
+    const uint32_t* nx = reinterpret_cast<const uint32_t*>(ring.next + slot * ring.SP);
+    const uint32_t* sn = reinterpret_cast<const uint32_t*>(ring.state + succ * ring.SP);
+    bool bad = false;
+    for (int c = lane; c < ring.S; c += 64) bad |= nx[c] != sn[c];
+    if (__ballot(bad)) { cnt += 1; mn = mn < (int)li ? mn : (int)li; }
+  }
+  if (lane == 0) { s_cnt[wave] = cnt; s_min[wave] = mn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int c = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    const int m01 = s_min[0] < s_min[1] ? s_min[0] : s_min[1], m23 = s_min[2] < s_min[3] ? s_min[2] : s_min[3];
+    if (c) { atomicAdd(a.violations, (unsigned long long)c); atomicMin(a.first_bad, m01 < m23 ? m01 : m23); }
+  }
+}
+
 // ---- acting-time helpers ---------------------------------------------------------
 // dense [n][S] -> padded panel [npad][SP] (pad rows/cols zero)
 static __global__ void k_pack_rows(const float* __restrict__ src, int n, int S, float* __restrict__ dst,

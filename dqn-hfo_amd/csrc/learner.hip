@@ -592,10 +592,30 @@ static TickArgs tick_args(const H* h, bool dp) {
                   h->cap_stats ? h->cap_stats + 4 * std::max(h->cap_u, 0) : h->stats_dev};
 }
 // 1-2: sample + gather (src/dqn.cpp:846-887).  Later updates of a multi-update graph: it rode in the previous update's last launch
+// (n-step returns: k_gather_n, the same arguments + the window — always a launch of its own, plan_of: no multi-update riders)
 static int gather_launch(H* h, hipStream_t st, const int* idx_dev) {
+  if (h->nstep && h->cap_u >= 0) return fail("internal: an n-step update inside a multi-update schedule");
   if (h->cap_u > 0) return 0;
   const GatherArgs g = gather_args(h, idx_dev, h->cap_u);
+  if (h->nstep) {
+    const GatherNArgs a{g, h->nstep->n, (double)h->cfg.gamma, h->nstep->disc, h->nstep->steps};
+    HIPCHK(launch(st, k_gather_n, dim3(g.blocks), dim3(256), 0, a));
+    return 0;
+  }
   HIPCHK(launch(st, k_gather, dim3(g.blocks), dim3(256), 0, g));
+  return 0;
+}
+// Step(1)'s head arithmetic in a launch of its own: k_head_q_train, its weighted form (prioritized replay), or the per-row-discount
+// form of either (n-step returns)
+static int q_train_launch(H* h, hipStream_t st, const UpdatePlan& P, const HeadTrainArgs& t) {
+  const dim3 grid((h->B + 3) / 4);
+  if (P.nstep) {
+    const HeadTrainNArgs an{P.prioritized ? q_train_w_args(h, t) : HeadTrainWArgs{t}, h->nstep->disc};
+    if (P.prioritized) HIPCHK(launch(st, k_head_q_train_n<true>, grid, dim3(256), 0, an));
+    else HIPCHK(launch(st, k_head_q_train_n<false>, grid, dim3(256), 0, an));
+  }
+  else if (P.prioritized) HIPCHK(launch(st, k_head_q_train_w, grid, dim3(256), 0, q_train_w_args(h, t)));
+  else HIPCHK(launch(st, k_head_q_train, grid, dim3(256), 0, t));
   return 0;
 }
 
@@ -632,8 +652,7 @@ int run_phase16(H* h, int phase, const int* idx_dev) {
       // with the head's dW / db riding in the net's last backward launch, the scaled fp16 tower-top gradient comes out of
       // this launch too (HeadTrainArgs::dZ16) — Step(1) has no head-backward launch (as on the fp32 path)
       if (P.fuse_q) { t.dZ16 = h->dZ16[1][L]; t.scale16 = h->ls_c; t.ls_mult = lsm_c; }
-      if (P.prioritized) HIPCHK(launch(st, k_head_q_train_w, dim3((B + 3) / 4), dim3(256), 0, q_train_w_args(h, t)));
-      else HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, t));
+      RC(q_train_launch(h, st, P, t));
     }
     const TailsArgs tails_c = critic_tails(h);
     {
@@ -805,8 +824,7 @@ int run_phase(H* h, int phase, const int* idx_dev) {
     // with the head's dW / db riding in the net's last backward launch, the head's dZ comes out of this launch too
     if (P.head_rides_c) qt_args.dZ = h->dZc[L];
     qt_args.pdt = h->qdot[0]; qt_args.pd = h->qdot[1];
-    if (P.prioritized) HIPCHK(launch(st, k_head_q_train_w, dim3((B + 3) / 4), dim3(256), 0, q_train_w_args(h, qt_args)));      // (plan_of: never with fuse_q)
-    else if (!fuse_q) HIPCHK(launch(st, k_head_q_train, dim3((B + 3) / 4), dim3(256), 0, qt_args));
+    if (!fuse_q) RC(q_train_launch(h, st, P, qt_args));      // (plan_of: prioritized replay and n-step returns never with fuse_q)
     // critic backward (rest of Step(1)): head (dgrad + ReLU' + wgrad fused), then tower; wgrad
     // writes (beta=0) so ClearParamDiffs/ZeroGradParameters (src/dqn.cpp:63-78, 908-909) vanish
     {

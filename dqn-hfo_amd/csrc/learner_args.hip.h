@@ -152,6 +152,22 @@ struct GatherArgs {
   const LrSchedule* sched;
 };
 
+// n-step returns (dqnhip_nstep_enable; k_gather_n): the gather's arguments + the window.  Row `row` of the minibatch starts at logical
+// index li and covers m <= n transitions: up to the first terminal one, the ring's last one, or n.  reward[row] becomes the discounted
+// sum R of the window's rewards, term / the next-state panels come from the window's last transition, disc[row] = gamma^m.
+constexpr int kNstepMax = 64;    // one lane per transition of a window
+struct GatherNArgs {
+  GatherArgs g;
+  int n;                               // 1 .. kNstepMax
+  double gamma;                        // cfg.gamma as the head kernel reads it
+  double* disc; int* steps;            // [B] out: gamma^m, m
+};
+// k_nstep_validate: the contiguity invariant n-step windows stand on, over the logical range [first, first + n)
+struct NstepValidateArgs {
+  Ring ring; const DevState* rs; int first, n;
+  unsigned long long* violations; int* first_bad;      // += the non-terminal transitions whose stored next state is not their successor's state; min= their logical index
+};
+
 // ---- head layers (head_fwd_kernels.hip.h, head_kernels.hip.h) ----------------------------------------------------------------
 enum HeadMode { HEAD_ACTOR = 0, HEAD_Q = 1, HEAD_Q_TRAIN = 2, HEAD_Q_POLICY = 3 };      // the MODE of k_head_fwd* / head_forward<>
 struct HeadArgs {
@@ -210,6 +226,13 @@ struct HeadTrainWArgs {
   const float* prob;                   // [rows]: the sampling probability of each row's transition (k_per_sample / k_per_fill)
   float* w; float* td_abs;             // [rows] out: the row's weight, |q - target|
   float beta0; int beta_anneal_iters;  // beta = min(1, beta0 + (1 - beta0) critic_iter / beta_anneal_iters); 0 iterations: constant
+};
+
+// k_head_q_train_n<WEIGHTED> (n-step returns): k_head_q_train's (WEIGHTED: k_head_q_train_w's) arguments + each row's discount, which
+// takes t.gamma's place; t.reward holds the window's discounted reward sum (k_gather_n).  Not WEIGHTED: prob / w / td_abs are unused
+struct HeadTrainNArgs {
+  HeadTrainWArgs w;
+  const double* disc;                  // [rows]: gamma^m of each row's window
 };
 
 // k_head_bwd

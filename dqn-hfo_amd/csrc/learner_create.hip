@@ -285,6 +285,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   drop_graphs(h);
   per_free(h);
+  nstep_free(h);
   diag_free(h);
   sweep_free(h);
   for (int i = 0; i < 2; ++i) {

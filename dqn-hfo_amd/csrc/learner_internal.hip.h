@@ -8,7 +8,7 @@
 //   learner_update.hip  index staging, graph capture (capture_updates), dqnhip_update* / dqnhip_get_update_plan / dqnhip_read_stats,
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
-//   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), parameters, multi-agent sharing,
+//   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), n-step returns (dqnhip_nstep_*), parameters, multi-agent sharing,
 //                       introspection, update diagnostics (dqnhip_diag_collect), the replay sweep (dqnhip_evaluate_memory /
 //                       dqnhip_per_refresh: sweep_kernels.hip.h; its forward launches are sweep_forward's, learner.hip), the launches
 //                       of the asynchronous state save and of the asynchronous Caffe snapshot (snapshot_kernels.hip.h)
@@ -137,6 +137,12 @@ struct PerHost {
   // the host's upper bound on the transitions appended since the last k_per_sync, and whether the ring may have changed at all
   long long pending = 0; bool changed = false;
   long long syncs = 0;                  // k_per_sync launches so far
+};
+// n-step returns (dqnhip_nstep_enable; k_gather_n, k_head_q_train_n).  Owned by the learner that enabled it, whoever owns the ring.
+struct NstepHost {
+  int n = 1;                            // 1 .. kNstepMax
+  double* disc = nullptr; int* steps = nullptr;     // [B]: gamma^m and m of the last update's rows (the gathered reward buffer holds R)
+  unsigned long long* viol = nullptr;   // dqnhip_nstep_validate's two result words: {violations, first_bad (an int in the second word)}
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
 struct SweepHost;                       // replay sweep (learner_io.hip; the kernels: sweep_kernels.hip.h)
@@ -292,6 +298,7 @@ struct dqnhip_learner {
   int ix_prev_flags = 0;                // the sticky device flags as the last harvested update left them (a raise = a bit not in here)
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
+  NstepHost* nstep = nullptr;           // n-step returns (dqnhip_nstep_enable); null: the 1-step target, nothing of it runs
   DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
   // replay sweep (dqnhip_evaluate_memory / dqnhip_per_refresh): its scratch, allocated by the first sweep, and one captured chunk of
   // each kind (by refresh)
@@ -395,6 +402,7 @@ struct UpdatePlan {
   bool early_l0;                    // multi-update graphs: next gather in the critic's optimiser launch, next first layers in the actor's
   bool tails_ride;                  // data parallel: the [loss, q, flag] tails block rides in each net's last backward launch (no k_tails launches)
   bool prioritized;                 // prioritized replay: k_per_sample / k_per_fill before, k_head_q_train_w inside, k_per_update behind every update
+  bool nstep;                       // n-step returns: k_gather_n first, k_head_q_train_n<prioritized> in the head launch's place; the stand-alone sequence per update
 };
 UpdatePlan plan_of(const H* h);
 // the current update's copies of the two double-buffered panels (by update parity inside a multi-update graph that gathers early;
@@ -462,6 +470,11 @@ void per_free(H* h);
 int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behind everything enqueued so far
 int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
 int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
+// n-step returns (learner_io.hip)
+int nstep_refuse(const H* h, const char* what);          // fails, naming n-step returns, if they are enabled on h
+void nstep_free(H* h);
+// does every update of this learner run the stand-alone sequence, also inside a multi-update graph?  (no rider serves a successor)
+inline bool standalone_updates(const H* h) { return h->per != nullptr || h->nstep != nullptr; }
 void diag_free(H* h);                                    // dqnhip_diag_collect's scratch
 void sweep_free(H* h);                                   // the replay sweep's scratch
 // asynchronous learner-state save: the launchers of state_kernels.hip.h, on the learner's stream (learner_io.hip) ...

@@ -696,6 +696,110 @@ int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t
   return 0;
 }
 
+// ---- n-step returns (include/dqnhip.h; k_gather_n: small_kernels.hip.h, launched by learner.hip; k_nstep_validate: io_kernels.hip.h) ----
+
+}  // extern "C"
+
+namespace dqnhip_host {
+
+int nstep_refuse(const H* h, const char* what) {
+  return h->nstep ? fail("%s: not available on a learner with n-step returns (dqnhip_nstep_enable) in this version", what) : 0;
+}
+void nstep_free(H* h) {
+  NstepHost* p = h->nstep;
+  if (!p) return;
+  hipFree(p->disc); hipFree(p->steps); hipFree(p->viol);
+  delete p;
+  h->nstep = nullptr;
+}
+
+}  // namespace dqnhip_host
+
+extern "C" {
+
+int dqnhip_nstep_enable(dqnhip_handle h, int32_t n) {
+  if (!h) return fail("dqnhip_nstep_enable: null handle (n-step returns are enabled on an existing learner)");
+  if (n < 1 || n > kNstepMax) return fail("dqnhip_nstep_enable: n-step returns take n in [1, %d] (got %d)", kNstepMax, n);
+  if (h->cfg.dp_world > 1 || h->comm || h->dp_half || h->dp_shard) return fail("dqnhip_nstep_enable: n-step returns on a data-parallel learner (dp_world > 1, dqnhip_dp_init) are not supported in this version");
+  if (h->next_phase != 0) return fail("dqnhip_nstep_enable: a phased update is in progress (next phase %d)", h->next_phase);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h->nstep) {
+    NstepHost* p = new NstepHost();
+    h->nstep = p;               // (from here on nstep_free releases whatever was allocated)
+    const size_t B = h->B;
+    auto alloc = [&](void** d, size_t bytes) -> int { HIPCHK(hipMalloc(d, bytes)); HIPCHK(hipMemset(*d, 0, bytes)); return 0; };
+    if (alloc((void**)&p->disc, B * sizeof(double)) || alloc((void**)&p->steps, B * sizeof(int)) || alloc((void**)&p->viol, 2 * sizeof(unsigned long long))) { nstep_free(h); return 1; }
+  }
+  h->nstep->n = n;
+  h->epoch += 1;
+  drop_graphs(h);
+  return 0;
+}
+
+int dqnhip_nstep_get(dqnhip_handle h, int32_t* n) {
+  if (!h || !n) return fail("dqnhip_nstep_get: null argument");
+  *n = h->nstep ? h->nstep->n : 0;
+  return 0;
+}
+
+static int nstep_ready(dqnhip_handle h, const char* what, const char* name, const void* host) {
+  if (!h || !name || !host) return fail("%s: null argument", what);
+  if (!h->nstep) return fail("%s: n-step returns are not enabled on this learner (dqnhip_nstep_enable)", what);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  return 0;
+}
+int dqnhip_nstep_debug_read(dqnhip_handle h, const char* name, float* host, size_t count) {
+  RC(nstep_ready(h, "dqnhip_nstep_debug_read", name, host));
+  const size_t B = h->B;
+  const bool is_steps = !strcmp(name, "steps");
+  if (!is_steps && strcmp(name, "reward")) return fail("dqnhip_nstep_debug_read: unknown buffer '%s' (reward|steps; \"disc\" is a double: dqnhip_nstep_debug_read_f64)", name);
+  if (count < B) return fail("buffer too small for '%s': %zu < %zu", name, count, B);
+  HIPCHK(hipMemcpyAsync(host, is_steps ? (const void*)h->nstep->steps : (const void*)h->mb_reward, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (is_steps) for (size_t i = 0; i < B; ++i) { int v; memcpy(&v, &host[i], sizeof v); host[i] = (float)v; }
+  return 0;
+}
+int dqnhip_nstep_debug_read_f64(dqnhip_handle h, const char* name, double* host, size_t count) {
+  RC(nstep_ready(h, "dqnhip_nstep_debug_read_f64", name, host));
+  const size_t B = h->B;
+  if (strcmp(name, "disc")) return fail("dqnhip_nstep_debug_read_f64: unknown buffer '%s' (disc)", name);
+  if (count < B) return fail("buffer too small for '%s': %zu < %zu", name, count, B);
+  HIPCHK(hipMemcpyAsync(host, h->nstep->disc, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int dqnhip_nstep_validate(dqnhip_handle h, int32_t first, int32_t n, int64_t* violations, int32_t* first_bad) {
+  if (!h) return fail("dqnhip_nstep_validate: null handle");
+  if (!violations || !first_bad) return fail("dqnhip_nstep_validate: null result pointer");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RingUse ring_use(h);
+  RC(refresh_ring(h));
+  const long long size = RO(h)->h_size;
+  if (first < 0 || first > size || n < -1 || (n >= 0 && (long long)first + n > size))
+    return fail("dqnhip_nstep_validate: the window [%d,%lld) lies outside the memory [0,%lld)", first, n < 0 ? size : (long long)first + n, size);
+  if (n < 0) n = (int32_t)(size - first);
+  *violations = 0; *first_bad = -1;
+  if (n == 0) return 0;
+  // (the scratch: the n-step learner's, or the staging buffer of a learner that only validates)
+  unsigned long long* res = h->nstep ? h->nstep->viol : nullptr;
+  HIPCHK(hipStreamSynchronize(h->stream));       // the staging buffer may still be in flight
+  if (!res) { RC(ensure_stage(h, 2 * sizeof(unsigned long long))); res = (unsigned long long*)h->stage_dev; }
+  const unsigned long long init[2] = {0ull, 0x7FFFFFFFull};
+  HIPCHK(hipMemcpyAsync(res, init, sizeof init, hipMemcpyHostToDevice, h->stream));
+  const H* o = RO(h);
+  NstepValidateArgs a{o->ring, (const DevState*)o->st, first, n, res, (int*)(res + 1)};
+  const int blocks = (int)std::max(1LL, std::min(4096LL, ((long long)n + 3) / 4));
+  HIPCHK(launch(h->stream, k_nstep_validate, dim3(blocks), dim3(256), 0, a));
+  unsigned long long out[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(out, res, sizeof out, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *violations = (int64_t)out[0];
+  if (out[0]) { int fb; memcpy(&fb, &out[1], sizeof fb); *first_bad = fb; }
+  return 0;
+}
+
 // ---- parameters ----------------------------------------------------------------------
 
 static float* arena_ptr(H* h, int net, int kind) {
@@ -1194,6 +1298,8 @@ static int sweep_run(H* h, const char* what, bool refresh, int32_t first, int32_
   if (rows && rows->struct_size != (int32_t)sizeof(dqnhip_sweep_rows))
     return fail("%s: dqnhip_sweep_rows.struct_size %d != %zu (ABI mismatch)", what, rows->struct_size, sizeof(dqnhip_sweep_rows));
   if (refresh && !h->per) return fail("%s: the replay sweep refreshes priorities, and prioritized replay is not enabled on this learner (dqnhip_per_enable)", what);
+  // (the sweep evaluates 1-step targets: on an n-step learner it would report 1-step errors and write 1-step priorities)
+  RC(nstep_refuse(h, what));
   if (h->next_phase != 0) return fail("%s: the replay sweep overwrites the update's panels, and a phased update is in progress (next phase %d)", what, h->next_phase);
   if (h->cfg.dp_world > 1 || h->comm || h->dp_half || h->dp_shard)
     return fail("%s: the replay sweep is not available on a data-parallel learner (dp_world > 1, dqnhip_dp_init) in this version", what);

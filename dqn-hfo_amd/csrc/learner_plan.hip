@@ -207,6 +207,7 @@ UpdatePlan plan_of(const H* h) {
   p.dp = h->cfg.dp_world > 1 || h->dp_half || h->dp_shard;     // (a one-rank group with bf16 exchange / a sharded optimiser runs the N-rank code path)
   p.fused_seed = !(tf & DQNHIP_TUNE_SEPARATE_HEAD_SEED);
   p.prioritized = h->per != nullptr;
+  p.nstep = h->nstep != nullptr;
   if (h->fp16) {
     // fp16 learner: the head's dW / db are column-sum workgroups of the net's last backward launch (hgemm_group_db, HeadWsum)
     // when that launch exists; Step(1)'s k_head_q_train then also writes the scaled fp16 tower-top gradient — no head-backward launch
@@ -227,7 +228,8 @@ UpdatePlan plan_of(const H* h) {
   p.head_rides_a = !head_big_ok(h, B, Hh) && head_wgrad_can_ride(la, B);
   // Step(1)'s head arithmetic inside the critic's top-layer dgrad launch (k_dgrad_qtrain; one 16-column piece per lane: H / 16 <= 64)
   // (prioritized replay: the DQNHIP_TUNE_SEPARATE_Q_TRAIN form, k_head_q_train_w in k_head_q_train's place)
-  p.fuse_q = !p.prioritized && h->U3 != nullptr && !(tf & DQNHIP_TUNE_SEPARATE_Q_TRAIN) && p.head_rides_c && p.shifted_c && Hc >= 512 && Hc <= 1024 && Hc % 256 == 0;
+  // (n-step returns: the same form, k_head_q_train_n there)
+  p.fuse_q = !p.prioritized && !p.nstep && h->U3 != nullptr && !(tf & DQNHIP_TUNE_SEPARATE_Q_TRAIN) && p.head_rides_c && p.shifted_c && Hc >= 512 && Hc <= 1024 && Hc % 256 == 0;
   // dQ/da's last step, the inverting gradients and the actor heads' backward in ONE launch (k_dqda_head_bwd): 16 columns from the first
   // action column inside the panel row, fewer than 1024 rows, any tower-top width
   p.fuse_head = p.head_rides_a && !(tf & DQNHIP_TUNE_SEPARATE_ACTOR_HEAD_BWD) && dqda_head_shape_ok(h, lc.kp[0]);
@@ -242,7 +244,8 @@ UpdatePlan plan_of(const H* h) {
   // inside a multi-update graph: the next update's gather rides in the critic's optimiser launch and its four first layers in the
   // actor's (k_adam_soft_fwd1_gather / k_adam_soft_l0).  Needs every piece those riders stand on.
   // (prioritized replay: an update's indices do not exist before its predecessor's write-back — no rider gathers ahead)
-  p.early_l0 = !p.prioritized && h->Xa_s2[1] != nullptr && !(tf & DQNHIP_TUNE_LATE_GATHER) && p.critic_l0 && p.first_layers_merged && h->shared_fl[DQNHIP_ACTOR] == 0 &&
+  // (n-step returns: the riders carry gather_block, not the window walk — v1 gathers in a launch of its own)
+  p.early_l0 = !p.prioritized && !p.nstep && h->Xa_s2[1] != nullptr && !(tf & DQNHIP_TUNE_LATE_GATHER) && p.critic_l0 && p.first_layers_merged && h->shared_fl[DQNHIP_ACTOR] == 0 &&
                la.kp[0] == 64 && l0_can_ride(la);
   // the first-layer riders step their slice with Adam's expression (adam_apply4): the other solvers' optimiser launches carry none —
   // the schedule DQNHIP_TUNE_SEPARATE_FIRST_LAYER | DQNHIP_TUNE_LATE_GATHER give an Adam learner

@@ -92,8 +92,8 @@ int capture_exec(H* h, const CaptureSpec& s, hipGraphExec_t* out, int* kernel_no
 // first kernel of the next (kernel trace, profiles/r04_graph_gap.txt; two instances of the graph launched alternately: the same) -
 // 2.8 % of a 300-us update; inside a graph the same boundary is a plain kernel boundary, and the gather of update u + 1 rides in
 // update u's last launch (adam_launch, DevState::gbase).
-// (a prioritized learner's graph: n stand-alone sequences back to back — no rider serves a successor)
-static CaptureSpec multi_spec(const H* h, int n) { CaptureSpec s; s.updates = n; s.multi = h->per == nullptr; s.of = n; return s; }
+// (a prioritized or n-step learner's graph: n stand-alone sequences back to back — no rider serves a successor)
+static CaptureSpec multi_spec(const H* h, int n) { CaptureSpec s; s.updates = n; s.multi = !standalone_updates(h); s.of = n; return s; }
 
 // what each slot of graph_exec captures.  idx_dev: the pipelined slots' index buffer (already on the device)
 static CaptureSpec slot_spec(const H* h, GraphSlot slot, const int* idx_dev) {
@@ -161,7 +161,7 @@ static int count_kernel_nodes(hipGraph_t g, int* out) {
 // the kernels `updates` consecutive updates launch — as a multi-update graph captures them (multi) or stand-alone.  A capture that
 // is thrown away: nothing executes, nothing is instantiated.
 static int count_launches(H* h, bool multi, int updates, int* out) {
-  CaptureSpec s; s.updates = updates; s.multi = multi && h->per == nullptr;
+  CaptureSpec s; s.updates = updates; s.multi = multi && !standalone_updates(h);
   hipGraph_t graph = nullptr;
   RC(capture_updates(h, s, &graph));
   const int rc = count_kernel_nodes(graph, out);
@@ -256,7 +256,7 @@ static int update_plan_fill(H* h, dqnhip_update_plan* out) {
                (p.fused_seed ? DQNHIP_PLAN_HEAD_SEED_FUSED : 0) | (p.fuse_head ? DQNHIP_PLAN_DQDA_HEAD_BWD : 0) |
                (p.critic_l0 ? DQNHIP_PLAN_CRITIC_L0_RIDES : 0) | (p.first_layers_merged ? DQNHIP_PLAN_FIRST_LAYERS_MERGED : 0) |
                (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0) |
-               (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0);
+               (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0) | (p.nstep ? DQNHIP_PLAN_NSTEP : 0);
   out->updates_per_graph = kMultiU; out->solver_type = h->cfg.solver_type;
   // per net and update: one all-reduce (per-layer buckets: one per tower layer + the head slice; bf16 exchange: the tails travel in a
   // second call beside the actor's; sharded optimiser: reduce-scatter + the 4-float all-reduce + 2 (fp16 learner: 4) all-gathers)
@@ -338,6 +338,7 @@ int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host, int32_t n)
   h->epoch += 1;
   if (n < 0) return fail("dqnhip_update_indexed_n: n must be >= 0");
   RC(per_refuse(h, "dqnhip_update_indexed_n"));
+  RC(nstep_refuse(h, "dqnhip_update_indexed_n"));
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_indexed_n: a phased update is in progress (next phase %d)", h->next_phase);
@@ -406,6 +407,7 @@ int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss, float* avg_q, int3
 int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host) {
   if (!h) return fail("null handle");
   RC(per_refuse(h, "dqnhip_update_phase"));
+  RC(nstep_refuse(h, "dqnhip_update_phase"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   // (with DQNHIP_DP_HALF_GRADS the exchange — bf16 image, all-reduce, widening by the clip-norm pass — lives inside
@@ -533,6 +535,7 @@ int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_
   if (!h) return fail("null handle");
   if (!idx_host) return fail("dqnhip_update_chained: explicit indices required (on-device sampling: dqnhip_update_async_n)");
   RC(per_refuse(h, "dqnhip_update_chained"));
+  RC(nstep_refuse(h, "dqnhip_update_chained"));
   HIPCHK(hipSetDevice(h->cfg.device));
   const UpdatePlan P = plan_of(h);
   const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && h->sharers == 0 && h->w_owner == nullptr;
@@ -580,6 +583,7 @@ int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_
 int dqnhip_update_pipelined(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, float* avg_q) {
   if (!h) return fail("null handle");
   RC(per_refuse(h, "dqnhip_update_pipelined"));
+  RC(nstep_refuse(h, "dqnhip_update_pipelined"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");

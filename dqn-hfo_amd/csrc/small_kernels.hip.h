@@ -1,4 +1,4 @@
-// small_kernels.hip.h — the small kernels learner.hip launches around the GEMMs and heads: the update's first launch (k_gather), the
+// small_kernels.hip.h — the small kernels learner.hip launches around the GEMMs and heads: the update's first launch (k_gather; k_gather_n with n-step returns), the
 // clip norm's passes (k_sumsq*, k_to_bf16), the fused clip + Adam + soft-update pass with its riders (k_adam_soft*), the data-parallel
 // tails and shards (k_tails, k_shard_*), k_advance_iter.  (Kernels are static: a unit that includes this embeds all of them.)
 // What else once lived under this name is in learner_args.hip.h (structs), update_bodies.hip.h (device functions), head_kernels.hip.h,
@@ -10,6 +10,8 @@ namespace dqnhip {
 
 // the minibatch gather in a launch of its own (gather_block, update_bodies.hip.h)
 static __global__ void k_gather(GatherArgs g) { gather_block(g, (int)blockIdx.x); }
+// ... of a learner with n-step returns (gather_n_block): the update's first launch there, always a launch of its own
+static __global__ void k_gather_n(GatherNArgs a) { gather_n_block(a, (int)blockIdx.x); }
 
 // ---- optimiser -----------------------------------------------------------------
 // Sum of squares of a gradient arena -> per-block partials (used after an

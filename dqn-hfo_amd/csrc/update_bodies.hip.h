@@ -122,6 +122,94 @@ __device__ __forceinline__ void gather_block(const GatherArgs& g, const int blk)
   }
 }
 
+// ---- the n-step gather (k_gather_n; dqnhip_nstep_enable) ----------------------------------------------------------------------
+// The window's discounted reward sum, Horner from the back, in double and without contraction, rounded to float once:
+// acc = r[m - 1]; acc = (double)r[k] + gamma acc for k = m - 2 .. 0.  rv: lane k holds r[li + k]; m is wave-uniform and the whole
+// wave walks the chain (the shuffles need every lane), so every lane returns R.  At m = 1 it is r[li] exactly.
+__device__ __forceinline__ float nstep_reward(float rv, int m, double gamma) {
+#pragma clang fp contract(off)
+  double acc = (double)__shfl(rv, m - 1, 64);
+  for (int k = m - 2; k >= 0; --k) acc = (double)__shfl(rv, k, 64) + gamma * acc;
+  return (float)acc;
+}
+// gamma^m as m - 1 successive products (what a caller who wants the same bits on the host writes down); gamma itself at m = 1
+__device__ __forceinline__ double nstep_discount(int m, double gamma) {
+  double d = gamma;
+  for (int k = 1; k < m; ++k) d = d * gamma;
+  return d;
+}
+// gather_block with a window behind every sampled index (a copy of its row part, so that gather_block — its riders, its register
+// budget — stays the code it is; the scalars block IS gather_block's).  One wave per row: lane k < n reads reward and terminal of
+// logical li + k where that is inside the ring (slot (ring_head + li + k) % cap: a window may cross the ring's physical end); the
+// window ends at the first lane that holds a terminal transition, the ring's last one, or lane n - 1: one ballot gives its length
+// m.  State and action come from li, next state and terminal from b = li + m - 1.  Every path that fills the ring appends whole
+// episodes contiguously, so b's stored next state is the state m steps after li's (k_nstep_validate checks that).
+// Beside gather_block's traffic: at most n reward words and n terminal bytes per row.
+__device__ __forceinline__ void gather_n_block(const GatherNArgs& a, const int blk) {
+  const GatherArgs& g = a.g;
+  if (blk == g.blocks - 1) { gather_block(g, blk); return; }      // the scalars block: the same code
+  const DevState* st = g.st;
+  const GatherOut& o = g.o; const Ring& ring = g.ring;
+  const int row = blk * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= g.B) return;
+  const int size = g.rs->ring_size;
+  int li;
+  if (g.idx_in != nullptr) li = g.idx_in[row];
+  else {
+    const unsigned long long ctr = g.ahead < 0 ? st->update_counter : st->gbase_counter + (unsigned long long)g.ahead;
+    const uint32_t u = philox_u32(g.seed, ctr, (uint32_t)row);
+    li = (int)(((uint64_t)u * (uint64_t)size) >> 32);
+  }
+  li = li < 0 ? 0 : (li >= size ? size - 1 : li);
+  const long long head = g.rs->ring_head;
+  float rv = 0.0f; int tv = 0;
+  if (lane < a.n && li + lane < size) {
+    const long long sk = (head + li + lane) % ring.cap;
+    rv = ring.reward[sk]; tv = ring.term[sk];
+  }
+  const unsigned long long ends = __ballot(lane < a.n && (tv != 0 || li + lane >= size - 1 || lane == a.n - 1));
+  const int m = __ffsll((long long)ends);          // 1 .. n: lane n - 1 always votes
+  const float R = nstep_reward(rv, m, a.gamma);
+  const int tb = __shfl(tv, m - 1, 64);
+  const long long slot = (head + li) % ring.cap, slot_b = (head + li + m - 1) % ring.cap;
+  const float* sp = ring.state + slot * ring.SP;
+  const float* np = ring.next + slot_b * ring.SP;
+  const float* ap = ring.act + slot * kAP;
+  const int S = ring.S;
+  if (o.Xa_s != nullptr)
+  for (int c = lane; c < o.KcP; c += 64) {
+    const float sv = c < S ? sp[c] : 0.0f;
+    const float nv = c < S ? np[c] : 0.0f;
+    const float av = (c >= S && c < S + kNO) ? ap[c - S] : 0.0f;
+    if (c < o.KaP) { o.Xa_s[(size_t)row * o.KaP + c] = sv; o.Xa_n[(size_t)row * o.KaP + c] = nv; }
+    o.Xc_tr[(size_t)row * o.KcP + c] = c < S ? sv : av;
+    o.Xc_pl[(size_t)row * o.KcP + c] = sv;
+    o.Xc_nx[(size_t)row * o.KcP + c] = nv;
+  }
+  if (o.Ha_s != nullptr) {
+    // (gather_block's fp16 panel loop: two columns per lane, 8-byte loads inside whole 256-B ring rows)
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    typedef __attribute__((ext_vector_type(2))) float f2;
+    for (int c = lane * 2; c < o.KcP; c += 128) {
+      f2 sv = f2{0.f, 0.f}, nv = f2{0.f, 0.f};
+      if (c < S) { sv = *reinterpret_cast<const f2*>(sp + c); nv = *reinterpret_cast<const f2*>(np + c); }
+      if (c + 1 >= S) { sv.y = 0.0f; nv.y = 0.0f; }
+      const float a0 = (c >= S && c < S + kNO) ? ap[c - S] : 0.0f, a1 = (c + 1 >= S && c + 1 < S + kNO) ? ap[c + 1 - S] : 0.0f;
+      const h2 hs = h2{(_Float16)sv.x, (_Float16)sv.y}, hn = h2{(_Float16)nv.x, (_Float16)nv.y};
+      if (c < o.KaP) { *reinterpret_cast<h2*>(o.Ha_s + (size_t)row * o.KaP + c) = hs; *reinterpret_cast<h2*>(o.Ha_n + (size_t)row * o.KaP + c) = hn; }
+      *reinterpret_cast<h2*>(o.Hc_tr + (size_t)row * o.KcP + c) = h2{(_Float16)(c < S ? sv.x : a0), (_Float16)(c + 1 < S ? sv.y : a1)};
+      *reinterpret_cast<h2*>(o.Hc_pl + (size_t)row * o.KcP + c) = hs;
+      *reinterpret_cast<h2*>(o.Hc_nx + (size_t)row * o.KcP + c) = hn;
+    }
+  }
+  if (lane == 0) {
+    o.reward[row] = R; o.mc[row] = ring.mc[slot];
+    o.term[row] = tb ? 1.0f : 0.0f; o.idx[row] = li;
+    a.disc[row] = nstep_discount(m, a.gamma); a.steps[row] = m;
+  }
+}
+
 // ---- skinny head layers ------------------------------------------------------
 // action_layer(4) + actionpara_layer(6) of the actor and q_values_layer(1) of
 // the critic (src/dqn.cpp:426-427, 450) are K=H4 dot products per row: one wave

@@ -809,6 +809,39 @@ class DQN:
         self._ck(self.lib.dqnhip_per_debug_read(self.h, name.encode(), _p(out), out.size))
         return out.astype(np.int64) if name == "slot" else out
 
+    # -- n-step returns (include/dqnhip.h: no reference counterpart, off unless enabled) ----------------------
+    def enable_n_step(self, n):
+        """dqnhip_nstep_enable: the off-policy target becomes sum_{k<m} gamma^k r_{t+k} + gamma^m Q'(s_{t+m}, mu'(s_{t+m})) with m <= n
+        (shorter at a terminal transition and at the memory's end).  n in 1 .. 64 (1: the 1-step learner's bits, on the n-step
+        schedule); may be called again; there is no disable.  Typical n (3 - 5) is the literature's value, not measured here."""
+        self._ck(self.lib.dqnhip_nstep_enable(self.h, int(n)))
+
+    def n_step(self):
+        """dqnhip_nstep_get: n, or 0 if n-step returns were never enabled."""
+        n = C.c_int32()
+        self._ck(self.lib.dqnhip_nstep_get(self.h, C.byref(n)))
+        return n.value
+
+    def n_step_debug_read(self, name):
+        """Of the last update, [B]: "reward" (the window's discounted reward sum, float32), "steps" (the window's length, int64) or
+        "disc" (gamma^steps, float64)."""
+        B = self.kMinibatchSize
+        if name == "disc":
+            out = np.empty(B, np.float64)
+            self._ck(self.lib.dqnhip_nstep_debug_read_f64(self.h, name.encode(), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+            return out
+        out = np.empty(B, np.float32)
+        self._ck(self.lib.dqnhip_nstep_debug_read(self.h, name.encode(), _p(out), out.size))
+        return out.astype(np.int64) if name == "steps" else out
+
+    def validate_memory(self, first=0, n=None):
+        """dqnhip_nstep_validate over the logical transitions [first, first + n) (n = None: to the end) -> (violations, first_bad):
+        how many non-terminal transitions' stored next state is not, bit for bit, the state of their logical successor, and the
+        smallest such index (-1: none).  Any learner may validate."""
+        v, fb = C.c_int64(), C.c_int32()
+        self._ck(self.lib.dqnhip_nstep_validate(self.h, int(first), -1 if n is None else int(n), C.byref(v), C.byref(fb)))
+        return v.value, fb.value
+
     # -- replay sweep (include/dqnhip.h: the nets evaluated over the stored memory, opt-in) -------------------
     @staticmethod
     def _sweep_dict(r):

@@ -405,6 +405,7 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world);
 #define DQNHIP_PLAN_EARLY_GATHER_L0 2048        /* multi-update graphs: next gather / next first layers ride in the two optimiser launches (DQNHIP_TUNE_LATE_GATHER) */
 #define DQNHIP_PLAN_DP_TAILS_RIDE 4096          /* data parallel: the [loss, q, flag] tails of the exchange ride in each net's last backward launch */
 #define DQNHIP_PLAN_PRIORITIZED 8192            /* prioritized replay (dqnhip_per_enable): sampler / fill before, k_head_q_train_w inside, the write-back behind every update */
+#define DQNHIP_PLAN_NSTEP 16384                 /* n-step returns (dqnhip_nstep_enable): k_gather_n first, k_head_q_train_n in the head launch's place; the stand-alone sequence per update */
 typedef struct dqnhip_update_plan {
   int32_t struct_size;          /* in: sizeof(dqnhip_update_plan) */
   int32_t forms;                /* DQNHIP_PLAN_* bits */
@@ -913,6 +914,47 @@ int dqnhip_per_sample(dqnhip_handle h, uint64_t counter, int32_t n_batches, int3
 /* "level<k>" (k = 0: the cap leaves by PHYSICAL slot; level k has ceil(cap / 64^k) nodes, the last one is the total), and of the
  * last update, [minibatch] each: "u", "slot", "prob", "w", "td_abs".  count: floats the buffer holds. */
 int dqnhip_per_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
+
+/* ---- n-step returns (opt-in) ----------------------------------------------------------------------------------------------------
+ * No reference counterpart: the reference's off-policy target is one step, r + gamma Q'(s', mu'(s')) (src/dqn.cpp:892-900), and so is
+ * that of every learner that never calls dqnhip_nstep_enable — it launches exactly the kernels it launched before this section
+ * existed.  With n-step returns the off-policy target of a sampled transition t becomes
+ *   sum_{k < m} gamma^k r_{t+k} + gamma^m Q'(s_{t+m}, mu'(s_{t+m}))
+ * gathered on the device from the ring as it is (no new array).  For a sampled logical index li, ring size `size`, gamma = cfg.gamma:
+ *   m     the smallest k in 1 .. n with terminal[li + k - 1] != 0, or li + k - 1 == size - 1, or k == n
+ *   R     acc = r[li + m - 1]; for k = m - 2 .. 0: acc = (double)r[li + k] + gamma * acc; R = (float)acc   (double, no contraction)
+ *   disc  d = gamma, then m - 1 times d = d * gamma                                                          (a double)
+ *   b     li + m - 1: the next state and the terminal flag are those stored with b; state, action, on_policy_target, "idx": li's
+ *   off   terminal ? R : (float)((double)R + disc * (double)q'), then the beta mix and everything after it as in the 1-step update
+ * At n = 1 every bit is the 1-step learner's.  The window walks LOGICAL successors, so it relies on the invariant the
+ * `.replaymemory` format relies on too: the logical successor of a non-terminal transition is the next step of its episode.  Every
+ * path that fills the memory appends whole episodes contiguously (the caller's dqnhip_add_transitions of a labelled episode, the
+ * env front-ends' flush, dqnhip_load_replay_memory, dqnhip_load_state); a caller that appends anything else — single transitions
+ * from interleaved episodes — breaks it, and dqnhip_nstep_validate says so.  An episode whose head was evicted keeps a valid
+ * suffix; a window never reads beyond the ring's last transition.
+ * Schedule: what a prioritized learner runs — the stand-alone sequence per update (fp32: the DQNHIP_TUNE_SEPARATE_Q_TRAIN form, no
+ * gather-ahead riders; inside dqnhip_update_async_n's graphs the sequences back to back), k_gather_n as its first launch and
+ * k_head_q_train_n as its head launch.  Composes with prioritized replay (the sampler feeds the indices, |q - y_n| is written back),
+ * both precisions, every solver and lr policy, shared replay memories and parameters, env front-ends, dqnhip_diag_collect.
+ * v1 refuses, on an n-step learner: dqnhip_update_chained / _pipelined / _indexed_n / _phase, dqnhip_dp_init*, dp_world > 1,
+ * dqnhip_evaluate_memory / dqnhip_per_refresh (the sweep forms 1-step targets).  The learner-state file does not hold n (a
+ * hyper-parameter, not state): enable it again before dqnhip_load_state.  Typical n (3 - 5) is the literature's value (D4PG,
+ * Rainbow), NOT measured on this workload. */
+#define DQNHIP_NSTEP_MAX 64
+/* n in [1, DQNHIP_NSTEP_MAX]; may be called again with another n; drops the captured update graphs; there is no disable. */
+int dqnhip_nstep_enable(dqnhip_handle h, int32_t n);
+/* *n = 0 if n-step returns were never enabled on this learner. */
+int dqnhip_nstep_get(dqnhip_handle h, int32_t* n);
+/* Of the last update, [minibatch] each: "reward" (R) and "steps" (m, as floats the way dqnhip_debug_read serves "idx").  The
+ * discount is a double and has an entry point of its own: dqnhip_nstep_debug_read_f64 serves "disc".  count: elements the buffer
+ * holds.  The window's terminal flag and "idx" are dqnhip_debug_read's "terminal" and "idx". */
+int dqnhip_nstep_debug_read(dqnhip_handle h, const char* name, float* host, size_t count);
+int dqnhip_nstep_debug_read_f64(dqnhip_handle h, const char* name, double* host, size_t count);
+/* The invariant above over the logical range [first, first + n) (n = -1: to the end): *violations = the non-terminal transitions
+ * whose stored next state differs, bitwise over state_size floats, from the state of their logical successor (the memory's last
+ * transition is exempt), *first_bad = the smallest such logical index, -1 when there is none.  Any learner may validate, n-step or
+ * not.  Stream-ordered, blocks. */
+int dqnhip_nstep_validate(dqnhip_handle h, int32_t first, int32_t n, int64_t* violations, int32_t* first_bad);
 
 /* ---- replay sweep: the nets evaluated over the stored memory (opt-in) ------------------------------------------------------------
  * No reference counterpart: the reference's -learn_offline only logs the smoothed loss of the minibatches it happened to draw.
