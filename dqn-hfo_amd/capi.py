@@ -20,7 +20,7 @@ TUNE_LATE_GATHER = 128
 TUNE_NO_KERNARG_PRELOAD = 256
 # dqnhip_update_plan.forms bits (DQNHIP_PLAN_*), in bit order
 PLAN_FORMS = ("fp16", "data_parallel", "bwd_shifted_critic", "bwd_shifted_actor", "head_wgrad_rides_critic", "head_wgrad_rides_actor",
-              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized", "n_step")
+              "q_train_in_dgrad", "head_seed_fused", "dqda_head_bwd", "critic_l0_rides", "first_layers_merged", "early_gather_l0", "dp_tails_ride", "prioritized", "n_step", "target_smoothing")
 LOSS_SCALE_STATIC, LOSS_SCALE_DYNAMIC = 0, 1        # dqnhip_config.loss_scale_mode
 FP32, FP16 = 0, 1                                   # DQNHIP_FP32 / DQNHIP_FP16: dqnhip_config.precision, dqnhip_set_act_precision
 ACTOR, CRITIC, ACTOR_TARGET, CRITIC_TARGET = 0, 1, 2, 3
@@ -284,6 +284,22 @@ SIGNATURES.update({
 })
 
 ENV_NO_RECORD = 1        # DQNHIP_ENV_NO_RECORD
+NOISE_EXPLORE, NOISE_TARGET = 0, 1   # DQNHIP_NOISE_*
+
+
+class NoiseConfig(C.Structure):
+    """struct dqnhip_noise_config (include/dqnhip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("clamp", C.c_int32), ("sigma_logits", C.c_float), ("sigma_params", C.c_float),
+                ("theta", C.c_float), ("clip", C.c_float), ("seed", C.c_uint64)]
+
+
+SIGNATURES.update({
+    "dqnhip_noise_default_config": (C.c_int, [C.POINTER(NoiseConfig), C.c_int32]),
+    "dqnhip_noise_explore_host": (C.c_int, [C.POINTER(NoiseConfig), C.c_uint64, C.c_int32, fp, fp]),
+    "dqnhip_env_set_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseConfig)]),
+    "dqnhip_target_noise_enable": (C.c_int, [H, C.POINTER(NoiseConfig)]),
+    "dqnhip_target_noise_get": (C.c_int, [H, ip, C.POINTER(NoiseConfig)]),
+})
 
 
 class EnvEpisode(C.Structure):

@@ -82,6 +82,17 @@ DEFINE_int32(n_step, 1, "N-step returns on the device (dqnhip_nstep_enable): the
              "1: off, nothing is called and the learner is what it was. Typical N (3 - 5) is the literature's value (D4PG, Rainbow), not "
              "measured on this workload. Composes with -prioritized_replay; not combinable with -deferred_updates, -pipelined_stats, "
              "-dp_world > 1, -evaluate_memory_freq or -per_refresh_on_load.");
+DEFINE_double(explore_noise_sigma, 0.0, "Ornstein-Uhlenbeck exploration noise on the six action parameters of SelectAction's GREEDY output, in units of "
+              "each parameter's range (100 for the powers, 360 for the angles), clamped to the parameter's bounds; the four action logits "
+              "and the epsilon-random outputs stay as they are. One state per learner, reset by LabelTransitions (the episode's end). The "
+              "noise has its own counter-based generator: random_engine's call order stays the reference's. 0: off. The literature's "
+              "value is 0.1 (not measured on this workload).");
+DEFINE_double(explore_noise_theta, 0.15, "-explore_noise_sigma: the mean reversion of the OU state, in (0, 1]; 1 is white Gaussian noise.");
+DEFINE_double(target_noise_sigma, 0.0, "Target policy smoothing (TD3; dqnhip_target_noise_enable): the critic-target's action input becomes "
+              "clamp(mu'(s') + range * clip(sigma * z)) with z standard normal per row and column, sigma in units of each column's range "
+              "(2 for the logits, 100 for the powers, 360 for the angles). 0: off, nothing is called. TD3's value is 0.1 (0.2 on a "
+              "range of 2; not measured on this workload). -precision fp32, single learner, not with -deferred_updates or -pipelined_stats.");
+DEFINE_double(target_noise_clip, 0.25, "-target_noise_sigma: the bound on sigma * z, in units of the range (TD3's 0.5 on a range of 2); 0: no clip.");
 DEFINE_bool(n_step_validate_on_load, false, "LoadReplayMemory() checks, on the device, that every loaded non-terminal transition's next state is its "
             "successor's state (dqnhip_nstep_validate: what n-step windows rely on) and aborts on a violation.");
 DEFINE_bool(native_state, false, "Snapshot() additionally writes <prefix>_iter_<N>.learnerstate (dqnhip_save_state: targets, sampling counters, loss-scale "
@@ -272,6 +283,7 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     LOG(INFO) << "Seeding RNG with seed = " << FLAGS_seed;
   }
   random_engine.seed(seed);
+  explore_seed_ = seed;          // (-explore_noise_sigma: the key of the noise draws; random_engine itself is not drawn from for them)
   // -gpu=false selects Caffe's CPU solver in the reference (KeepPlayingGames: Caffe::set_mode(Caffe::CPU),
   // src/dqn_main.cpp:208-212).  This library replaces the GPU path only and by design has no CPU fallback — a learner that
   // silently computed somewhere else would void every measurement — so the flag ends here, through the driver's own logging
@@ -290,6 +302,16 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     CHECK(!FLAGS_deferred_updates) << "-prioritized_replay cannot be combined with -deferred_updates (a deferred burst runs on indices drawn ahead; a prioritized update's indices do not exist before its predecessor's write-back)";
     CHECK(!FLAGS_pipelined_stats) << "-prioritized_replay cannot be combined with -pipelined_stats";
     CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-prioritized_replay is a single-learner option (-dp_world 1, no -dp_rendezvous)";
+  }
+  CHECK(FLAGS_explore_noise_sigma >= 0.0 && std::isfinite(FLAGS_explore_noise_sigma)) << "-explore_noise_sigma must be >= 0 and finite (got " << FLAGS_explore_noise_sigma << ")";
+  CHECK(FLAGS_explore_noise_theta > 0.0 && FLAGS_explore_noise_theta <= 1.0) << "-explore_noise_theta must lie in (0, 1] (got " << FLAGS_explore_noise_theta << ")";
+  CHECK(FLAGS_target_noise_sigma >= 0.0 && std::isfinite(FLAGS_target_noise_sigma)) << "-target_noise_sigma must be >= 0 and finite (got " << FLAGS_target_noise_sigma << ")";
+  CHECK(FLAGS_target_noise_clip >= 0.0 && std::isfinite(FLAGS_target_noise_clip)) << "-target_noise_clip must be >= 0 and finite (got " << FLAGS_target_noise_clip << ")";
+  if (FLAGS_target_noise_sigma > 0.0) {
+    CHECK(!FLAGS_deferred_updates) << "-target_noise_sigma cannot be combined with -deferred_updates (target smoothing has no host-indexed graph form in this version)";
+    CHECK(!FLAGS_pipelined_stats) << "-target_noise_sigma cannot be combined with -pipelined_stats";
+    CHECK(FLAGS_dp_world == 1 && FLAGS_dp_rendezvous.empty()) << "-target_noise_sigma is a single-learner option (-dp_world 1, no -dp_rendezvous)";
+    CHECK(FLAGS_precision != "fp16") << "-target_noise_sigma needs -precision fp32 (target smoothing has no fp16 form in this version)";
   }
   CHECK(FLAGS_n_step >= 1 && FLAGS_n_step <= DQNHIP_NSTEP_MAX) << "-n_step must lie in [1, " << DQNHIP_NSTEP_MAX << "] (got " << FLAGS_n_step << ")";
   if (FLAGS_n_step > 1) {
@@ -421,6 +443,13 @@ DQN::DQN(caffe::SolverParameter& actor_solver_param, caffe::SolverParameter& cri
     pc.alpha = (float)FLAGS_per_alpha; pc.beta0 = (float)FLAGS_per_beta; pc.beta_anneal_iters = FLAGS_per_beta_anneal_iters;
     pc.seed = (uint64_t)seed;
     DQNHIP_CK(dqnhip_per_enable(h_, &pc));
+  }
+  if (FLAGS_target_noise_sigma > 0.0) {
+    dqnhip_noise_config nc;
+    DQNHIP_CK(dqnhip_noise_default_config(&nc, DQNHIP_NOISE_TARGET));
+    nc.sigma_logits = nc.sigma_params = (float)FLAGS_target_noise_sigma; nc.clip = (float)FLAGS_target_noise_clip; nc.seed = (uint64_t)seed;
+    DQNHIP_CK(dqnhip_target_noise_enable(h_, &nc));
+    LOG(INFO) << "[Agent" << tid << "] target smoothing: sigma = " << FLAGS_target_noise_sigma << ", clip = " << FLAGS_target_noise_clip;
   }
   if (FLAGS_n_step > 1) {
     DQNHIP_CK(dqnhip_nstep_enable(h_, FLAGS_n_step));
@@ -714,6 +743,14 @@ std::vector<ActorOutput> DQN::SelectActions(const std::vector<InputStates>& stat
     std::copy(sp->begin(), sp->end(), s.begin() + n * state_size_);
   }
   DQNHIP_CK(dqnhip_select_actions(h_, s.data(), (int)states_batch.size(), out[0].data()));
+  if (FLAGS_explore_noise_sigma > 0.0) {
+    dqnhip_noise_config nc;
+    DQNHIP_CK(dqnhip_noise_default_config(&nc, DQNHIP_NOISE_EXPLORE));
+    nc.sigma_params = (float)FLAGS_explore_noise_sigma; nc.theta = (float)FLAGS_explore_noise_theta; nc.seed = explore_seed_;
+    if (explore_ou_.size() < out.size() * out[0].size()) explore_ou_.resize(out.size() * out[0].size(), 0.f);
+    for (size_t n = 0; n < out.size(); ++n) DQNHIP_CK(dqnhip_noise_explore_host(&nc, explore_calls_, (int)n, &explore_ou_[n * out[0].size()], out[n].data()));
+    explore_calls_ += 1;
+  }
   return out;
 }
 
@@ -765,6 +802,7 @@ void DQN::AddTransitions(const std::vector<Transition>& ts) {
 
 void DQN::LabelTransitions(std::vector<Transition>& ts) {
   CHECK_GT(ts.size(), 0u) << "Need at least one transition to label.";
+  std::fill(explore_ou_.begin(), explore_ou_.end(), 0.f);       // the episode is over: -explore_noise_sigma starts the next one from zero
   std::vector<float> r(ts.size()), mc(ts.size());
   for (size_t i = 0; i < ts.size(); ++i) r[i] = std::get<2>(ts[i]);
   DQNHIP_CK(dqnhip_label_transitions(gamma_, r.data(), (int)ts.size(), mc.data()));
@@ -915,7 +953,7 @@ std::pair<float, float> DQN::UpdateActorCritic() {
     return std::make_pair(loss, avgq);
   }
   // (-n_step: the unchained call on the host-drawn indices — random_engine advances as the reference's does)
-  if (dp_ || FLAGS_pipelined_stats || !FLAGS_chained_updates || FLAGS_n_step > 1) return UpdateActorCritic(SampleTransitionsFromMemory(minibatch_));
+  if (dp_ || FLAGS_pipelined_stats || !FLAGS_chained_updates || FLAGS_n_step > 1 || FLAGS_target_noise_sigma > 0.0) return UpdateActorCritic(SampleTransitionsFromMemory(minibatch_));
   // The driver calls this in bursts (src/dqn_main.cpp:359-361), each call drawing its indices from random_engine (:501-509).  What the
   // NEXT call will draw is known now — unless something else draws from the engine or the memory changes in between: take it from a
   // COPY of the engine and hand it to the library as a prediction (dqnhip_update_chained: the next update's gather and first layers

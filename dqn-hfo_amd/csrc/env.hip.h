@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "update_bodies.hip.h"     // philox_u32; Ring, DevState (learner_args.hip.h)
+#include "noise_bodies.hip.h"      // exploration noise: the normal draw, the OU step, apply-and-clamp
 
 namespace dqnhip {
 
@@ -53,6 +54,28 @@ template <bool F16> struct EnvArgs;
 template <> struct EnvArgs<false> { EnvDev e; };
 template <> struct EnvArgs<true> { EnvDev e; Env16 x; };
 static_assert(sizeof(EnvArgs<false>) == sizeof(EnvDev), "the fp32 step's kernel argument is EnvDev");
+
+// Exploration noise (dqnhip_env_set_noise): what the NOISE instantiations of k_env_step / k_env_act / k_env_observe take as one
+// further kernel argument.  The instantiations without it take the arguments they always took, and their code is what it was.
+struct EnvNoise {
+  NoiseCfg cfg;
+  float* ou;                       // [N][16] the workers' Ornstein-Uhlenbeck states: zero at creation and after every episode end
+  float* z_last;                   // [N][16] the normal draws of the last step
+  float* chosen;                   // [N][16] the row the last step chose (noisy greedy row, or the random row)
+};
+__device__ __forceinline__ const EnvNoise* env_noise_of() { return nullptr; }
+__device__ __forceinline__ const EnvNoise* env_noise_of(const EnvNoise& n) { return &n; }
+
+// One column of a worker's step (lane j < kNO of its block): the draw keyed by (noise seed, the worker's draw counter as read at the
+// step's start, w 32 + 2 j), the OU step — on every step, whether or not epsilon chose the random row — and the greedy value with the
+// state on it.  Ten Box-Muller evaluations side by side per worker.  Returns the noisy greedy value; x_out is the advanced state.
+__device__ __forceinline__ float env_noise_column(const EnvNoise& n, unsigned long long g, int w, int j, float v, float& x_out) {
+  const float z = noise_normal(n.cfg.seed, g, noise_lane0(w, j));
+  const float x = noise_ou_step(n.ou[(size_t)w * kAP + j], n.cfg.theta, noise_sigma(n.cfg, j), z);
+  n.z_last[(size_t)w * kAP + j] = z;
+  x_out = x;
+  return noise_apply(v, j, x, n.cfg.clamp);
+}
 
 __device__ __forceinline__ float env_u01(unsigned long long seed, unsigned long long g, int w, int k) {
   return (float)(philox_u32(seed, g, (uint32_t)(w * 256 + k)) >> 8) * (1.0f / 16777216.0f);
@@ -156,8 +179,11 @@ __global__ void k_env_init(const EnvArgs<F16> a) {
 // each pull all of W0 (512 KB) through one CU's load path, where the separate launch spreads it over 256.)
 // F16 (fp16 acting): the fused heads read the fp16 tower-top row, and the actor's next input row also goes, rounded to fp16, into
 // the fp16 panel beside the fp32 `cur` row (which the episode rows and the reward keep reading): a step has no pack launch.
-template <bool F16>
-__global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a) {
+// NOISE (exploration noise): NZ is one EnvNoise; lanes tid < kNO draw, advance the worker's OU state and put it on the greedy value
+// where they form v.  The noisy row is what goes to ep_a and into GetAction; the greedy row stays in out16.
+template <bool F16, bool NOISE = false, typename... NZ>
+__global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a, const NZ... nz) {
+  static_assert(sizeof...(NZ) == (NOISE ? 1 : 0), "the NOISE instantiation takes one EnvNoise");
   const EnvDev& e = a.e;
   bool fused_heads = e.head_x != nullptr;
   if constexpr (F16) fused_heads = a.x.head_x16 != nullptr;
@@ -215,6 +241,14 @@ __global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a) {
       else v = e.out16[(size_t)w * kAP + tid];       // written by the separate head launch
     }
     if (fused_heads) e.out16[(size_t)w * kAP + tid] = v;
+    if constexpr (NOISE) {
+      if (tid < kNO) {
+        const EnvNoise& n = *env_noise_of(nz...);
+        float x;
+        v = env_noise_column(n, g, w, tid, v, x);
+        n.ou[(size_t)w * kAP + tid] = status != 0 ? 0.0f : x;       // the episode ends on this step: zero after use
+      }
+    }
     if (tid < kNO && rnd) {                          // GetRandomActorOutput (src/dqn.cpp:664-682)
       const float u = env_u01(e.seed, g, w, 1 + tid);
       if (tid < kNA) v = fmaf(2.0f, u, -1.0f);
@@ -224,6 +258,7 @@ __global__ __launch_bounds__(256) void k_env_step(const EnvArgs<F16> a) {
     }
     s_ao[tid] = v;
     e.ep_a[((size_t)w * e.T + len) * kAP + tid] = v;
+    if constexpr (NOISE) env_noise_of(nz...)->chosen[(size_t)w * kAP + tid] = v;
   }
   // the actor's next input row: the next state, or — the episode is over — the first state of the new one
   // (src/dqn_main.cpp:97-105; the finished episode's transitions are labelled and added by k_env_flush, which
@@ -314,8 +349,9 @@ __global__ void k_env_ext_init(const EnvArgs<F16> a, const EnvExt x) {
 }
 
 // SelectAction + GetAction of every worker (src/dqn.cpp:684-711, 196-208): block = one worker, 4 waves, as k_env_step
-template <bool F16>
-__global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const EnvExt x) {
+template <bool F16, bool NOISE = false, typename... NZ>
+__global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const EnvExt x, const NZ... nz) {
+  static_assert(sizeof...(NZ) == (NOISE ? 1 : 0), "the NOISE instantiation takes one EnvNoise");
   const EnvDev& e = a.e;
   bool fused_heads = e.head_x != nullptr;
   if constexpr (F16) fused_heads = a.x.head_x16 != nullptr;
@@ -358,6 +394,14 @@ __global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const Env
       else v = e.out16[(size_t)w * kAP + tid];       // written by the separate head launch
     }
     if (fused_heads) e.out16[(size_t)w * kAP + tid] = v;
+    if constexpr (NOISE) {
+      if (tid < kNO) {
+        const EnvNoise& n = *env_noise_of(nz...);
+        float xs;
+        v = env_noise_column(n, g, w, tid, v, xs);
+        n.ou[(size_t)w * kAP + tid] = xs;            // (k_env_observe zeroes it where the step ends the episode)
+      }
+    }
     if (tid < kNO && rnd) {                          // GetRandomActorOutput (src/dqn.cpp:664-682)
       const float u = env_u01(e.seed, g, w, 1 + tid);
       if (tid < kNA) v = fmaf(2.0f, u, -1.0f);
@@ -366,6 +410,7 @@ __global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const Env
       else v = fmaf(360.0f, u, -180.0f);
     }
     s_ao[tid] = v;
+    if constexpr (NOISE) env_noise_of(nz...)->chosen[(size_t)w * kAP + tid] = v;
     if (x.record) e.ep_a[((size_t)w * e.T + len) * kAP + tid] = v;
     if (x.out_ao != nullptr && tid < kNO) x.out_ao[(size_t)w * kNO + tid] = v;
   }
@@ -390,8 +435,10 @@ __global__ __launch_bounds__(256) void k_env_act(const EnvArgs<F16> a, const Env
 // row and totals, and at an episode's end its record and the next episode's HFOGameState.  next[w] is the row the worker shows the
 // actor next: the successor state, or — the status is terminal — the first state of the worker's next episode (a terminal
 // transition has no next state, src/dqn_main.cpp:138-140, and :164-168 zeroes the deltas the row would feed).
-template <bool F16>
-__global__ __launch_bounds__(256) void k_env_observe(const EnvArgs<F16> a, const EnvExt x) {
+// NOISE: a terminal status (max_steps included) zeroes the worker's OU state, which k_env_act has used and advanced.
+template <bool F16, bool NOISE = false, typename... NZ>
+__global__ __launch_bounds__(256) void k_env_observe(const EnvArgs<F16> a, const EnvExt x, const NZ... nz) {
+  static_assert(sizeof...(NZ) == (NOISE ? 1 : 0), "the NOISE instantiation takes one EnvNoise");
   const EnvDev& e = a.e;
   extern __shared__ float s_next[];                  // [SP]
   const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -410,6 +457,9 @@ __global__ __launch_bounds__(256) void k_env_observe(const EnvArgs<F16> a, const
     const float v = f < e.S ? row[f] : 0.0f;         // the pad columns of the actor's input panel stay zero
     s_next[f] = v; cur[f] = v;
     if constexpr (F16) { if (f < a.x.ldx16) a.x.x16[(size_t)w * a.x.ldx16 + f] = (_Float16)v; }
+  }
+  if constexpr (NOISE) {
+    if (status != 0 && tid < kNO) env_noise_of(nz...)->ou[(size_t)w * kAP + tid] = 0.0f;
   }
   __syncthreads();
   if (wave == 0) {

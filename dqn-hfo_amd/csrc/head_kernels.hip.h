@@ -4,6 +4,7 @@
 #pragma once
 #include "gemm_direct.hip.h"
 #include "update_bodies.hip.h"
+#include "noise_bodies.hip.h"      // k_target_smooth: the normal draw, the clipped term, apply-and-clamp
 
 namespace dqnhip {
 
@@ -854,6 +855,35 @@ __global__ __launch_bounds__(256) void k_head_wred(HeadBwdBigArgs b, int chunks)
   float ssq = v * v;
   ssq = wave_sum64(ssq);
   if (lane == 0 && a.partial != nullptr) a.partial[j * gridDim.x + blockIdx.x] = ssq + s_bias;
+}
+
+// ---- target policy smoothing (dqnhip_target_noise_enable) ----------------------------------------------------------------------
+// One launch between the actors' head launch and the critics' first layers: a~ = clamp(mu'(s') + range clip(sigma z, -clip, clip)) over
+// the mu'(s') columns the head left in aout_t16 (which keep the clean values), written into the critic-target's action columns of Xc_nx
+// and, with the z used, into the debug rows.  z is keyed by (noise seed, c, row 32 + 2 j) with c = DevState::update_counter as it
+// stands when the launch runs: every earlier update's tick has advanced it, this update's has not, so c is the counter gather_block
+// samples this update with (update_counter, or gbase_counter + ahead inside a multi-update graph).  Thread = one (row, padded column).
+struct TargetSmoothArgs {
+  NoiseCfg cfg;
+  const DevState* st;
+  const float* mu16;               // [rows][kAP] the target actor's head outputs
+  float* xc; int ldxc, xc_col;     // the critic-target's input panel: a~ goes to columns [xc_col, xc_col + kNO)
+  float* smoothed16; float* z16;   // [rows][kAP] a~ and the z used
+  unsigned long long* counter;     // [1] c
+  int rows;
+};
+static __global__ __launch_bounds__(256) void k_target_smooth(const TargetSmoothArgs a) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int r = gid >> 4, j = gid & 15;
+  const unsigned long long c = a.st->update_counter;
+  if (gid == 0) *a.counter = c;
+  if (r >= a.rows || j >= kNO) return;
+  const float z = noise_normal(a.cfg.seed, c, noise_lane0(r, j));
+  const float t = noise_clipped(noise_sigma(a.cfg, j), z, a.cfg.clip);
+  const float v = noise_apply(a.mu16[(size_t)r * kAP + j], j, t, a.cfg.clamp);
+  a.xc[(size_t)r * a.ldxc + a.xc_col + j] = v;
+  a.smoothed16[(size_t)r * kAP + j] = v;
+  a.z16[(size_t)r * kAP + j] = z;
 }
 
 }  // namespace dqnhip

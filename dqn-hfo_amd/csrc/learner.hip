@@ -818,6 +818,12 @@ int run_phase(H* h, int phase, const int* idx_dev) {
       RC(tower_forward(h, st, ap, 2, B, merged_l0 ? 1 : 0));
       RC((head_forward<kNO, HEAD_ACTOR>(h, st, hAT, &hA)));     // both actors' heads in one launch
     }
+    if (P.smooth) {
+      // target policy smoothing: a~ over the mu'(s') columns the head left in Xc_nx (plan_of: the critics' first layers are behind this)
+      const TargetNoiseHost* tn = h->tnoise;
+      const TargetSmoothArgs sa{tn->cfg, h->st, h->aout_t16, h->Xc_nx, lc.kp[0], h->S, tn->smoothed16, tn->z16, tn->counter, B};
+      HIPCHK(launch(st, k_target_smooth, dim3((B * kAP + 255) / 256), dim3(256), 0, sa));
+    }
     RC(tower_forward(h, st, cp, 2, B, merged_l0 ? 1 : 0));
     HeadTrainArgs qt_args = q_train_args(h);
     qt_args.Xt = h->act[2][L]; qt_args.X = h->act[3][L];

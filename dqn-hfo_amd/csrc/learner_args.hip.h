@@ -5,7 +5,7 @@
 //               one function for the host and the device), gemm_plan.hip.h (the fp32 family's
 //               launch forms: table, preconditions, choosers), hgemm_plan.hip.h (the fp16 family's problem description and tile choice)
 //   bodies      gemm_bodies.hip.h, update_bodies.hip.h, solver_bodies.hip.h (the optimiser pass of the solvers other than Adam):
-//               __device__ functions only
+//               __device__ functions only; noise_bodies.hip.h (exploration noise: __host__ __device__, one text for both sides)
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
 //               solver_kernels.hip.h (the optimiser launches of the solvers other than Adam; learner.hip),
 //               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), diag_kernels.hip.h (update diagnostics;

@@ -286,6 +286,7 @@ int dqnhip_destroy(dqnhip_handle h) {
   drop_graphs(h);
   per_free(h);
   nstep_free(h);
+  smooth_free(h);
   diag_free(h);
   sweep_free(h);
   for (int i = 0; i < 2; ++i) {

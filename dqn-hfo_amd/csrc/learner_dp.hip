@@ -243,6 +243,7 @@ int dqnhip_dp_init(dqnhip_handle h, const void* id, size_t bytes, int32_t flags)
   RC(sched_refuse(h, "dqnhip_dp_init"));
   RC(per_refuse(h, "dqnhip_dp_init"));
   RC(nstep_refuse(h, "dqnhip_dp_init"));
+  RC(smooth_refuse(h, "dqnhip_dp_init"));
   if (h->w_owner || h->sharers) return fail("dp_init: learners that share layers cannot join a data-parallel group");
   if (h->ls_dynamic) return fail("dp_init: loss_scale_mode = dynamic is a single-learner mode (the data-parallel form has never run: DESIGN.md 9)");
   HIPCHK(hipSetDevice(h->cfg.device));

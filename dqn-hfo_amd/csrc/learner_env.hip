@@ -18,6 +18,7 @@ struct dqnhip_env {
   int* commit_ticket = nullptr;
   hipGraphExec_t graph[2] = {nullptr, nullptr};   // one batched step / kEnvUnroll steps, captured on first use
   bool graph_failed = false;
+  int graph_nodes[2] = {0, 0};                    // launches in each captured graph (dqnhip_env_debug_read "graph_nodes")
   // inside a sequence of batched steps the episode flush of step t (LabelTransitions + AddTransitions of the
   // finished episodes) rides as extra workgroups of step t+1's first-layer launch: k_env_step resets the worker
   // itself, so nothing before the next k_env_step depends on the flush
@@ -43,6 +44,10 @@ struct dqnhip_env {
   std::vector<unsigned long long> rec_read;
   std::deque<dqnhip_env_episode> pending;
   long long dropped = 0;
+  // exploration noise (dqnhip_env_set_noise): off — the handle launches the kernels it always launched — or on: the NOISE
+  // instantiations with nz as their further argument.  nz's buffers are allocated when noise is first enabled.
+  bool noise = false;
+  EnvNoise nz{};
 };
 constexpr int kEnvUnroll = 16;
 static_assert(sizeof(EnvEpisode) == sizeof(dqnhip_env_episode) && offsetof(EnvEpisode, step_index) == offsetof(dqnhip_env_episode, step_index) &&
@@ -233,7 +238,8 @@ static int env_one_step(dqnhip_env* e, bool more_follow) {
     a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.b = wat(h, DQNHIP_ACTOR, la.hb_off); a.out16 = d.out16;
     RC((head_forward<kNO, HEAD_ACTOR>(h, st, a)));
   }
-  HIPCHK(launch(st, k_env_step<false>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<false>{d}));
+  if (e->noise) HIPCHK(launch(st, k_env_step<false, true, EnvNoise>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<false>{d}, e->nz));
+  else HIPCHK(launch(st, k_env_step<false>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<false>{d}));
   if (more_follow && fused && l0_direct && !h->timing) { e->flush_deferred = true; return 0; }
   HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring,
                      (const DevState*)RO(h)->st, h->cfg.gamma));
@@ -265,7 +271,8 @@ static int env_one_step16(dqnhip_env* e) {
     a.W = wat(h, DQNHIP_ACTOR, la.hw_off); a.b = wat(h, DQNHIP_ACTOR, la.hb_off); a.out16 = d.out16;
     RC((head_forward<kNO, HEAD_ACTOR>(h, st, a)));
   }
-  HIPCHK(launch(st, k_env_step<true>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, fused)}));
+  if (e->noise) HIPCHK(launch(st, k_env_step<true, true, EnvNoise>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, fused)}, e->nz));
+  else HIPCHK(launch(st, k_env_step<true>, dim3(d.N), dim3(256), 2 * d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, fused)}));
   HIPCHK(launch(st, k_env_flush, dim3(d.N), dim3(256), d.T * sizeof(float), d, RO(h)->ring,
                      (const DevState*)RO(h)->st, h->cfg.gamma));
   if (d.commit_ticket == nullptr) {
@@ -301,6 +308,8 @@ static int env_capture(dqnhip_env* e, int which) {
   hipError_t err = hipStreamEndCapture(h->stream, &graph);
   if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
   if (err != hipSuccess) return fail("hipStreamEndCapture (env): %s", hipGetErrorString(err));
+  size_t nodes = 0;
+  if (hipGraphGetNodes(graph, nullptr, &nodes) == hipSuccess) e->graph_nodes[which] = (int)nodes;
   err = hipGraphInstantiate(&e->graph[which], graph, nullptr, nullptr, 0);
   hipGraphDestroy(graph);
   if (err != hipSuccess) return fail("hipGraphInstantiate (env): %s", hipGetErrorString(err));
@@ -383,7 +392,10 @@ int dqnhip_env_act_device(dqnhip_env_handle e, float epsilon, int32_t* action_de
   if (!fused) RC((head_forward<kNO, HEAD_ACTOR>(h, st, ha)));
   EnvExt x = e->x;
   x.epsilon = epsilon; x.out_action = action_dev; x.out_args = args_dev; x.out_ao = actor_out_dev;
-  if (e->f16) HIPCHK(launch(st, k_env_act<true>, dim3(d.N), dim3(256), 0, EnvArgs<true>{d, env16_of(e, fused)}, x));
+  if (e->noise) {
+    if (e->f16) HIPCHK(launch(st, k_env_act<true, true, EnvNoise>, dim3(d.N), dim3(256), 0, EnvArgs<true>{d, env16_of(e, fused)}, x, e->nz));
+    else HIPCHK(launch(st, k_env_act<false, true, EnvNoise>, dim3(d.N), dim3(256), 0, EnvArgs<false>{d}, x, e->nz));
+  } else if (e->f16) HIPCHK(launch(st, k_env_act<true>, dim3(d.N), dim3(256), 0, EnvArgs<true>{d, env16_of(e, fused)}, x));
   else HIPCHK(launch(st, k_env_act<false>, dim3(d.N), dim3(256), 0, EnvArgs<false>{d}, x));
   e->acted = true;
   return 0;
@@ -414,7 +426,10 @@ int dqnhip_env_observe_device(dqnhip_env_handle e, const float* next_states_dev,
   EnvExt x = e->x;
   x.next = next_states_dev; x.status = status_dev; x.pob = player_on_ball_dev; x.step_index = e->observes + 1;
   auto observe = [&]() -> int {
-    if (e->f16) HIPCHK(launch(st, k_env_observe<true>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}, x));
+    if (e->noise) {
+      if (e->f16) HIPCHK(launch(st, k_env_observe<true, true, EnvNoise>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}, x, e->nz));
+      else HIPCHK(launch(st, k_env_observe<false, true, EnvNoise>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<false>{d}, x, e->nz));
+    } else if (e->f16) HIPCHK(launch(st, k_env_observe<true>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<true>{d, env16_of(e, false)}, x));
     else HIPCHK(launch(st, k_env_observe<false>, dim3(d.N), dim3(256), d.SP * sizeof(float), EnvArgs<false>{d}, x));
     e->observes += 1; e->acted = false;
     return 0;
@@ -446,6 +461,37 @@ int dqnhip_env_observe(dqnhip_env_handle e, const float* next_states, const int3
   return dqnhip_env_observe_device(e, e->d_next, e->d_status, e->d_pob);
 }
 
+// Exploration noise on or off (cfg NULL).  The captured steps hold the kernels of the other setting and its config as kernel
+// arguments: they are dropped, as a change of the acting precision drops them.  Every call zeroes the workers' OU states.
+int dqnhip_env_set_noise(dqnhip_env_handle e, const dqnhip_noise_config* cfg) {
+  if (!e) return fail("null env");
+  dqnhip_learner* h = e->h;
+  NoiseCfg c{};
+  if (cfg) {
+    if (cfg->struct_size != (int32_t)sizeof(dqnhip_noise_config)) return fail("dqnhip_noise_config.struct_size mismatch");
+    c.sigma_logits = cfg->sigma_logits; c.sigma_params = cfg->sigma_params; c.theta = cfg->theta; c.clip = cfg->clip;
+    c.clamp = cfg->clamp ? 1 : 0; c.seed = cfg->seed;
+    char msg[256];
+    if (noise_config_check(c, msg, sizeof msg)) return fail("dqnhip_env_set_noise: %s", msg);
+  }
+  if (e->acted) return fail("dqnhip_env_set_noise: an act is waiting for its observe");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 2; ++i) if (e->graph[i]) { HIPCHK(hipGraphExecDestroy(e->graph[i])); e->graph[i] = nullptr; }
+  e->graph_failed = false;
+  const size_t n = (size_t)e->d.N * kAP;
+  if (cfg && !e->nz.ou) { RC(env_alloc(e, &e->nz.ou, n)); RC(env_alloc(e, &e->nz.z_last, n)); RC(env_alloc(e, &e->nz.chosen, n)); }
+  if (e->nz.ou) {
+    HIPCHK(hipMemsetAsync(e->nz.ou, 0, n * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(e->nz.z_last, 0, n * sizeof(float), h->stream));
+    // "actor_out" before the first noisy step: the greedy rows, what a handle without noise reports
+    HIPCHK(hipMemcpyAsync(e->nz.chosen, e->d.out16, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  e->nz.cfg = c;
+  e->noise = cfg != nullptr;
+  return 0;
+}
 // the sticky status flag of an external handle (src/hfo_game.cpp:124-126 throws "Server Down!"); the stream is idle
 static int env_check_flag(dqnhip_env* e) {
   if (!e->external) return 0;
@@ -520,6 +566,12 @@ int dqnhip_env_debug_read(dqnhip_env_handle e, const char* name, float* host, si
     for (size_t i = 0; i < N; ++i) host[i] = (float)t[i];
     return 0;
   }
+  if (!strcmp(name, "graph_nodes")) {
+    // launches of the captured one-step graph and of the captured 16-step graph (0: not captured yet)
+    if (count < 2) return fail("buffer too small");
+    host[0] = (float)(e->graph[0] ? e->graph_nodes[0] : 0); host[1] = (float)(e->graph[1] ? e->graph_nodes[1] : 0);
+    return 0;
+  }
   if (!strcmp(name, "truncated")) {
     // episodes that reached max_steps while IN_GAME and were closed as OUT_OF_TIME (external handles; a synthetic one reports 0)
     if (count < 1) return fail("buffer too small");
@@ -542,12 +594,16 @@ int dqnhip_env_debug_read(dqnhip_env_handle e, const char* name, float* host, si
     HIPCHK(hipMemcpy(t.data(), e->d.cur, t.size() * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < N; ++i) memcpy(host + i * h->S, &t[i * e->d.SP], h->S * 4);
     return 0;
-  } else if (!strcmp(name, "actor_out")) {
-    // the ActorOutput chosen at the last step = last written row of the open episode, or (if the
-    // episode just ended) not available any more: report the greedy output instead
+  } else if (!strcmp(name, "actor_out") || !strcmp(name, "greedy_out") || !strcmp(name, "noise_state") || !strcmp(name, "noise_z")) {
+    // "actor_out" without noise: the ActorOutput chosen at the last step = last written row of the open episode, or (if the
+    // episode just ended) not available any more: report the greedy output instead.  With noise the NOISE kernels keep the chosen
+    // row (the noisy greedy row, or the random row) and "greedy_out" is the heads' own output.
     if (count < N * kNO) return fail("buffer too small");
+    const bool is_z = !strcmp(name, "noise_z"), is_state = !strcmp(name, "noise_state");
+    if ((is_z || is_state) && !e->noise) return fail("env debug buffer '%s': exploration noise is not enabled on this handle (dqnhip_env_set_noise)", name);
+    const float* rows = is_z ? e->nz.z_last : is_state ? e->nz.ou : (!strcmp(name, "actor_out") && e->noise) ? e->nz.chosen : e->d.out16;
     std::vector<float> t(N * kAP);
-    HIPCHK(hipMemcpy(t.data(), e->d.out16, t.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t.data(), rows, t.size() * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < N; ++i) memcpy(host + i * kNO, &t[i * kAP], kNO * 4);
     return 0;
   } else return fail("unknown env debug buffer '%s'", name);

@@ -50,6 +50,7 @@
 #include "../../include/dqnhip_env.h"
 #include "gemm_common.hip.h"      // LaunchOn, launch, TailsArgs, the flags
 #include "learner_args.hip.h"
+#include "noise_bodies.hip.h"     // NoiseCfg and the host side of the noise body (no kernel)
 #include "gemm_plan.hip.h"        // the fp32 forms and their choosers (bwd_layer_is_pair)
 #include "hgemm_plan.hip.h"
 #include "state_image.h"        // plain structures of the asynchronous state save
@@ -143,6 +144,12 @@ struct NstepHost {
   int n = 1;                            // 1 .. kNstepMax
   double* disc = nullptr; int* steps = nullptr;     // [B]: gamma^m and m of the last update's rows (the gathered reward buffer holds R)
   unsigned long long* viol = nullptr;   // dqnhip_nstep_validate's two result words: {violations, first_bad (an int in the second word)}
+};
+// target policy smoothing (dqnhip_target_noise_enable; k_target_smooth, head_kernels.hip.h)
+struct TargetNoiseHost {
+  dqnhip::NoiseCfg cfg{};
+  float* smoothed16 = nullptr; float* z16 = nullptr;   // [B][kAP]: a~ and the z of the last update
+  unsigned long long* counter = nullptr;               // [1] the Philox counter the last update's noise was keyed by
 };
 struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
 struct SweepHost;                       // replay sweep (learner_io.hip; the kernels: sweep_kernels.hip.h)
@@ -298,6 +305,7 @@ struct dqnhip_learner {
   int ix_prev_flags = 0;                // the sticky device flags as the last harvested update left them (a raise = a bit not in here)
   long long per_env_slack = 0;          // transitions the recording env front-ends of this ring may hold back and append later (workers x max_steps each)
   PerHost* per = nullptr;               // prioritized replay (dqnhip_per_enable); null: uniform sampling, nothing below runs
+  TargetNoiseHost* tnoise = nullptr;    // target policy smoothing (dqnhip_target_noise_enable); null: the clean mu'(s'), nothing of it runs
   NstepHost* nstep = nullptr;           // n-step returns (dqnhip_nstep_enable); null: the 1-step target, nothing of it runs
   DiagHost* diag = nullptr;             // update diagnostics (dqnhip_diag_collect): its work table and scratch, allocated by the first collection
   // replay sweep (dqnhip_evaluate_memory / dqnhip_per_refresh): its scratch, allocated by the first sweep, and one captured chunk of
@@ -402,6 +410,7 @@ struct UpdatePlan {
   bool early_l0;                    // multi-update graphs: next gather in the critic's optimiser launch, next first layers in the actor's
   bool tails_ride;                  // data parallel: the [loss, q, flag] tails block rides in each net's last backward launch (no k_tails launches)
   bool prioritized;                 // prioritized replay: k_per_sample / k_per_fill before, k_head_q_train_w inside, k_per_update behind every update
+  bool smooth;                      // target policy smoothing: k_target_smooth behind the actors' heads, the critics' first layers behind it (never merged)
   bool nstep;                       // n-step returns: k_gather_n first, k_head_q_train_n<prioritized> in the head launch's place; the stand-alone sequence per update
 };
 UpdatePlan plan_of(const H* h);
@@ -473,6 +482,8 @@ int per_refuse(const H* h, const char* what);            // fails, naming priori
 // n-step returns (learner_io.hip)
 int nstep_refuse(const H* h, const char* what);          // fails, naming n-step returns, if they are enabled on h
 void nstep_free(H* h);
+int smooth_refuse(const H* h, const char* what);         // fails, naming target smoothing, if it is enabled on h
+void smooth_free(H* h);
 // does every update of this learner run the stand-alone sequence, also inside a multi-update graph?  (no rider serves a successor)
 inline bool standalone_updates(const H* h) { return h->per != nullptr || h->nstep != nullptr; }
 void diag_free(H* h);                                    // dqnhip_diag_collect's scratch

@@ -705,6 +705,16 @@ namespace dqnhip_host {
 int nstep_refuse(const H* h, const char* what) {
   return h->nstep ? fail("%s: not available on a learner with n-step returns (dqnhip_nstep_enable) in this version", what) : 0;
 }
+int smooth_refuse(const H* h, const char* what) {
+  return h->tnoise ? fail("%s: not available on a learner with target smoothing (dqnhip_target_noise_enable) in this version", what) : 0;
+}
+void smooth_free(H* h) {
+  TargetNoiseHost* p = h->tnoise;
+  if (!p) return;
+  hipFree(p->smoothed16); hipFree(p->z16); hipFree(p->counter);
+  delete p;
+  h->tnoise = nullptr;
+}
 void nstep_free(H* h) {
   NstepHost* p = h->nstep;
   if (!p) return;
@@ -734,6 +744,45 @@ int dqnhip_nstep_enable(dqnhip_handle h, int32_t n) {
   h->nstep->n = n;
   h->epoch += 1;
   drop_graphs(h);
+  return 0;
+}
+
+// ---- target policy smoothing (include/dqnhip.h; k_target_smooth: head_kernels.hip.h, launched by learner.hip) ----
+int dqnhip_target_noise_enable(dqnhip_handle h, const dqnhip_noise_config* cfg) {
+  if (!h) return fail("dqnhip_target_noise_enable: null handle (target smoothing is enabled on an existing learner)");
+  if (!cfg) { h->epoch += 1; HIPCHK(hipSetDevice(h->cfg.device)); HIPCHK(hipStreamSynchronize(h->stream)); smooth_free(h); drop_graphs(h); return 0; }
+  if (cfg->struct_size != (int32_t)sizeof(dqnhip_noise_config)) return fail("dqnhip_target_noise_enable: dqnhip_noise_config.struct_size mismatch");
+  NoiseCfg c{};
+  c.sigma_logits = cfg->sigma_logits; c.sigma_params = cfg->sigma_params; c.theta = cfg->theta; c.clip = cfg->clip;
+  c.clamp = cfg->clamp ? 1 : 0; c.seed = cfg->seed;
+  char msg[256];
+  if (noise_config_check(c, msg, sizeof msg)) return fail("dqnhip_target_noise_enable: %s", msg);
+  if (c.theta != 1.0f) return fail("dqnhip_target_noise_enable: target smoothing draws white noise: theta must be 1 (got %g)", (double)c.theta);
+  if (h->fp16) return fail("dqnhip_target_noise_enable: target smoothing on a learner with precision = DQNHIP_FP16 is not supported in this version");
+  if (h->cfg.dp_world > 1 || h->comm || h->dp_half || h->dp_shard) return fail("dqnhip_target_noise_enable: target smoothing on a data-parallel learner (dp_world > 1, dqnhip_dp_init) is not supported in this version");
+  if (h->w_owner || h->ring_owner || h->shared_fl[0] || h->shared_fl[1] || h->sharers) return fail("dqnhip_target_noise_enable: target smoothing on a learner that shares parameters or its replay memory is not supported in this version");
+  if (h->next_phase != 0) return fail("dqnhip_target_noise_enable: a phased update is in progress (next phase %d)", h->next_phase);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h->tnoise) {
+    TargetNoiseHost* p = new TargetNoiseHost();
+    h->tnoise = p;              // (from here on smooth_free releases whatever was allocated)
+    const size_t n = (size_t)h->B * kAP * sizeof(float);
+    auto alloc = [&](void** d, size_t bytes) -> int { HIPCHK(hipMalloc(d, bytes)); HIPCHK(hipMemset(*d, 0, bytes)); return 0; };
+    if (alloc((void**)&p->smoothed16, n) || alloc((void**)&p->z16, n) || alloc((void**)&p->counter, sizeof(unsigned long long))) { smooth_free(h); return 1; }
+  }
+  h->tnoise->cfg = c;
+  h->epoch += 1;
+  drop_graphs(h);
+  return 0;
+}
+int dqnhip_target_noise_get(dqnhip_handle h, int32_t* enabled, dqnhip_noise_config* cfg) {
+  if (!h || !enabled) return fail("dqnhip_target_noise_get: null argument");
+  *enabled = h->tnoise ? 1 : 0;
+  if (cfg && h->tnoise) {
+    const NoiseCfg& c = h->tnoise->cfg;
+    *cfg = dqnhip_noise_config{(int32_t)sizeof(dqnhip_noise_config), c.clamp, c.sigma_logits, c.sigma_params, c.theta, c.clip, c.seed};
+  }
   return 0;
 }
 
@@ -896,6 +945,7 @@ static int shared_prefix(const NetLayout& l, int n, size_t* fl) {
 
 int dqnhip_share_parameters(dqnhip_handle owner, dqnhip_handle other, int32_t num_actor_layers, int32_t num_critic_layers) {
   if (!owner || !other || owner == other) return fail("ShareParameters needs two distinct learners");
+  RC(smooth_refuse(owner, "dqnhip_share_parameters (owner)")); RC(smooth_refuse(other, "dqnhip_share_parameters (other)"));
   owner->epoch += 1; other->epoch += 1;
   if (owner->cfg.device != other->cfg.device) return fail("ShareParameters: both learners must live on the same device");
   if (!same_nets(owner, other)) return fail("ShareParameters: net shapes differ");
@@ -920,6 +970,7 @@ int dqnhip_share_replay_memory(dqnhip_handle owner, dqnhip_handle other) {
   if (!owner || !other || owner == other) return fail("ShareReplayMemory needs two distinct learners");
   RC(per_refuse(owner, "dqnhip_share_replay_memory (owner)")); RC(per_refuse(RO(owner), "dqnhip_share_replay_memory (owner)"));
   RC(per_refuse(other, "dqnhip_share_replay_memory (other)"));
+  RC(smooth_refuse(owner, "dqnhip_share_replay_memory (owner)")); RC(smooth_refuse(other, "dqnhip_share_replay_memory (other)"));
   owner->epoch += 1; other->epoch += 1; RO(owner)->epoch += 1;
   if (owner->cfg.device != other->cfg.device) return fail("ShareReplayMemory: both learners must live on the same device");
   if (owner->S != other->S) return fail("ShareReplayMemory: state sizes differ");
@@ -1032,6 +1083,19 @@ int dqnhip_debug_read(dqnhip_handle h, const char* name, float* host, size_t cou
   }
   else if (!strcmp(name, "dq")) src = h->dq;
   else if (!strcmp(name, "actor_target_out")) { src = h->aout_t16; pad16 = true; n = B * kNO; }
+  else if (!strcmp(name, "actor_target_smoothed") || !strcmp(name, "target_noise_z") || !strcmp(name, "target_noise_counter")) {
+    if (!h->tnoise) return fail("debug buffer '%s': target smoothing is not enabled on this learner (dqnhip_target_noise_enable)", name);
+    if (!strcmp(name, "target_noise_counter")) {
+      // the 64-bit counter through a float interface, exactly: [c mod 2^24, c / 2^24] (a counter below 2^48)
+      if (count < 2) return fail("buffer too small for '%s'", name);
+      unsigned long long c = 0;
+      HIPCHK(hipStreamSynchronize(h->stream));
+      HIPCHK(hipMemcpy(&c, h->tnoise->counter, sizeof c, hipMemcpyDeviceToHost));
+      host[0] = (float)(c & 0xFFFFFFull); host[1] = (float)(c >> 24);
+      return 0;
+    }
+    src = !strcmp(name, "target_noise_z") ? h->tnoise->z16 : h->tnoise->smoothed16; pad16 = true; n = B * kNO;
+  }
   else if (!strcmp(name, "dz_c") || !strcmp(name, "dz_a")) {
     // the tower-top gradient the head-backward forms leave for the tower, dense [B][H] (the pitch the head kernels write with);
     // fp16 learner: the scaled fp16 panel, widened as stored

@@ -208,6 +208,7 @@ UpdatePlan plan_of(const H* h) {
   p.fused_seed = !(tf & DQNHIP_TUNE_SEPARATE_HEAD_SEED);
   p.prioritized = h->per != nullptr;
   p.nstep = h->nstep != nullptr;
+  p.smooth = h->tnoise != nullptr;
   if (h->fp16) {
     // fp16 learner: the head's dW / db are column-sum workgroups of the net's last backward launch (hgemm_group_db, HeadWsum)
     // when that launch exists; Step(1)'s k_head_q_train then also writes the scaled fp16 tower-top gradient — no head-backward launch
@@ -239,7 +240,9 @@ UpdatePlan plan_of(const H* h) {
   p.critic_l0 = !h->dp_shard && h->shared_fl[DQNHIP_CRITIC] == 0 && !(tf & DQNHIP_TUNE_SEPARATE_FIRST_LAYER) &&
                 (lc.kp[0] == 64 || lc.kp[0] == 128) && l0_can_ride(lc) && B % 16 == 0 && B <= 512 && L >= 2;
   // Step(1)'s four first layers in one launch, critic_target's action half in the target actor's head kernel (first_layers_launch)
-  p.first_layers_merged = h->Zs != nullptr && !(tf & DQNHIP_TUNE_SEPARATE_CRITIC_FIRST_LAYERS) && L >= 2 && B % 32 == 0 && B < 1024 && la.kp[0] < 512 &&
+  // (target smoothing: a~ must stand in Xc_nx before the critic-target's first layer reads it — the schedule of
+  // DQNHIP_TUNE_SEPARATE_CRITIC_FIRST_LAYERS: no action half inside the head kernel, and with it no early_l0)
+  p.first_layers_merged = !p.smooth && h->Zs != nullptr && !(tf & DQNHIP_TUNE_SEPARATE_CRITIC_FIRST_LAYERS) && L >= 2 && B % 32 == 0 && B < 1024 && la.kp[0] < 512 &&
                           lc.kp[0] < 512 && la.dims[1] % 64 == 0 && lc.dims[1] % 64 == 0 && lc.dims[1] <= 1024 && round_up(h->S, 64) <= lc.kp[0];
   // inside a multi-update graph: the next update's gather rides in the critic's optimiser launch and its four first layers in the
   // actor's (k_adam_soft_fwd1_gather / k_adam_soft_l0).  Needs every piece those riders stand on.
@@ -264,5 +267,34 @@ extern "C" {
 const char* dqnhip_last_error(void) { return g_err.c_str(); }
 // used by snapshot.cpp (same library, different translation unit) to report through the same channel
 int dqnhip_internal_set_error(const char* msg) { g_err = msg ? msg : ""; return 1; }
+
+// action noise: the literature's values in units of the column's range — not measured on this workload (include/dqnhip.h)
+int dqnhip_noise_default_config(dqnhip_noise_config* cfg, int32_t purpose) {
+  if (!cfg) return fail("null argument");
+  if (purpose != DQNHIP_NOISE_EXPLORE && purpose != DQNHIP_NOISE_TARGET) return fail("dqnhip_noise_default_config: unknown purpose %d", (int)purpose);
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = (int32_t)sizeof *cfg;
+  cfg->clamp = 1;
+  if (purpose == DQNHIP_NOISE_EXPLORE) { cfg->sigma_logits = 0.0f; cfg->sigma_params = 0.1f; cfg->theta = 0.15f; cfg->clip = 0.0f; cfg->seed = 0x6E6F697365ull; }
+  else { cfg->sigma_logits = 0.1f; cfg->sigma_params = 0.1f; cfg->theta = 1.0f; cfg->clip = 0.25f; cfg->seed = 0x736D6F6F7468ull; }
+  return 0;
+}
+
+int dqnhip_noise_explore_host(const dqnhip_noise_config* cfg, uint64_t counter, int32_t row, float* ou_state, float* actor_out) {
+  if (!cfg || !ou_state || !actor_out) return fail("null argument");
+  if (cfg->struct_size != (int32_t)sizeof(dqnhip_noise_config)) return fail("dqnhip_noise_config.struct_size mismatch");
+  if (row < 0) return fail("dqnhip_noise_explore_host: row must be >= 0");
+  NoiseCfg c{};
+  c.sigma_logits = cfg->sigma_logits; c.sigma_params = cfg->sigma_params; c.theta = cfg->theta; c.clip = cfg->clip;
+  c.clamp = cfg->clamp ? 1 : 0; c.seed = cfg->seed;
+  char msg[256];
+  if (noise_config_check(c, msg, sizeof msg)) return fail("dqnhip_noise_explore_host: %s", msg);
+  for (int j = 0; j < kNO; ++j) {
+    const float z = noise_normal(c.seed, counter, noise_lane0(row, j));
+    ou_state[j] = noise_ou_step(ou_state[j], c.theta, noise_sigma(c, j), z);
+    actor_out[j] = noise_apply(actor_out[j], j, ou_state[j], c.clamp);
+  }
+  return 0;
+}
 
 }  // extern "C"

@@ -256,7 +256,8 @@ static int update_plan_fill(H* h, dqnhip_update_plan* out) {
                (p.fused_seed ? DQNHIP_PLAN_HEAD_SEED_FUSED : 0) | (p.fuse_head ? DQNHIP_PLAN_DQDA_HEAD_BWD : 0) |
                (p.critic_l0 ? DQNHIP_PLAN_CRITIC_L0_RIDES : 0) | (p.first_layers_merged ? DQNHIP_PLAN_FIRST_LAYERS_MERGED : 0) |
                (p.early_l0 ? DQNHIP_PLAN_EARLY_GATHER_L0 : 0) | (p.tails_ride ? DQNHIP_PLAN_DP_TAILS_RIDE : 0) |
-               (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0) | (p.nstep ? DQNHIP_PLAN_NSTEP : 0);
+               (p.prioritized ? DQNHIP_PLAN_PRIORITIZED : 0) | (p.nstep ? DQNHIP_PLAN_NSTEP : 0) |
+               (p.smooth ? DQNHIP_PLAN_TARGET_SMOOTHING : 0);
   out->updates_per_graph = kMultiU; out->solver_type = h->cfg.solver_type;
   // per net and update: one all-reduce (per-layer buckets: one per tower layer + the head slice; bf16 exchange: the tails travel in a
   // second call beside the actor's; sharded optimiser: reduce-scatter + the 4-float all-reduce + 2 (fp16 learner: 4) all-gathers)
@@ -339,6 +340,7 @@ int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host, int32_t n)
   if (n < 0) return fail("dqnhip_update_indexed_n: n must be >= 0");
   RC(per_refuse(h, "dqnhip_update_indexed_n"));
   RC(nstep_refuse(h, "dqnhip_update_indexed_n"));
+  RC(smooth_refuse(h, "dqnhip_update_indexed_n"));
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_indexed_n: a phased update is in progress (next phase %d)", h->next_phase);
@@ -408,6 +410,7 @@ int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host)
   if (!h) return fail("null handle");
   RC(per_refuse(h, "dqnhip_update_phase"));
   RC(nstep_refuse(h, "dqnhip_update_phase"));
+  RC(smooth_refuse(h, "dqnhip_update_phase"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   // (with DQNHIP_DP_HALF_GRADS the exchange — bf16 image, all-reduce, widening by the clip-norm pass — lives inside
@@ -536,6 +539,7 @@ int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_
   if (!idx_host) return fail("dqnhip_update_chained: explicit indices required (on-device sampling: dqnhip_update_async_n)");
   RC(per_refuse(h, "dqnhip_update_chained"));
   RC(nstep_refuse(h, "dqnhip_update_chained"));
+  RC(smooth_refuse(h, "dqnhip_update_chained"));
   HIPCHK(hipSetDevice(h->cfg.device));
   const UpdatePlan P = plan_of(h);
   const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && h->sharers == 0 && h->w_owner == nullptr;
@@ -584,6 +588,7 @@ int dqnhip_update_pipelined(dqnhip_handle h, const int32_t* idx_host, float* cri
   if (!h) return fail("null handle");
   RC(per_refuse(h, "dqnhip_update_pipelined"));
   RC(nstep_refuse(h, "dqnhip_update_pipelined"));
+  RC(smooth_refuse(h, "dqnhip_update_pipelined"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");

@@ -685,7 +685,7 @@ class DQN:
             out = np.zeros(2, np.float32)
             self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
             return out.astype(np.int64)
-        wide = name in ("actor_out", "dq_da", "actor_target_out", "dxc")
+        wide = name in ("actor_out", "dq_da", "actor_target_out", "dxc", "actor_target_smoothed", "target_noise_z")
         out = np.empty(B * (10 if wide else 1), np.float32)
         self._ck(self.lib.dqnhip_debug_read(self.h, name.encode(), _p(out), out.size))
         return out.reshape(B, 10) if wide else out
@@ -815,6 +815,33 @@ class DQN:
         (shorter at a terminal transition and at the memory's end).  n in 1 .. 64 (1: the 1-step learner's bits, on the n-step
         schedule); may be called again; there is no disable.  Typical n (3 - 5) is the literature's value, not measured here."""
         self._ck(self.lib.dqnhip_nstep_enable(self.h, int(n)))
+
+    def enable_target_smoothing(self, sigma_logits=None, sigma_params=None, clip=None, clamp=None, seed=None):
+        """Target policy smoothing (TD3; include/dqnhip.h): the critic-target sees clamp(mu'(s') + range clip(sigma z, -clip, clip)).
+        Sigmas and clip in units of each column's range; what is left None keeps the default (sigma 0.1, clip 0.25, clamp on: TD3's
+        values on a range of 2, not measured on this workload)."""
+        cfg = capi.NoiseConfig()
+        self._ck(self.lib.dqnhip_noise_default_config(C.byref(cfg), capi.NOISE_TARGET))
+        for k, v in (("sigma_logits", sigma_logits), ("sigma_params", sigma_params), ("clip", clip), ("seed", seed)):
+            if v is not None:
+                setattr(cfg, k, v)
+        if clamp is not None:
+            cfg.clamp = 1 if clamp else 0
+        self._ck(self.lib.dqnhip_target_noise_enable(self.h, C.byref(cfg)))
+
+    def target_smoothing(self):
+        """None while target smoothing is off, else its config as a dict."""
+        on, cfg = C.c_int32(), capi.NoiseConfig()
+        self._ck(self.lib.dqnhip_target_noise_get(self.h, C.byref(on), C.byref(cfg)))
+        if not on.value:
+            return None
+        return dict(sigma_logits=cfg.sigma_logits, sigma_params=cfg.sigma_params, clip=cfg.clip, clamp=bool(cfg.clamp), seed=cfg.seed)
+
+    def target_noise_counter(self):
+        """The Philox counter the last update's target noise was keyed by (debug_read "target_noise_counter")."""
+        out = np.empty(2, np.float32)
+        self._ck(self.lib.dqnhip_debug_read(self.h, b"target_noise_counter", _p(out), 2))
+        return int(out[0]) + (int(out[1]) << 24)
 
     def n_step(self):
         """dqnhip_nstep_get: n, or 0 if n-step returns were never enabled."""
@@ -1048,14 +1075,36 @@ class EnvFrontEnd:
             out = np.empty(1, np.float32)
             self.dqn._ck(self.lib.dqnhip_env_debug_read(self.h, name.encode(), _p(out), 1))
             return int(out[0])
-        n = N * (S if name == "state" else 10 if name == "actor_out" else 1)
+        if name == "graph_nodes":
+            out = np.empty(2, np.float32)
+            self.dqn._ck(self.lib.dqnhip_env_debug_read(self.h, name.encode(), _p(out), 2))
+            return int(out[0]), int(out[1])
+        rows10 = name in ("actor_out", "greedy_out", "noise_state", "noise_z")
+        n = N * (S if name == "state" else 10 if rows10 else 1)
         out = np.empty(n, np.float32)
         self.dqn._ck(self.lib.dqnhip_env_debug_read(self.h, name.encode(), _p(out), n))
         if name == "state":
             return out.reshape(N, S)
-        if name == "actor_out":
+        if rows10:
             return out.reshape(N, 10)
         return out
+
+    def set_noise(self, enable=True, sigma_logits=None, sigma_params=None, theta=None, clamp=None, seed=None):
+        """Exploration noise on the greedy ActorOutput, on the device (include/dqnhip_env.h): an Ornstein-Uhlenbeck state per worker
+        and column, theta = 1 for white Gaussian noise; sigmas in units of the column's range.  What is left None keeps the
+        default (theta 0.15, sigma_params 0.1, sigma_logits 0, clamp on: the literature's values, not measured on this workload).
+        set_noise(False) switches it off.  Every call zeroes the OU states."""
+        if not enable:
+            self.dqn._ck(self.lib.dqnhip_env_set_noise(self.h, None))
+            return
+        cfg = capi.NoiseConfig()
+        self.dqn._ck(self.lib.dqnhip_noise_default_config(C.byref(cfg), capi.NOISE_EXPLORE))
+        for k, v in (("sigma_logits", sigma_logits), ("sigma_params", sigma_params), ("theta", theta), ("seed", seed)):
+            if v is not None:
+                setattr(cfg, k, v)
+        if clamp is not None:
+            cfg.clamp = 1 if clamp else 0
+        self.dqn._ck(self.lib.dqnhip_env_set_noise(self.h, C.byref(cfg)))
 
     def close(self):
         if self.h:

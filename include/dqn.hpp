@@ -147,6 +147,9 @@ class DQN {
   bool dp_sync_pending_ = false;                       // a Restore* / Load* ran since the group's last broadcast: re-sync at the next update
   // UpdateActorCritic(): the next call's indices, predicted from a copy of random_engine (dqnhip_update_chained)
   bool spec_valid_ = false; int spec_size_ = 0;
+  // -explore_noise_sigma: Ornstein-Uhlenbeck noise on SelectActions' greedy outputs (dqnhip_noise_explore_host): one state per batch row
+  // (the driver's SelectAction: one), reset by LabelTransitions; the draw counter is the number of greedy SelectActions calls
+  std::vector<float> explore_ou_; unsigned long long explore_calls_ = 0, explore_seed_ = 0;
   std::mt19937 spec_before_, spec_after_;              // the engine as the prediction found / left it
   std::vector<int> spec_idx_;
   bool dp_synced_once_ = false;                        // the group's first update has passed: Restore* / Load* are refused from here on (one-sided collective)

@@ -405,6 +405,7 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world);
 #define DQNHIP_PLAN_EARLY_GATHER_L0 2048        /* multi-update graphs: next gather / next first layers ride in the two optimiser launches (DQNHIP_TUNE_LATE_GATHER) */
 #define DQNHIP_PLAN_DP_TAILS_RIDE 4096          /* data parallel: the [loss, q, flag] tails of the exchange ride in each net's last backward launch */
 #define DQNHIP_PLAN_PRIORITIZED 8192            /* prioritized replay (dqnhip_per_enable): sampler / fill before, k_head_q_train_w inside, the write-back behind every update */
+#define DQNHIP_PLAN_TARGET_SMOOTHING 32768      /* target policy smoothing (dqnhip_target_noise_enable): k_target_smooth behind the actors' heads, the critics' first layers in a launch of their own behind it */
 #define DQNHIP_PLAN_NSTEP 16384                 /* n-step returns (dqnhip_nstep_enable): k_gather_n first, k_head_q_train_n in the head launch's place; the stand-alone sequence per update */
 typedef struct dqnhip_update_plan {
   int32_t struct_size;          /* in: sizeof(dqnhip_update_plan) */
@@ -1082,6 +1083,57 @@ int dqnhip_save_state_poll(dqnhip_handle h, int32_t* done);  /* never blocks; *d
  * a 16-byte boundary, the chunk kernel and the combine step of the asynchronous save run, *crc = zlib's crc32 of the bytes.
  * Stream-ordered, blocks.  For tests, and for anyone who wants to verify a buffer. */
 int dqnhip_state_crc32_device(dqnhip_handle h, const void* host_bytes, size_t bytes, int32_t misalign, uint32_t* crc);
+
+/* ---- action noise on the device: exploration (env handles), target policy smoothing (learner) ---------------------------------
+ * Gaussian noise added to an ActorOutput row inside the kernels that form it.  Both uses are OPT-IN: a learner or env handle that
+ * never enables them launches exactly the kernels it launched before.  One noise body (csrc/noise_bodies.hip.h, one text for host
+ * and device) and one counter-based generator (the Philox-4x32-10 of the sampler):
+ *     standard normal z of the key (seed, ctr, lane0): x1, x2 = the generator's words at lanes lane0, lane0 + 1;
+ *         u1 = ((x1 >> 8) + 1) 2^-24 in (0, 1], u2 = (x2 >> 8) 2^-24 in [0, 1);
+ *         z = (float)(sqrt(-2 log u1) cos(6.283185307179586 u2)), evaluated in double and rounded once; |z| <= 5.77
+ *     column scale: range_j = max - min of ActorOutput column j's bounds (the inverting gradients' table): 2 for the four action
+ *         logits, 100 for the two powers, 360 for the four angles.  sigma_j = sigma_logits for j < 4, sigma_params from there.
+ *         sigma_logits, sigma_params and clip are in UNITS OF THE COLUMN'S RANGE.
+ *     everything after the draw is one separately rounded float32 operation per step (no fma).
+ * Exploration (dqnhip_env_set_noise, dqnhip_env.h): an Ornstein-Uhlenbeck state per worker and column,
+ *         x <- (x - theta x) + sigma_j z,      greedy value v' = v + range_j x,      clamp: min(max(v', min_j), max_j)
+ *     with z keyed by (noise seed, the worker's draw counter at the step's start, worker 32 + 2 j).  theta = 1 is white Gaussian
+ *     noise.  x is zero at creation and after every episode end, and advances on every step whether or not epsilon chose the
+ *     random ActorOutput, which stays un-noised.
+ * The defaults are the literature's values rescaled to units of the range and NOT MEASURED ON THIS WORKLOAD:
+ *     DQNHIP_NOISE_EXPLORE: theta 0.15, sigma_params 0.1 (the OU parameters of Lillicrap et al. 2016 are theta 0.15, sigma 0.2 on
+ *         actions in [-1, 1], a range of 2), sigma_logits 0 (the discrete choice is explored by epsilon), clip 0 (unused), clamp on;
+ *     DQNHIP_NOISE_TARGET: theta 1, sigma_logits = sigma_params = 0.1, clip 0.25 (TD3's sigma 0.2 and clip 0.5 on a range of 2),
+ *         clamp on.
+ * Refused, by message: a sigma that is negative or not finite, theta outside (0, 1], a negative clip, a struct_size mismatch.
+ * Target policy smoothing (TD3, Fujimoto et al. 2018; dqnhip_target_noise_enable; cfg NULL switches it off):
+ *         y = r + gamma Q'(s', a~),   a~_j = clamp(mu'(s')_j + range_j t_j),   t_j = sigma_j z, clipped to [-clip, clip] if clip > 0
+ *     for row r and column j of the update whose sampling counter is c (DevState's update counter: consecutive updates, also the
+ *     sixteen of one dqnhip_update_async_n graph, use consecutive c), z keyed by (noise seed, c, r 32 + 2 j).  a~ replaces mu'(s') as
+ *     the critic-target's action input and nowhere else: dqnhip_debug_read "actor_target_out" keeps the clean mu'(s'),
+ *     "actor_target_smoothed" [B,10] is a~, "target_noise_z" [B,10] the z used, "target_noise_counter" [2] c as (c mod 2^24, c / 2^24).
+ *     One launch more per update (k_target_smooth, between the actors' heads and the critics' first layers), on the schedule of
+ *     DQNHIP_TUNE_SEPARATE_CRITIC_FIRST_LAYERS (DQNHIP_PLAN_TARGET_SMOOTHING).  It composes with prioritized replay, n-step returns,
+ *     every solver and lr policy and dqnhip_update_async_n.  theta must be 1.  Refused in this version, each by a message naming target
+ *     smoothing: precision = DQNHIP_FP16; dqnhip_update_chained / _pipelined / _indexed_n / _phase; data parallelism; parameter and
+ *     replay sharing.  The replay sweep (dqnhip_evaluate_memory, dqnhip_per_refresh) keeps evaluating the CLEAN target.  The
+ *     learner-state file is unchanged (the noise is a hyper-parameter plus the saved update counter): enable it again before
+ *     dqnhip_load_state.  Twin critics and delayed policy updates, TD3's other two ingredients, are not built. */
+#define DQNHIP_NOISE_EXPLORE 0
+#define DQNHIP_NOISE_TARGET 1
+typedef struct dqnhip_noise_config {
+  int32_t struct_size;   /* = sizeof(dqnhip_noise_config) */
+  int32_t clamp;         /* non-zero: clamp the noisy value to the column's bounds */
+  float sigma_logits, sigma_params, theta, clip;
+  uint64_t seed;         /* key of the noise draws (not the env's or the sampler's seed) */
+} dqnhip_noise_config;
+int dqnhip_noise_default_config(dqnhip_noise_config* cfg, int32_t purpose);
+/* The exploration step of ONE row on the host — the text the env kernels evaluate, compiled for the host — for a caller that
+ * selects its actions one state at a time (dqn_dropin.cpp's SelectAction): draws the ten normals of the key (cfg->seed, counter,
+ * row 32 + 2 j), advances ou_state[10] and puts it on actor_out[10] in place.  No device is touched. */
+int dqnhip_target_noise_enable(dqnhip_handle h, const dqnhip_noise_config* cfg);
+int dqnhip_target_noise_get(dqnhip_handle h, int32_t* enabled, dqnhip_noise_config* cfg);   /* cfg may be NULL */
+int dqnhip_noise_explore_host(const dqnhip_noise_config* cfg, uint64_t counter, int32_t row, float* ou_state, float* actor_out);
 
 /* ---- batched env front-end (HFOGameState reward shaping, N workers) ----- */
 

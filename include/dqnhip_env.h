@@ -69,8 +69,21 @@ int dqnhip_env_stats(dqnhip_env_handle e, int64_t* env_steps, int64_t* episodes,
 
 /* Parity / debugging: per-worker values of the LAST step.  name: "action" [N] (GetAction index),
  * "arg1" [N], "arg2" [N], "reward" [N], "actor_out" [N,10], "state" [N,S] (current state),
- * "episode_len" [N]; "truncated" [1] (episodes an external handle closed at max_steps). */
+ * "episode_len" [N]; "truncated" [1] (episodes an external handle closed at max_steps); "graph_nodes" [2] (launches in the
+ * captured one-step and 16-step graphs of a synthetic handle, 0 while not captured). */
 int dqnhip_env_debug_read(dqnhip_env_handle e, const char* name, float* host, size_t count);
+
+/* Exploration noise on the greedy ActorOutput, both kinds of handle (semantics, key and defaults: "action noise" in dqnhip.h).
+ * cfg NULL switches it off.  Off is the state at creation, and a handle that stays there launches what it always launched.
+ * With noise on, every step draws ten normals per worker and advances the worker's OU state (on an epsilon-random step too, whose
+ * random row stays un-noised); on a greedy step the noisy row is what opens the transition (the episode row, and through it the
+ * replay memory), what dqnhip_env_act hands out as actor_out, and what GetAction reads.  The state is zero after a step that ends
+ * the worker's episode.  It works in both acting precisions: the noise sits behind the heads.  cfg->clip is not used.
+ * Every call zeroes all OU states and drops the handle's captured steps (the config is a kernel argument), blocking once.
+ * dqnhip_env_debug_read then also knows "greedy_out" [N,10] (the heads' own output), "noise_state" [N,10] (the OU states after the
+ * last step) and "noise_z" [N,10] (the last step's draws), and its "actor_out" is the row the last step chose (noisy greedy or
+ * random; before the first step with noise: the greedy row). */
+int dqnhip_env_set_noise(dqnhip_env_handle e, const dqnhip_noise_config* cfg);
 
 /* ---- the external kind: states from the caller ------------------------------------------------ */
 
