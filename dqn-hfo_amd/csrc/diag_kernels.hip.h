@@ -1,5 +1,5 @@
 // diag_kernels.hip.h — update diagnostics (dqnhip_diag_collect, include/dqnhip.h has the definitions): what the last update left on
-// the device, reduced on the device to a few tens of KB.  Included and launched by learner_io.hip only; a learner that never collects
+// the device, reduced on the device to a few tens of KB.  Included and launched by learner_eval.hip only; a learner that never collects
 // launches none of this.  A collection READS the learner and writes nothing but its own scratch.
 //
 // Three launches per collection:

@@ -1008,7 +1008,7 @@ int dqnhip_apply_update(dqnhip_handle h, int32_t net) {
   h->epoch += 1;
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
   if (h->next_phase != 0) return fail("dqnhip_apply_update: a phased update is in progress (next phase %d)", h->next_phase);
-  RC(sched_refuse(h, "dqnhip_apply_update"));
+  RC(feature_refuse(h, kFeatSched, "dqnhip_apply_update"));
   HIPCHK(hipSetDevice(h->cfg.device));
   RC(sync_dirty16(h));
   const NetLayout& l = layout_of(h, net);
@@ -1031,7 +1031,7 @@ int dqnhip_apply_update_sharded(dqnhip_handle h, int32_t net, int32_t world) {
   h->epoch += 1;
   if (net != DQNHIP_ACTOR && net != DQNHIP_CRITIC) return fail("net must be ACTOR or CRITIC");
   if (h->next_phase != 0) return fail("dqnhip_apply_update_sharded: a phased update is in progress (next phase %d)", h->next_phase);
-  RC(sched_refuse(h, "dqnhip_apply_update_sharded"));
+  RC(feature_refuse(h, kFeatSched, "dqnhip_apply_update_sharded"));
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
     return fail("dqnhip_apply_update_sharded: the %s solver has no sharded form in this version (DESIGN.md 9); use dqnhip_apply_update", dqnhip_solver_name(h->cfg.solver_type));
   const NetLayout& l = layout_of(h, net);

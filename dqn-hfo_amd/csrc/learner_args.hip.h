@@ -8,9 +8,10 @@
 //               __device__ functions only; noise_bodies.hip.h (exploration noise: __host__ __device__, one text for both sides)
 //   kernels     gemm_direct.hip.h, hgemm.hip.h, head_fwd_kernels.hip.h, head_kernels.hip.h, small_kernels.hip.h (gather, optimiser),
 //               solver_kernels.hip.h (the optimiser launches of the solvers other than Adam; learner.hip),
-//               io_kernels.hip.h, per_kernels.hip.h (prioritized replay; learner_io.hip), diag_kernels.hip.h (update diagnostics;
-//               learner_io.hip), state_kernels.hip.h, snapshot_kernels.hip.h (asynchronous state save / Caffe snapshot;
-//               learner_io.hip), env.hip.h: __global__ functions and their launchers, grouped by the unit that launches them
+//               io_kernels.hip.h (learner_io.hip), per_kernels.hip.h (prioritized replay; learner_per.hip), diag_kernels.hip.h,
+//               sweep_kernels.hip.h (update diagnostics, replay sweep; learner_eval.hip), state_kernels.hip.h, snapshot_kernels.hip.h
+//               (asynchronous state save / Caffe snapshot; learner_save_async.hip), env.hip.h (learner_env.hip): __global__ functions
+//               and their launchers, grouped by the unit that launches them
 // One include points upwards: head_fwd_kernels.hip.h holds the launcher head_forward<>, which takes the learner and reports through
 // HIPCHK, and so includes learner_internal.hip.h.
 #pragma once

@@ -240,11 +240,8 @@ int dqnhip_dp_init(dqnhip_handle h, const void* id, size_t bytes, int32_t flags)
   if (h->comm) return fail("dp_init: this learner already has a communicator");
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)
     return fail("dp_init: the %s solver is a single-learner solver in this version (its data-parallel forms do not exist: DESIGN.md 9)", dqnhip_solver_name(h->cfg.solver_type));
-  RC(sched_refuse(h, "dqnhip_dp_init"));
-  RC(per_refuse(h, "dqnhip_dp_init"));
-  RC(nstep_refuse(h, "dqnhip_dp_init"));
-  RC(smooth_refuse(h, "dqnhip_dp_init"));
-  if (h->w_owner || h->sharers) return fail("dp_init: learners that share layers cannot join a data-parallel group");
+  RC(feature_refuse(h, kFeatAll, "dqnhip_dp_init"));
+  if (shares_params(h)) return fail("dp_init: learners that share layers cannot join a data-parallel group");
   if (h->ls_dynamic) return fail("dp_init: loss_scale_mode = dynamic is a single-learner mode (the data-parallel form has never run: DESIGN.md 9)");
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -313,7 +310,7 @@ int dqnhip_dp_init_file(dqnhip_handle h, const char* path, int32_t flags, int32_
   if (h->cfg.solver_type != DQNHIP_SOLVER_ADAM)      // (before the rendezvous: no rank is left waiting for this one)
     return fail("dp_init: the %s solver is a single-learner solver in this version (its data-parallel forms do not exist: DESIGN.md 9)", dqnhip_solver_name(h->cfg.solver_type));
   if (h->ls_dynamic) return fail("dp_init: loss_scale_mode = dynamic is a single-learner mode (the data-parallel form has never run: DESIGN.md 9)");
-  RC(sched_refuse(h, "dqnhip_dp_init_file"));
+  RC(feature_refuse(h, kFeatSched, "dqnhip_dp_init_file"));
   ncclUniqueId uid;
   if (h->cfg.dp_rank == 0) RC(dqnhip_dp_unique_id(&uid, sizeof uid));
   RC(dqnhip_dp_rendezvous_file(path, h->cfg.dp_rank, h->cfg.dp_world, timeout_s, &uid, sizeof uid));

@@ -8,14 +8,17 @@
 //   learner_update.hip  index staging, graph capture (capture_updates), dqnhip_update* / dqnhip_get_update_plan / dqnhip_read_stats,
 //                       the in-library benchmark loops; host only
 //   learner_dp.hip      native data parallelism: RCCL inside the library, the file rendezvous (dqnhip_dp_*)
-//   learner_io.hip      acting, replay memory (+ .replaymemory files), prioritized replay (dqnhip_per_*), n-step returns (dqnhip_nstep_*), parameters, multi-agent sharing,
-//                       introspection, update diagnostics (dqnhip_diag_collect), the replay sweep (dqnhip_evaluate_memory /
-//                       dqnhip_per_refresh: sweep_kernels.hip.h; its forward launches are sweep_forward's, learner.hip), the launches
-//                       of the asynchronous state save and of the asynchronous Caffe snapshot (snapshot_kernels.hip.h)
+//   learner_io.hip      acting, replay memory (+ .replaymemory files, dqnhip_nstep_validate), parameters, multi-agent sharing,
+//                       iterations / learning rate, dqnhip_debug_read, stream and kernel timing (head_fwd_kernels.hip.h, io_kernels.hip.h)
+//   learner_per.hip     prioritized replay: the per_* launchers the other units call and dqnhip_per_* (per_kernels.hip.h)
+//   learner_eval.hip    update diagnostics (dqnhip_diag_collect: diag_kernels.hip.h) and the replay sweep (dqnhip_evaluate_memory /
+//                       dqnhip_per_refresh: sweep_kernels.hip.h; its forward launches are sweep_forward's, learner.hip)
+//   learner_features.hip  n-step returns (dqnhip_nstep_*) and target smoothing (dqnhip_target_noise_*), whose kernels learner.hip
+//                       launches, and feature_refuse: the one place a call refuses a learner for an opt-in feature; host only
 //   learner_env.hip     host side of the batched env front-end (include/dqnhip_env.h)
 //   learner_state.hip   the native learner-state file: dqnhip_save_state / dqnhip_load_state; host only
-//   learner_save_async.hip  the host side of dqnhip_save_state_async and dqnhip_snapshot_async: the writer thread they share and
-//                       each one's staging buffer and job (the kernels are launched from learner_io.hip); host only.
+//   learner_save_async.hip  dqnhip_save_state_async and dqnhip_snapshot_async: their pack and checksum launches (state_kernels.hip.h,
+//                       snapshot_kernels.hip.h), the writer thread they share and each one's staging buffer and job.
 //                       learner_state.hip.h: what the two units above share
 //   snapshot.cpp        Caffe snapshot layout (no device code); snapshot_codec.h: its builders on host pointers, for the writer thread
 //   state_codec.cpp     the learner-state file's container (header, table, CRCs) and its manifest (the order of the sections),
@@ -53,7 +56,6 @@
 #include "noise_bodies.hip.h"     // NoiseCfg and the host side of the noise body (no kernel)
 #include "gemm_plan.hip.h"        // the fp32 forms and their choosers (bwd_layer_is_pair)
 #include "hgemm_plan.hip.h"
-#include "state_image.h"        // plain structures of the asynchronous state save
 
 namespace dqnhip_host {
 using namespace dqnhip;
@@ -151,8 +153,8 @@ struct TargetNoiseHost {
   float* smoothed16 = nullptr; float* z16 = nullptr;   // [B][kAP]: a~ and the z of the last update
   unsigned long long* counter = nullptr;               // [1] the Philox counter the last update's noise was keyed by
 };
-struct DiagHost;                        // update diagnostics (learner_io.hip; the kernels: diag_kernels.hip.h)
-struct SweepHost;                       // replay sweep (learner_io.hip; the kernels: sweep_kernels.hip.h)
+struct DiagHost;                        // update diagnostics (learner_eval.hip; the kernels: diag_kernels.hip.h)
+struct SweepHost;                       // replay sweep (learner_eval.hip; the kernels: sweep_kernels.hip.h)
 struct SaveWriter;                      // asynchronous learner-state save and Caffe snapshot (learner_save_async.hip; the kernels: state_kernels.hip.h, snapshot_kernels.hip.h)
 
 }  // namespace dqnhip_host
@@ -364,8 +366,27 @@ inline bool has_policy(const H* h) { return h->cfg.lr_policy != DQNHIP_LR_FIXED;
 inline bool has_decay(const H* h) { return h->cfg.weight_decay != 0.0f; }
 // does this learner's optimiser pass run k_sched_soft<>?  (an Adam learner with a policy and no decay keeps the tuned kernels)
 inline bool sched_family(const H* h) { return has_decay(h) || (has_policy(h) && h->cfg.solver_type != DQNHIP_SOLVER_ADAM); }
-// the v1 refusals of a learner with a policy or a decay: fails, as `what`, naming both
-int sched_refuse(const H* h, const char* what);
+// ---- what a call asks of a learner before it refuses it: every site composes these, none writes a condition out ----
+// Data parallelism, twice: a one-rank group has a communicator (dqnhip_dp_init) and still runs the single-learner entry points.
+// dp_exchanges: this learner's update runs the N-rank code path (plan_of's dp; the single-learner update forms refuse it)
+inline bool dp_exchanges(const H* h) { return h->cfg.dp_world > 1 || h->dp_half || h->dp_shard; }
+// dp_grouped: ... or it belongs to a group at all, a one-rank group included (what the opt-in features, the sweep and the state file refuse)
+inline bool dp_grouped(const H* h) { return dp_exchanges(h) || h->comm; }
+// uses another learner's ring, or others use (or used) its own
+inline bool shares_ring(const H* h) { return h->ring_owner || h->ring_shared; }
+// reads another learner's parameters, or other learners reference this one (sharers counts ring users too)
+inline bool shares_params(const H* h) { return h->w_owner || h->sharers; }
+// The four opt-in features a learner can carry, in the order feature_refuse checks them
+enum Feature : unsigned {
+  kFeatSched = 1u,                      // cfg.lr_policy / cfg.weight_decay
+  kFeatPer = 2u,                        // prioritized replay (dqnhip_per_enable)
+  kFeatNstep = 4u,                      // n-step returns (dqnhip_nstep_enable)
+  kFeatSmooth = 8u,                     // target policy smoothing (dqnhip_target_noise_enable)
+  kFeatSampling = kFeatPer | kFeatNstep | kFeatSmooth,      // the three that change what an update gathers and targets
+  kFeatAll = kFeatSched | kFeatSampling
+};
+// the v1 refusals (learner_features.hip): fails, as `what`, naming the first feature of `mask` — in the order above — that h carries
+int feature_refuse(const H* h, unsigned mask, const char* what);
 bool is_pow2(float x);                                   // a positive, normal power of two (loss-scale multipliers)
 // shape predicates of the launch schedules (learner_plan.hip)
 bool bwd_layer_is_pair(const NetLayout& l, int i, int rows);
@@ -468,7 +489,7 @@ const char* rccl_path();
 bool same_nets(const H* a, const H* b);
 // k_pack_rows16: fp32 [n][ld_src] (the first S columns of each row) -> fp16 [rows][k16], pad rows and columns zero
 int pack_rows16_launch(hipStream_t st, const float* src, int n, int S, int ld_src, h16* dst, int rows, int k16);
-// prioritized replay: the host launchers of per_kernels.hip.h (learner_io.hip) and what the other units need of it
+// learner_per.hip — prioritized replay: the host launchers of per_kernels.hip.h and what the other units need of it
 int per_sync_if_needed(H* h);                            // k_per_sync, if the ring may have changed since the last one
 void per_note_append(H* h, long long n);                 // BEFORE up to n transitions are appended: keeps the bound below cap (may enqueue a sync)
 int per_sample_launch(H* h);                             // k_per_sample on the live counter -> per->idx / slot / prob
@@ -476,27 +497,20 @@ int per_fill_launch(H* h, const int* idx_dev);           // k_per_fill: explicit
 int per_update_launch(H* h);                             // k_per_update
 int per_clear(H* h);                                     // dqnhip_clear_memory: the tree zero, p_max stays
 void per_free(H* h);
+const float* per_p_max_dev(const H* h);                  // the device address of PerDev::p_max (null: not a prioritized learner)
 int per_read_p_max(H* h, float* p_max);                  // PerDev::p_max, behind everything enqueued so far
 int per_restore(H* h, const float* leaves, int head, int size, float p_max, long long syncs);   // dqnhip_load_state: the tree from a window's leaves
-int per_refuse(const H* h, const char* what);            // fails, naming prioritized replay, if h is a prioritized learner
-// n-step returns (learner_io.hip)
-int nstep_refuse(const H* h, const char* what);          // fails, naming n-step returns, if they are enabled on h
+// learner_features.hip
 void nstep_free(H* h);
-int smooth_refuse(const H* h, const char* what);         // fails, naming target smoothing, if it is enabled on h
 void smooth_free(H* h);
 // does every update of this learner run the stand-alone sequence, also inside a multi-update graph?  (no rider serves a successor)
 inline bool standalone_updates(const H* h) { return h->per != nullptr || h->nstep != nullptr; }
+// learner_eval.hip
 void diag_free(H* h);                                    // dqnhip_diag_collect's scratch
 void sweep_free(H* h);                                   // the replay sweep's scratch
-// asynchronous learner-state save: the launchers of state_kernels.hip.h, on the learner's stream (learner_io.hip) ...
-int state_pack_params_launch(H* h, const dqnhip_state::PackSeg* segs_dev, int n_seg, dqnhip_state::StateRec* rec_dev);
-int state_pack_ring_launch(H* h, const dqnhip_state::RingPackArgs& a);
-int state_crc_launch(H* h, const dqnhip_state::CrcArgs& a);
-// ... and its host side (learner_save_async.hip)
+// learner_save_async.hip
 int state_async_join(H* h, const char* what);            // waits for a save in flight; fails, as `what`, with its message if it failed
 void state_async_free(H* h);                             // dqnhip_destroy: joins both kinds of job, stops the writer thread, frees; never fails
-// asynchronous Caffe snapshot (dqnhip_snapshot_async): the launcher of snapshot_kernels.hip.h (learner_io.hip), the join (learner_save_async.hip)
-int snap_pack_replay_launch(H* h, uint8_t* stream_dev);
 int snapshot_async_join(H* h, const char* what);         // waits for a snapshot in flight; fails, as `what`, with its message if it failed
 
 }  // namespace dqnhip_host

@@ -94,12 +94,6 @@ LrSchedule schedule_of(const dqnhip_config& c) {
   return s;
 }
 
-int sched_refuse(const H* h, const char* what) {
-  if (!has_policy(h) && !has_decay(h)) return 0;
-  return fail("%s: not available on a learner with lr_policy %s / weight_decay %g in this version (single learner, inside an update only, no diagnostics: DESIGN.md 9)",
-              what, dqnhip_lr_policy_name(h->cfg.lr_policy), (double)h->cfg.weight_decay);
-}
-
 int validate(const dqnhip_config* in, dqnhip_config* full) {
   if (!in) return fail("config is null");
   // the struct as it is, or as it was before the lr_policy .. regularization_type block was put in behind rms_decay (a caller compiled
@@ -204,7 +198,7 @@ UpdatePlan plan_of(const H* h) {
   const int tf = h->cfg.tuning_flags;
   UpdatePlan p{};
   p.fp16 = h->fp16;
-  p.dp = h->cfg.dp_world > 1 || h->dp_half || h->dp_shard;     // (a one-rank group with bf16 exchange / a sharded optimiser runs the N-rank code path)
+  p.dp = dp_exchanges(h);     // (a one-rank group with bf16 exchange / a sharded optimiser runs the N-rank code path)
   p.fused_seed = !(tf & DQNHIP_TUNE_SEPARATE_HEAD_SEED);
   p.prioritized = h->per != nullptr;
   p.nstep = h->nstep != nullptr;

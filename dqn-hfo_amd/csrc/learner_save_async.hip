@@ -1,5 +1,5 @@
-// learner_save_async.hip — the host side of the two saves that run behind training, and the writer thread they share.  Host only:
-// the kernels (state_kernels.hip.h, snapshot_kernels.hip.h) are launched from learner_io.hip.
+// learner_save_async.hip — the two saves that run behind training: their pack and checksum launches (state_kernels.hip.h,
+// snapshot_kernels.hip.h), their host side, and the writer thread they share.
 // dqnhip_save_state_async: the file of dqnhip_save_state (learner_state.hip; the same manifest, state_codec.h).  The caller's thread
 // enqueues the pack and the chunk CRCs on the learner's stream and posts a job to the writer, which waits for the event, folds the
 // CRCs, and streams the staging buffer to the file through two pinned chunks.
@@ -14,6 +14,8 @@
 #include "gzip_parallel.h"
 #include "snapshot_codec.h"
 #include "snapshot_stream.h"
+#include "state_kernels.hip.h"
+#include "snapshot_kernels.hip.h"
 
 using namespace dqnhip_state;
 
@@ -389,6 +391,39 @@ int snap_stage_init(H* h) {
 
 void stage_free(Stage* s) { hipEventDestroy(s->ev); hipFree(s->buf); }
 
+// ---- the launchers of state_kernels.hip.h, on the learner's stream ----
+int state_pack_params_launch(H* h, const PackSeg* segs_dev, int n_seg, StateRec* rec_dev) {
+  HIPCHK(launch(h->stream, k_state_pack_params, dim3(64, n_seg + 1), dim3(256), 0, segs_dev, n_seg, (const DevState*)h->st, per_p_max_dev(h), rec_dev));
+  return 0;
+}
+int state_pack_ring_launch(H* h, const RingPackArgs& a) {
+  if (a.cap < 1 || a.n_arr < 1 || a.n_arr > kRingArrays) return fail("state_pack_ring_launch: bad arguments");
+  HIPCHK(launch(h->stream, k_state_pack_ring, dim3((a.cap + kPackRows - 1) / kPackRows, a.n_arr), dim3(256), 0, a));
+  return 0;
+}
+int state_crc_launch(H* h, const CrcArgs& a) {
+  if (a.n < 1 || a.n > kMaxCrcSections) return fail("state_crc_launch: bad arguments");
+  if (a.total_chunks == 0) return 0;
+  HIPCHK(launch(h->stream, k_state_crc, dim3((a.total_chunks + 255) / 256), dim3(256), 0, a));
+  return 0;
+}
+// asynchronous Caffe snapshot (snapshot_kernels.hip.h): the ring's window as the `.replaymemory` stream at `stream_dev`, which has
+// room for the stream of a full ring and, behind that (rounded up to a dword), the guard band this call fills and nothing else writes.
+// The stream's first record (stream_dev + 4) lies on a 16-byte boundary.  64 records per workgroup measured fastest
+// (profiles/snapshot_async_ab.md); fewer where the state is so long that 64 rows do not fit the LDS a launch gets without asking
+int snap_pack_replay_launch(H* h, uint8_t* stream_dev) {
+  const uint64_t max_dwords = dqnhip_snap::stream_dwords(h->S, (uint64_t)h->ring.cap);
+  const size_t row_bytes = (size_t)dqnhip_snap::snap_lds_row_words(h->S) * sizeof(uint32_t);
+  int K = 64;
+  while (K > 16 && K * row_bytes > 48 * 1024) K /= 2;
+  if (K * row_bytes > 48 * 1024) return fail("the asynchronous snapshot's pack kernel stages 16 records of %zu bytes in LDS: too long a state (S = %d)", row_bytes, h->S);
+  if ((uintptr_t)(stream_dev + 4) % 16 != 0 || h->ring.cap < 1) return fail("snap_pack_replay_launch: bad arguments");
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(stream_dev + 4 * max_dwords), (int)dqnhip_snap::kGuardWord, dqnhip_snap::kGuardWords, h->stream));
+  HIPCHK(launch(h->stream, k_snap_pack_replay, dim3((unsigned)((h->ring.cap + K - 1) / K)), dim3(256), K * row_bytes, h->ring, (const DevState*)h->st,
+                (uint32_t*)stream_dev, max_dwords, K));
+  return 0;
+}
+
 }  // namespace
 
 namespace dqnhip_host {
@@ -525,6 +560,31 @@ int dqnhip_snapshot_wait(dqnhip_handle h, int32_t* actor_iter, int32_t* critic_i
 int dqnhip_snapshot_poll(dqnhip_handle h, int32_t* done) {
   if (!h || !done) return fail("dqnhip_snapshot_poll: null argument");
   *done = !h->sasync || h->sasync->poll(kJobSnapshot);
+  return 0;
+}
+
+// k_state_crc on caller-supplied bytes, through the learner's staging buffer: the door the tests check the device checksum through
+int dqnhip_state_crc32_device(dqnhip_handle h, const void* host_bytes, size_t bytes, int32_t misalign, uint32_t* crc) {
+  if (!h || !crc || (!host_bytes && bytes)) return fail("dqnhip_state_crc32_device: null argument");
+  if (misalign < 0 || misalign > 15) return fail("dqnhip_state_crc32_device: misalign %d is outside 0 ... 15", misalign);
+  if (bytes > ((size_t)1 << 31)) return fail("dqnhip_state_crc32_device: %zu bytes are more than this door takes (2^31)", bytes);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t chunks = (bytes + kCrcChunk - 1) / kCrcChunk, out_off = round_up_z((size_t)misalign + bytes, 16);
+  RC(ensure_stage(h, out_off + chunks * sizeof(uint32_t) + 16));
+  uint8_t* base = (uint8_t*)h->stage_dev;
+  if (bytes) HIPCHK(hipMemcpyAsync(base + misalign, host_bytes, bytes, hipMemcpyHostToDevice, h->stream));
+  CrcArgs a{};
+  a.base = base; a.rec = nullptr; a.out = (uint32_t*)(base + out_off); a.n = 1; a.max_rows = 0; a.total_chunks = (uint32_t)chunks;
+  a.sec[0] = CrcSection{(uint64_t)misalign, (uint64_t)bytes, 0u, 0u};
+  RC(state_crc_launch(h, a));
+  std::vector<uint32_t> raws(chunks);
+  if (chunks) HIPCHK(hipMemcpyAsync(raws.data(), a.out, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint32_t op[32];
+  std::vector<uint32_t> tab(kCrcTableWords);
+  crc_zeros_op(op, kCrcChunk);
+  crc_op_table(tab.data(), op);
+  *crc = crc_fold_chunks(raws.data(), bytes, tab.data());
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // learner_state.hip — dqnhip_save_state / dqnhip_load_state: the native learner-state file (include/dqnhip.h; DESIGN.md 9 has the
 // byte layout, state_codec.cpp the container and the manifest: which sections, in which order).  Host only: copies between the
 // learner's device state and the file's sections, no kernel of its own — the one launch a load may need, the priority tree's set
-// pass, goes through per_restore (learner_io.hip).  The save takes its bytes through dqnhip_get_params and plain copies of the ring's
+// pass, goes through per_restore (learner_per.hip).  The save takes its bytes through dqnhip_get_params and plain copies of the ring's
 // window: it shares the manifest with dqnhip_save_state_async (learner_save_async.hip) and nothing of that one's device path, so
 // either checks the other.
 #include "learner_state.hip.h"
@@ -11,9 +11,9 @@ using namespace dqnhip_state;
 namespace dqnhip_host {
 
 int state_refuse(const H* h, const char* what) {
-  if (h->ring_owner || h->ring_shared) return fail("%s: a learner that shares a replay memory (dqnhip_share_replay_memory) is not supported in this version", what);
-  if (h->w_owner || h->sharers) return fail("%s: a learner that shares parameters or is shared from (dqnhip_share_parameters) is not supported in this version", what);
-  if (h->cfg.dp_world > 1 || h->comm || h->dp_half || h->dp_shard) return fail("%s: a data-parallel learner (dp_world > 1, dqnhip_dp_init) is not supported in this version", what);
+  if (shares_ring(h)) return fail("%s: a learner that shares a replay memory (dqnhip_share_replay_memory) is not supported in this version", what);
+  if (shares_params(h)) return fail("%s: a learner that shares parameters or is shared from (dqnhip_share_parameters) is not supported in this version", what);
+  if (dp_grouped(h)) return fail("%s: a data-parallel learner (dp_world > 1, dqnhip_dp_init) is not supported in this version", what);
   if (h->next_phase != 0) return fail("%s: a phased update is in progress (next phase %d)", what, h->next_phase);
   if (h->timing) return fail("%s: kernel timing is on (dqnhip_set_kernel_timing)", what);
   return 0;

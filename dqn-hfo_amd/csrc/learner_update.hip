@@ -311,7 +311,7 @@ int dqnhip_update_async_n(dqnhip_handle h, int32_t n) {
   h->epoch += 1;
   if (n < 0) return fail("dqnhip_update_async_n: n must be >= 0");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_async_n: data-parallel learners use dqnhip_dp_update");
+  if (dp_exchanges(h)) return fail("dqnhip_update_async_n: data-parallel learners use dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_async_n: a phased update is in progress (next phase %d)", h->next_phase);
   RingUse ring_use(h);
   RC(sync_dirty16(h));
@@ -338,11 +338,9 @@ int dqnhip_update_indexed_n(dqnhip_handle h, const int32_t* idx_host, int32_t n)
   if (!h) return fail("null handle");
   h->epoch += 1;
   if (n < 0) return fail("dqnhip_update_indexed_n: n must be >= 0");
-  RC(per_refuse(h, "dqnhip_update_indexed_n"));
-  RC(nstep_refuse(h, "dqnhip_update_indexed_n"));
-  RC(smooth_refuse(h, "dqnhip_update_indexed_n"));
+  RC(feature_refuse(h, kFeatSampling, "dqnhip_update_indexed_n"));
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
+  if (dp_exchanges(h)) return fail("dqnhip_update_indexed_n: data-parallel learners use dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_indexed_n: a phased update is in progress (next phase %d)", h->next_phase);
   if (n == 0) return 0;
   if (!idx_host) return fail("dqnhip_update_indexed_n: explicit indices required (on-device sampling: dqnhip_update_async_n)");
@@ -408,9 +406,7 @@ int dqnhip_collect_stats(dqnhip_handle h, float* critic_loss, float* avg_q, int3
 
 int dqnhip_update_phase(dqnhip_handle h, int32_t phase, const int32_t* idx_host) {
   if (!h) return fail("null handle");
-  RC(per_refuse(h, "dqnhip_update_phase"));
-  RC(nstep_refuse(h, "dqnhip_update_phase"));
-  RC(smooth_refuse(h, "dqnhip_update_phase"));
+  RC(feature_refuse(h, kFeatSampling, "dqnhip_update_phase"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
   // (with DQNHIP_DP_HALF_GRADS the exchange — bf16 image, all-reduce, widening by the clip-norm pass — lives inside
@@ -537,12 +533,10 @@ int dqnhip_update(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, 
 int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_t* idx_next, float* critic_loss, float* avg_q) {
   if (!h) return fail("null handle");
   if (!idx_host) return fail("dqnhip_update_chained: explicit indices required (on-device sampling: dqnhip_update_async_n)");
-  RC(per_refuse(h, "dqnhip_update_chained"));
-  RC(nstep_refuse(h, "dqnhip_update_chained"));
-  RC(smooth_refuse(h, "dqnhip_update_chained"));
+  RC(feature_refuse(h, kFeatSampling, "dqnhip_update_chained"));
   HIPCHK(hipSetDevice(h->cfg.device));
   const UpdatePlan P = plan_of(h);
-  const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && h->sharers == 0 && h->w_owner == nullptr;
+  const bool can = P.early_l0 && !P.dp && !h->comm && h->cfg.use_graph && !h->timing && !h->graph_failed && !shares_params(h);
   if (!can) { h->chain_valid = false; return dqnhip_update(h, idx_host, critic_loss, avg_q); }
   if (h->next_phase != 0) return fail("dqnhip_update_chained: a phased update is in progress (next phase %d)", h->next_phase);
   {
@@ -586,12 +580,10 @@ int dqnhip_update_chained(dqnhip_handle h, const int32_t* idx_host, const int32_
 // every call.  Indices and scalars use two pinned slots each (nothing in flight is overwritten).
 int dqnhip_update_pipelined(dqnhip_handle h, const int32_t* idx_host, float* critic_loss, float* avg_q) {
   if (!h) return fail("null handle");
-  RC(per_refuse(h, "dqnhip_update_pipelined"));
-  RC(nstep_refuse(h, "dqnhip_update_pipelined"));
-  RC(smooth_refuse(h, "dqnhip_update_pipelined"));
+  RC(feature_refuse(h, kFeatSampling, "dqnhip_update_pipelined"));
   h->epoch += 1;
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->cfg.dp_world > 1 || h->dp_half || h->dp_shard) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");
+  if (dp_exchanges(h)) return fail("dqnhip_update_pipelined: data-parallel learners use dqnhip_update_phase / dqnhip_dp_update");
   if (h->next_phase != 0) return fail("dqnhip_update_pipelined: a phased update is in progress (next phase %d)", h->next_phase);
   if (!h->pipe_ev[0]) {
     for (int i = 0; i < 2; ++i) {

@@ -1,6 +1,6 @@
 // per_kernels.hip.h — proportional prioritized replay (Schaul et al. 2016), the replay-side kernels: a radix-64 sum tree over the
 // PHYSICAL slots of the ring, its reconciliation with the ring (k_per_sync), the stratified sampler (k_per_sample), the fill for
-// explicit indices (k_per_fill) and the write-back (k_per_update).  Launched by learner_io.hip.  (Kernels are static: a unit that
+// explicit indices (k_per_fill) and the write-back (k_per_update).  Launched by learner_per.hip.  (Kernels are static: a unit that
 // includes this embeds all of them.)  The weighted critic loss is k_head_q_train_w, head_kernels.hip.h.
 //
 // THE TREE.  Level 0 holds one float32 leaf per physical slot, padded with zeros to a multiple of 64; level k + 1 holds one node per

@@ -1,6 +1,6 @@
 // snapshot_kernels.hip.h — the device side of the asynchronous Caffe snapshot (dqnhip_snapshot_async, include/dqnhip.h):
 // the replay memory as the uncompressed `.replaymemory` stream, in its final bytes, in the snapshot's staging buffer.  Included and
-// launched by learner_io.hip only; a learner that never snapshots asynchronously launches none of this.  The parameters and the
+// launched by learner_save_async.hip only; a learner that never snapshots asynchronously launches none of this.  The parameters and the
 // record (k_state_pack_params) and the stream's CRC-32 (k_state_crc) are the learner-state save's kernels, unchanged.
 //
 //   k_snap_pack_replay   a workgroup owns K records (K a multiple of 16, so their bytes are whole 16-byte pieces; snapshot_stream.h

@@ -1,5 +1,5 @@
 // snapshot_stream.h — the uncompressed `.replaymemory` stream (reference src/dqn.cpp:1146-1178) as the asynchronous Caffe snapshot
-// (dqnhip_snapshot_async) assembles it: what k_snap_pack_replay (snapshot_kernels.hip.h, launched from learner_io.hip) runs, its host
+// (dqnhip_snapshot_async) assembles it: what k_snap_pack_replay (snapshot_kernels.hip.h, launched from learner_save_async.hip) runs, its host
 // side (learner_save_async.hip) and the host test (tests/cpp/snapshot_stream_host.cpp) share.  Plain C++: no HIP header is needed.
 //
 // The stream:  i32 n, then n records of R = 4 S + 49 bytes in logical order (logical i <- physical slot (head + i) % cap):

@@ -1,5 +1,5 @@
 // state_image.h — what the asynchronous learner-state save (dqnhip_save_state_async) shares between its kernels
-// (state_kernels.hip.h, launched from learner_io.hip), its host side (learner_save_async.hip) and the host test
+// (state_kernels.hip.h), the unit that launches them and holds its host side (learner_save_async.hip) and the host test
 // (tests/cpp/state_stream_host.cpp): the device record, the CRC section table, and zlib's CRC-32 as bodies that compile for the
 // device and for the host.  Plain C++: no HIP header is needed to include it.
 //

@@ -1,6 +1,6 @@
 // state_kernels.hip.h — the device side of the asynchronous learner-state save (dqnhip_save_state_async, include/dqnhip.h):
 // one pass on the learner's stream freezes the file's sections, as their final bytes, in a staging buffer and checksums them there.
-// Included and launched by learner_io.hip only; a learner that never saves asynchronously launches none of this.  The kernels READ
+// Included and launched by learner_save_async.hip only; a learner that never saves asynchronously launches none of this.  The kernels READ
 // the learner and write nothing but the staging buffer.  state_image.h has the structures and the CRC bodies (host and device).
 //
 //   k_state_pack_params  grid (x, segments + 1): slice y < segments moves one strided piece of a parameter arena (a layer's weights

@@ -1,6 +1,6 @@
 // sweep_kernels.hip.h — the replay sweep (dqnhip_evaluate_memory / dqnhip_per_refresh, include/dqnhip.h has the definitions): the
 // row arithmetic and the reduction behind the forward passes of one chunk of B consecutive transitions.  Included and launched by
-// learner_io.hip only; a learner that never sweeps launches none of this.  What a chunk launches in front of k_sweep_rows — the
+// learner_eval.hip only; a learner that never sweeps launches none of this.  What a chunk launches in front of k_sweep_rows — the
 // update's gather and its forward launches, no backward, no optimiser — is sweep_forward's business (learner.hip).
 //
 // The chunk base lives in device memory (SweepDev), as the indices of a captured update do: one captured chunk serves every chunk.

@@ -42,7 +42,7 @@ def launch_stubs(obj):
 def test_each_unit_embeds_the_kernels_it_launches(pkg, tmp_path):
     pkg.build()
     objects = sorted(glob.glob(os.path.join(CSRC, "*.o")))
-    assert len(objects) >= 8, objects
+    assert len(objects) >= 11, objects
     kernels = {}
     for obj in objects:
         tmp = tmp_path / os.path.basename(obj)
@@ -50,7 +50,7 @@ def test_each_unit_embeds_the_kernels_it_launches(pkg, tmp_path):
         k = embedded_kernels(obj, str(tmp))
         if k is not None:
             kernels[os.path.basename(obj)] = k
-    assert sorted(kernels) == ["learner.o", "learner_env.o", "learner_io.o"]
+    assert sorted(kernels) == ["learner.o", "learner_env.o", "learner_eval.o", "learner_io.o", "learner_per.o", "learner_save_async.o"]
     for name, embedded in sorted(kernels.items()):
         stubs = launch_stubs(os.path.join(CSRC, name))
         print(name, len(embedded), "kernels embedded,", len(stubs), "launch stubs")
